@@ -8,6 +8,11 @@ the timed region starts (`value`); the same loop with the per-step H2D copy of t
 memory inside the step (async copies on a second stream per slot) is timed right after it and reported as `value_with_h2d` (SURVEY.md 8d's definition).
 Weights are random-init closed-form (no checkpoints available).
 
+A plain run only sets up, warms up, times the `--steps` steps of the resident loop and prints the result line (`value`,
+`ms_per_step`, ...).  Everything else the benchmark measures or checks -- the H2D-inclusive loop, latencies, the per-kernel
+roofline pass, the CPU baseline, the collective probe, the pose sanity check -- runs only with `--full`.
+`--dump-outputs DIR` writes what the timed path computed in its last step as DIR/<name>.npy (see write_outputs).
+
 Multi-GPU: one process per GPU over RCCL.  `python bench.py --gpus N` launches the N ranks itself
 (torch.distributed.run, 127.0.0.1 rendezvous) unless it already runs under a launcher (WORLD_SIZE set).
   --mode frames (default)  frames sharded across ranks, no data-path collective, weak scaling (configs[1]/[3])
@@ -16,6 +21,7 @@ Multi-GPU: one process per GPU over RCCL.  `python bench.py --gpus N` launches t
                            argmin on every rank; strong scaling, collective latency reported
 
     python bench.py --gpus 1 --steps 12 --warmup 3
+    python bench.py --gpus 1 --steps 12 --warmup 3 --full --dump-outputs out/
 """
 import argparse
 import json
@@ -95,12 +101,17 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=None, help="frames per GPU per step (frames: 32, hyp: 16 in total)")
     ap.add_argument("--points", type=int, default=None)
     ap.add_argument("--restarts", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: H2D-inclusive loop, latencies, per-kernel roofline pass, CPU baseline, "
+                         "collective probe, pose check (frames / hyp); the per-call pass, roofline and all-reduce timing (train)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed step as DIR/<name>.npy (float32 / float64, <= 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--train-graph", action="store_true", help="--mode train, one GPU: forward + losses + backward of a step replayed from one hipGraph (ClassifierTrainer.optimize_graphed)")
     ap.add_argument("--streams", type=int, default=None,
                     help="HIP streams = batches in flight (1 = fully serial); default 8 for the frames mode (with GPU_MAX_HW_QUEUES=16, "
                          "set below unless the environment already has it), 3 otherwise")
-    ap.add_argument("--no-h2d-pass", action="store_true", help="skip the second timed loop with the H2D copy inside the step")
+    ap.add_argument("--no-h2d-pass", action="store_true", help="--full without the second timed loop with the H2D copy inside the step")
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel eagerly instead of replaying one captured hipGraph per stream")
     ap.add_argument("--split-solver", action="store_true", help="experiment: classifier and pose solve of a step as two graphs on a high- and a normal-priority stream")
     ap.add_argument("--launch-selftest", action="store_true",
@@ -192,6 +203,31 @@ def broadcast_weights(detector, dist, backend):
         off += n
     detector._invalidate()
     return flat.numel() * 4
+
+
+DUMP_LIMIT_BYTES = (64 << 20) - (1 << 20)     # 64 MB in all, the .npy headers included
+
+
+def write_outputs(path, outputs):
+    """--dump-outputs: every tensor the timed path handed back for its last step, as <path>/<name>.npy -- float64 for fp64 and integer
+    outputs (exact), float32 for the rest.  If they would take more than 64 MB in all, each array above an equal share of that is
+    replaced by a fixed seeded sample of its flattened entries (the same indices in every run with the same arguments).  Rank 0's
+    outputs only.  The inputs are seeded: two builds run with the same arguments can be compared output for output."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, v in sorted(outputs.items()):
+        if torch.is_tensor(v):
+            dt = torch.float32 if v.dtype in (torch.float32, torch.float16, torch.bfloat16) else torch.float64
+            host[name] = v.detach().to(dt).cpu().numpy()
+    share = DUMP_LIMIT_BYTES // max(len(host), 1)
+    sample = sum(a.nbytes for a in host.values()) > DUMP_LIMIT_BYTES
+    for name, a in host.items():
+        if sample and a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def main():
@@ -297,16 +333,53 @@ def main():
     # the two timed loops run back to back on a chip whose clock follows its power / thermal state: DI2P_BENCH_H2D_FIRST=1 swaps their order
     # (a probe: how much of `value_with_h2d / value` is the second loop running on a warmer chip)
     dt_h2d = lat_h2d = None
-    if os.environ.get("DI2P_BENCH_H2D_FIRST") and not args.no_h2d_pass:
+    h2d_pass = args.full and not args.no_h2d_pass
+    if os.environ.get("DI2P_BENCH_H2D_FIRST") and h2d_pass:
         dt_h2d, _, lat_h2d = timed_loop(True)
-        dt, out, lat = timed_loop(False)
-    else:
-        dt, out, lat = timed_loop(False)
-        if not args.no_h2d_pass:
-            dt_h2d, _, lat_h2d = timed_loop(True)
+    dt, out, lat = timed_loop(False)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, out)         # now: the slot's buffers are reused by every later step
+    if h2d_pass and dt_h2d is None:
+        dt_h2d, _, lat_h2d = timed_loop(True)
     use_graph = ex.use_graph
     if ex.graph_error:
         print("hipGraph capture failed (%s); ran eagerly" % ex.graph_error, file=sys.stderr)
+    frames_per_step = B if hyp else B * world
+    frames = frames_per_step * args.steps
+    ms_per_step = dt / args.steps * 1e3
+    placement = [{"rank": rank, "device": local_rank, "device_count": torch.cuda.device_count(), "name": torch.cuda.get_device_name(local_rank)}]
+    if world > 1:
+        gathered = [None] * world
+        dist.all_gather_object(gathered, placement[0])
+        placement = gathered
+    line = {
+        "metric": "frames/sec (img+pc infer + 60-restart GN pose) KITTI 20k-pt, 1/2/4/8 GPU",
+        "schema": 6,
+        "value": frames / dt, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong" if hyp else "weak", "vs_baseline": None,
+        "dtype": "f32 network (fp32-input MFMA; 3x3 convolutions, GEMM-shaped point layers and the per-point head: bf16 MFMA on exact three-way fp32 splits, fp32 accumulation) + f64 solver",
+        "data": "synthetic frames, random-init closed-form weights; solver labels = GT frustum labels with 5% flips (SURVEY 8d)",
+        "config": {"workload": ("BASELINE configs[4]: Oxford-shaped %d-pt / %dx%d, %d frames per step on every rank, coarse classification "
+                                "+ %d 2D GN/LM hypotheses per frame sharded over the ranks, all_gather + argmin" % (N, H, W, B, R)) if hyp else
+                               ("BASELINE configs[1]: KITTI 20480-pt / 160x512, batch %d per GPU, coarse classification "
+                                "+ %d-restart 2D GN/LM solver, max_iter 500" % (B, R)),
+                   "mode": args.mode, "frames_per_gpu_per_step": B, "points": N, "image": [H, W], "restarts": R,
+                   "parallelism": ("hyp%d" if hyp else "dp%d") % world, "streams": n_streams, "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")), "hip_graph": bool(use_graph),
+                   "weights_broadcast_bytes": bcast_bytes, "placement": placement},
+        "full": bool(args.full),
+        "value_resident": frames / dt,
+        "value_definition": "`value` = `value_resident`: every step's inputs are already in HBM when the timed region starts (the bench "
+                            "contract: inputs resident; a PCIe-inclusive rate is never `value`).  `value_with_h2d` (--full) = SURVEY.md 8(d)'s "
+                            "definition of the metric: the same loop with the host->device copy of every batch (50 MB from pinned host "
+                            "memory) inside the step.",
+        "per_rank_ms_per_step": rank_ms or None,
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line))
+        if world > 1:
+            dist.destroy_process_group()
+        return
     # per-batch latency with ONE step in flight (the other end of the throughput / latency trade: `value` keeps n_streams in flight)
     lat1 = None
     if not hyp and n_streams > 1:
@@ -330,9 +403,6 @@ def main():
     torch.cuda.synchronize()
     timed, work = _lib.TIMED, _lib.WORK
     _lib.TIMED = _lib.WORK = None
-    frames_per_step = B if hyp else B * world
-    frames = frames_per_step * args.steps
-    ms_per_step = dt / args.steps * 1e3
 
     fam_ms = {n: sum(e0.elapsed_time(e1) for e0, e1, _ in v) / prof_steps for n, v in timed.items()}
     launches = {n: len(v) // prof_steps for n, v in timed.items()}
@@ -526,34 +596,10 @@ def main():
         # all_gather is timed anyway as a probe of the RCCL / xGMI set-up the ranks run on
         collective = measure_collective(dist, backend, dev, B, R, world)
         collective["in_data_path"] = bool(hyp)
-    placement = [{"rank": rank, "device": local_rank, "device_count": torch.cuda.device_count(), "name": torch.cuda.get_device_name(local_rank)}]
-    if world > 1:
-        gathered = [None] * world
-        dist.all_gather_object(gathered, placement[0])
-        placement = gathered
     if rank == 0:
-        line = {
-            "metric": "frames/sec (img+pc infer + 60-restart GN pose) KITTI 20k-pt, 1/2/4/8 GPU",
-            "schema": 6,
-            "value": frames / dt, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong" if hyp else "weak", "vs_baseline": None,
-            "dtype": "f32 network (fp32-input MFMA; 3x3 convolutions, GEMM-shaped point layers and the per-point head: bf16 MFMA on exact three-way fp32 splits, fp32 accumulation) + f64 solver",
-            "data": "synthetic frames, random-init closed-form weights; solver labels = GT frustum labels with 5% flips (SURVEY 8d)",
-            "config": {"workload": ("BASELINE configs[4]: Oxford-shaped %d-pt / %dx%d, %d frames per step on every rank, coarse classification "
-                                    "+ %d 2D GN/LM hypotheses per frame sharded over the ranks, all_gather + argmin" % (N, H, W, B, R)) if hyp else
-                                   ("BASELINE configs[1]: KITTI 20480-pt / 160x512, batch %d per GPU, coarse classification "
-                                    "+ %d-restart 2D GN/LM solver, max_iter 500" % (B, R)),
-                       "mode": args.mode, "frames_per_gpu_per_step": B, "points": N, "image": [H, W], "restarts": R,
-                       "parallelism": ("hyp%d" if hyp else "dp%d") % world, "streams": n_streams, "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")), "hip_graph": bool(use_graph),
-                       "weights_broadcast_bytes": bcast_bytes, "placement": placement},
-            "value_resident": frames / dt,
+        line.update({
             "value_with_h2d": (frames / dt_h2d) if dt_h2d else None,
             "ms_per_step_with_h2d": (dt_h2d / args.steps * 1e3) if dt_h2d else None,
-            "value_definition": "`value` = `value_resident`: every step's inputs are already in HBM when the timed region starts (the bench "
-                                "contract: inputs resident; a PCIe-inclusive rate is never `value`).  `value_with_h2d` = SURVEY.md 8(d)'s "
-                                "definition of the metric: the same loop with the host->device copy of every batch (50 MB from pinned host "
-                                "memory) inside the step.",
-            "per_rank_ms_per_step": rank_ms or None,
             "latency_ms_per_batch": {"streams_%d" % n_streams: (sum(lat) / len(lat)) if lat else None,
                                      "streams_%d_with_h2d" % n_streams: (sum(lat_h2d) / len(lat_h2d)) if lat_h2d else None,
                                      "one_step_in_flight": (sum(lat1) / len(lat1)) if lat1 else None,
@@ -561,7 +607,7 @@ def main():
                                              "under) and with a single step in flight"},
             "roofline": roofline, "kernels": roofs, "cpu_baseline": cpu_baseline, "collective": collective,
             "pose_check": pose_check(out, batch),
-        }
+        })
         print(json.dumps(line))
     if world > 1:
         dist.destroy_process_group()
@@ -606,7 +652,8 @@ def main_train(args):
     sync_all()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        losses.append(step_fn(*t, K, Pgt)["loss"].clone())
+        L = step_fn(*t, K, Pgt)
+        losses.append(L["loss"].clone())
     t_enqueue = time.perf_counter() - t0          # host time to enqueue the steps (close to dt: the step is launch-bound)
     sync_all()
     dt = time.perf_counter() - t0
@@ -614,6 +661,27 @@ def main_train(args):
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, dict(L, weights=tr.flat))     # the last step's losses, gradients and the weights it left
+    line = {"metric": "training frames/sec (train-mode fwd + focal/CE loss + bwd + gradient all-reduce + Adam) KITTI 20k-pt 160x512, batch %d per GPU" % B,
+            "value": B * world * args.steps / dt, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": 1e3 * dt / args.steps, "host_enqueue_ms_per_step": 1e3 * t_enqueue / args.steps,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32 (fp32-input MFMA contractions; the big point layers and the 256- / 512-channel 3x3 layers, forward and input gradient: bf16 MFMA on exact "
+                     "three-way fp32 splits, fp32 accumulation; fp64 BatchNorm/bias reductions)", "data": "synthetic frames, seeded He-normal initial weights",
+            "config": {"workload": "reference training configuration kitti/options.py:20-60 (batch 8, 20480 pts, 160x512, coarse+fine, Adam 1e-3)",
+                       "mode": "train", "frames_per_gpu_per_step": B, "points": N, "image": [H, W], "parallelism": "dp%d" % world,
+                       "step": "optimize_graphed (forward + losses + backward replayed from one hipGraph)" if step_fn is not tr.optimize else "optimize (eager launches)",
+                       "weights_broadcast_bytes": bcast_bytes},
+            "full": bool(args.full),
+            "gradient_allreduce": {"bytes": int(tr.flat_grad.numel() * 4), "ms": None, "launches_per_step": 1},
+            "loss_first_last": [float(losses[0]), float(losses[-1])]}
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # the gradient exchange on its own (one all-reduce of the flat fp32 buffer), and a serial pass with events around every C-ABI call
     ar_ms = None
@@ -656,21 +724,10 @@ def main_train(args):
                             "BatchNorm statistics / normalisation passes (HBM-bound), routers and the optimiser"}
     if rank == 0:
         top = sorted(fam.items(), key=lambda kv: -kv[1][0])[:10]
-        line = {"metric": "training frames/sec (train-mode fwd + focal/CE loss + bwd + gradient all-reduce + Adam) KITTI 20k-pt 160x512, batch %d per GPU" % B,
-                "value": B * world * args.steps / dt, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-                "ms_per_step": 1e3 * dt / args.steps, "host_enqueue_ms_per_step": 1e3 * t_enqueue / args.steps,
-                "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-                "dtype": "f32 (fp32-input MFMA contractions; the big point layers and the 256- / 512-channel 3x3 layers, forward and input gradient: bf16 MFMA on exact "
-                         "three-way fp32 splits, fp32 accumulation; fp64 BatchNorm/bias reductions)", "data": "synthetic frames, seeded He-normal initial weights",
-                "config": {"workload": "reference training configuration kitti/options.py:20-60 (batch 8, 20480 pts, 160x512, coarse+fine, Adam 1e-3)",
-                           "mode": "train", "frames_per_gpu_per_step": B, "points": N, "image": [H, W], "parallelism": "dp%d" % world,
-                           "step": "optimize_graphed (forward + losses + backward replayed from one hipGraph)" if step_fn is not tr.optimize else "optimize (eager launches)",
-                           "weights_broadcast_bytes": bcast_bytes},
-                "gradient_allreduce": {"bytes": int(tr.flat_grad.numel() * 4), "ms": ar_ms, "launches_per_step": 1},
-                "roofline": roofline,
-                "loss_first_last": [float(losses[0]), float(losses[-1])],
-                "calls_ms_per_step": {k: {"ms": round(v[0], 3), "calls": v[1]} for k, v in top},
-                "note": "calls_ms_per_step: HIP events around every C-ABI call of one extra serial step (ATen views/concatenations excluded)"}
+        line["gradient_allreduce"]["ms"] = ar_ms
+        line.update({"roofline": roofline,
+                     "calls_ms_per_step": {k: {"ms": round(v[0], 3), "calls": v[1]} for k, v in top},
+                     "note": "calls_ms_per_step: HIP events around every C-ABI call of one extra serial step (ATen views/concatenations excluded)"})
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -25,6 +25,8 @@ where /root/reference exists):   python tests/golden/make_golden.py
                          reference's FocalLoss / CrossEntropyLoss assembled as foraward_pass does, then loss.backward():
                          train-mode scores (sub-sampled), losses, and for EVERY parameter the gradient's (l2, sum, abs-max) and 16
                          sampled entries, plus the BatchNorm running buffers after the step (B=2, N=1024, 64x128, coarse+fine)
+  live_reference_golden.npz   the inputs and outputs of the two oracle checks that once imported the reference at test time: the
+                         imported KeypointDetector (coarse+fine, B=1, N=512, 64x64, weights seed 2) and index_max forward_cpu
 Fixtures hold data only (inputs + expected outputs), never reference source.
 """
 import ast
@@ -660,6 +662,33 @@ def make_lsq_restart_driver():
     print("lsq_restart_golden.npz written")
 
 
+def make_live_cases():
+    """The inputs and reference outputs of the two tests that used to need the live reference at test time
+    (test_oracle_network_vs_live_reference, test_index_max_against_live_reference_build): same seeds, same shapes."""
+    out = {}
+    torch.manual_seed(0)
+    N, H, W, B = 512, 64, 64, 1
+    det = rn.load_reference_detector(rn.make_opt(N, H, W, True, B=B))
+    det.load_state_dict(nt.synthetic_state_dict(nt.OptLike(N, H, W, True), seed=2))
+    pc = torch.randn(B, 3, N) * 10
+    args = (pc, torch.rand(B, 1, N), torch.randn(B, 3, N), pc[:, :, :128].contiguous(), pc[:, :, 128:256].contiguous(),
+            torch.rand(B, 3, H, W) * 255)
+    with torch.no_grad():
+        r = det(*args)
+    for k, v in zip(("pc", "intensity", "sn", "node_a", "node_b", "img"), args):
+        out["net_" + k] = v.numpy()
+    out["net_coarse"], out["net_fine"] = r[0].numpy(), r[1].numpy()
+    out["net_meta"] = np.array([B, N, H, W], dtype=np.int32)
+    m = load_ref_index_max()
+    rng = np.random.default_rng(3)
+    data = rng.standard_normal((2, 4, 513)).astype(np.float32)
+    index = rng.integers(0, 20, (2, 513)).astype(np.int32)
+    out["im_data"], out["im_index"], out["im_K"] = data, index, np.int32(24)
+    out["im_out"] = m.forward_cpu(torch.from_numpy(data), torch.from_numpy(index), 24).numpy()
+    np.savez_compressed(os.path.join(HERE, "live_reference_golden.npz"), **out)
+    print("live_reference_golden.npz written")
+
+
 def make_front_ends():
     make_forward_pass()
     make_eval_script()
@@ -683,6 +712,9 @@ if __name__ == "__main__":
     if only == "frontends":
         make_front_ends()
         sys.exit(0)
+    if only == "live":
+        make_live_cases()
+        sys.exit(0)
     make_index_max()
     make_network(True, "network_golden.npz")
     make_network(False, "network_coarse_golden.npz")
@@ -692,3 +724,4 @@ if __name__ == "__main__":
     make_losses()
     make_training()
     make_front_ends()
+    make_live_cases()

@@ -80,7 +80,7 @@ def test_single_rank_needs_no_process_group():
 def test_two_ranks_full_path_on_one_device(mode):
     """Both modes end to end with 2 ranks (gloo, shared device): frames = weak scaling (2 x batch), hyp = the same frames on
     both ranks, hypotheses sharded, all_gather + argmin."""
-    args = [sys.executable, BENCH, "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--mode", mode]
+    args = [sys.executable, BENCH, "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--mode", mode]
     args += ["--batch", "4"] if mode == "frames" else ["--batch", "2", "--points", "8192", "--restarts", "24"]
     r = subprocess.run(args, env=_env(DI2P_BENCH_ONE_DEVICE="1"), capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -95,10 +95,31 @@ def test_two_ranks_full_path_on_one_device(mode):
 def test_two_ranks_training_step_on_one_device():
     """--mode train with 2 ranks (gloo, shared device): data-parallel optimisation steps with one all-reduce of the flat gradient
     buffer per step; both ranks keep identical weights, the loss falls."""
-    args = [sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--mode", "train", "--batch", "2", "--points", "2048"]
+    args = [sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--mode", "train", "--batch", "2", "--points", "2048"]
     r = subprocess.run(args, env=_env(DI2P_BENCH_ONE_DEVICE="1"), capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     line = _last_json(r.stdout)
     assert line["n_gpus"] == 2 and line["config"]["mode"] == "train" and line["value"] > 0
     assert line["gradient_allreduce"]["bytes"] > 1e8 and line["gradient_allreduce"]["ms"] > 0
     assert line["loss_first_last"][1] < line["loss_first_last"][0]
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_and_dumps_its_outputs(tmp_path):
+    """Without --full: the headline line alone (no roofline / kernel / CPU-baseline pass), and --dump-outputs writes the last timed
+    step's outputs as float32 / float64 arrays."""
+    args = [sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2", "--points", "2048", "--restarts", "8",
+            "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(args, env=_env(), capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = _last_json(r.stdout)
+    assert line["full"] is False and line["steps"] == 3 and line["value"] > 0 and line["higher_is_better"] is True
+    assert abs(line["ms_per_step"] - 1e3 * line["config"]["frames_per_gpu_per_step"] / line["value"]) <= 1e-6 * line["ms_per_step"]
+    assert not {"kernels", "roofline", "cpu_baseline", "pose_check", "value_with_h2d"} & set(line)
+    import numpy as np
+    files = sorted(os.listdir(tmp_path / "out"))
+    assert {"P.npy", "cost.npy", "pred.npy", "labels_front.npy"} <= set(files)
+    arrays = {f: np.load(tmp_path / "out" / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert arrays["P.npy"].shape == (2, 4, 4) and arrays["pred.npy"].shape == (2, 2048)

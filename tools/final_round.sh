@@ -25,8 +25,8 @@ if [ "$STAGE" = "counters" ]; then
   exit 0
 fi
 timeout 900 python -m pytest tests -q -m gpu 2>&1 | tail -3 > $OUT/${TAG}_gputest_tail.txt
-timeout 400 python bench.py > $OUT/${TAG}_bench_line.json 2> $OUT/${TAG}_bench.err
-timeout 200 python bench.py --mode train --steps 6 --warmup 2 > $OUT/${TAG}_train_line.json 2>> $OUT/${TAG}_bench.err
+timeout 400 python bench.py --full > $OUT/${TAG}_bench_line.json 2> $OUT/${TAG}_bench.err
+timeout 200 python bench.py --full --mode train --steps 6 --warmup 2 > $OUT/${TAG}_train_line.json 2>> $OUT/${TAG}_bench.err
 timeout 100 python tools/bench_index_max.py > $OUT/${TAG}_index_max_cold.txt 2>&1
 timeout 300 python tools/bench_conv_x3.py 2>&1 | grep -v amdgpu.ids > $OUT/${TAG}_conv_layers.txt
 timeout 100 python tools/diag_conv_x3_accuracy.py 2>&1 | grep -v amdgpu.ids > $OUT/${TAG}_conv_x3_accuracy.txt
@@ -41,6 +41,6 @@ timeout 200 python tools/call_times.py 15 > $OUT/${TAG}_call_times.txt 2>&1
 timeout 200 bash tools/sweep_streams2.sh > $OUT/${TAG}_sweep_streams.txt 2>&1
 timeout 200 bash tools/probe_additivity.sh > $OUT/${TAG}_additivity.txt 2>&1
 export TMPDIR=/tmp; ROOT=$(pwd); cd /tmp; rm -rf /tmp/pt
-timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pt -- python $ROOT/bench.py --mode train --steps 4 --warmup 2 > /tmp/pt.log 2>&1
+timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pt -- python $ROOT/bench.py --full --mode train --steps 4 --warmup 2 > /tmp/pt.log 2>&1
 f=$(find /tmp/pt -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $ROOT/$OUT/${TAG}_train_kernel_stats.csv
 cd $ROOT; cat $OUT/${TAG}_gputest_tail.txt; head -c 600 $OUT/${TAG}_bench_line.json; echo; ls $OUT | grep "^${TAG}_" | tr '\n' ' '

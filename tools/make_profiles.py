@@ -119,7 +119,7 @@ micro-benchmarks, `tools/profile_round.sh {TAG}`) at the end of the round and tu
 files listed in KEEP_OLD (if present) come from earlier calls of the round.
 
 * `{TAG}_gputest_tail.txt` -- `python -m pytest tests -q -m gpu`: {gt}.
-* `{TAG}_bench_line.json` -- the JSON line of `python bench.py` ({line['steps']} steps, {line['warmup']} warm-up, {line['config']['streams']} streams on {line['config']['hw_queues']} hardware queues, one hipGraph per stream, CPU baseline
+* `{TAG}_bench_line.json` -- the JSON line of `python bench.py --full` ({line['steps']} steps, {line['warmup']} warm-up, {line['config']['streams']} streams on {line['config']['hw_queues']} hardware queues, one hipGraph per stream, CPU baseline
   leg included): **{line['value']:.0f} frames/s** resident ({line['ms_per_step']:.2f} ms per 32-frame step), {line['value_with_h2d']:.0f} frames/s with the
   host->device copy of every batch inside the step; device time of one batch {line['latency_ms_per_batch']['streams_%d' % line['config']['streams']]:.1f} ms with all streams busy,
   {line['latency_ms_per_batch']['one_step_in_flight']:.1f} ms with a single step in flight.  Roofline object = time-dominant family = `solve_kernel`:
@@ -130,7 +130,7 @@ files listed in KEEP_OLD (if present) come from earlier calls of the round.
   {cv['winograd']['stem_kernel_ms_per_step']:.2f} ms); pointwise {pw['ms_per_step']:.2f} ms ({pw['achieved_executed']:.0f} TFLOP/s executed = {pw['frac']:.2f} of the matrix pipes its launches run on; {pw['achieved_reference_algorithmic']:.0f} TFLOP/s by the reference's layer sizes); index_max
   {k['index_max_kernel']['ms_per_step']*1e3:.0f} us in-pipeline ({k['index_max_kernel']['achieved']:.0f} GB/s).  CPU baseline: {line['cpu_baseline']['value']:.3f} frames/s on {line['cpu_baseline']['cores']} threads.
 * `{TAG}_bench_kernel_stats_pipelined.csv` / `{TAG}_bench_line_pipelined.json` -- `rocprofv3 --kernel-trace --stats --output-format csv --
-  python bench.py --no-cpu-baseline --no-h2d-pass` ({s3['value']:.0f} frames/s under the profiler); several batches in flight: durations include
+  python bench.py --full --no-cpu-baseline --no-h2d-pass` ({s3['value']:.0f} frames/s under the profiler); several batches in flight: durations include
   contention.
 * `{TAG}_bench_kernel_stats_serial.csv` / `{TAG}_bench_line_serial.json` -- the same with `--streams 1` ({ser['value']:.0f} frames/s): durations without
   contention.  `solve_kernel` averages {avg('solve_kernel')/1e3:.2f} ms (rocprof) against {ser['kernels']['solve_kernel']['ms_per_step']:.2f} ms from the HIP events of the same run's JSON
@@ -173,7 +173,7 @@ files listed in KEEP_OLD (if present) come from earlier calls of the round.
 * `{TAG}_step_instructions.txt` -- `tools/prof_step_instructions.sh`: VALU / MFMA / SALU / LDS wave-instruction counters of every kernel of a step
   (what the 8-stream step time is bounded by: DESIGN.md section 4).
 * `{TAG}_index_max_cold.txt` -- cache-cold index_max.
-* `{TAG}_train_line.json`, `{TAG}_train_kernel_stats.csv` -- `python bench.py --mode train` (reference training configuration: batch 8, 20480
+* `{TAG}_train_line.json`, `{TAG}_train_kernel_stats.csv` -- `python bench.py --full --mode train` (reference training configuration: batch 8, 20480
   points, 160x512, coarse+fine): **{tr['ms_per_step']:.1f} ms per step = {tr['value']:.0f} frames/s**,
   and `rocprofv3 --kernel-trace --stats` of the same command.
 

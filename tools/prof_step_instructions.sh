@@ -9,7 +9,7 @@ cd /tmp
 i=0
 for set in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR" "SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_WAVES SQ_BUSY_CYCLES" "GRBM_GUI_ACTIVE"; do
   i=$((i+1)); rm -rf /tmp/si$i
-  timeout 300 rocprofv3 --pmc $set --kernel-trace --output-format csv -d /tmp/si$i -- python $ROOT/bench.py --no-cpu-baseline --no-h2d-pass --no-graph --streams 1 --steps 4 --warmup 2 > /tmp/si$i.log 2>&1
+  timeout 300 rocprofv3 --pmc $set --kernel-trace --output-format csv -d /tmp/si$i -- python $ROOT/bench.py --full --no-cpu-baseline --no-h2d-pass --no-graph --streams 1 --steps 4 --warmup 2 > /tmp/si$i.log 2>&1
   f=$(find /tmp/si$i -name "*counter_collection.csv" | head -1)
   [ -n "$f" ] && cp $f /tmp/si_pass$i.csv || { echo "pass $i ($set) failed"; tail -3 /tmp/si$i.log; }
 done

@@ -14,7 +14,7 @@ cd /tmp
 stats() {  # name, args...
   local name=$1; shift
   rm -rf $OUT/prof_$TAG/$name
-  timeout 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG/$name -- python $ROOT/bench.py --no-cpu-baseline "$@" > $OUT/prof_$TAG/$name.log 2>&1
+  timeout 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG/$name -- python $ROOT/bench.py --full --no-cpu-baseline "$@" > $OUT/prof_$TAG/$name.log 2>&1
   f=$(find $OUT/prof_$TAG/$name -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && cp $f $OUT/${TAG}_bench_kernel_stats_$name.csv
   grep '^{' $OUT/prof_$TAG/$name.log | tail -1 > $OUT/${TAG}_bench_line_$name.json
