@@ -39,6 +39,13 @@ class HeadX3T(ctypes.Structure):      # di2p_head_x3_t
                 ("W2t", c_void_p), ("scale2", c_void_p), ("shift2", c_void_p), ("relu2", c_int), ("P", c_int)]
 
 
+class HeadLabelsX3T(ctypes.Structure):      # di2p_head_labels_x3_t
+    _fields_ = [("y0", c_void_p), ("batch_stride", c_ll), ("row_stride", c_int), ("K", c_int),
+                ("W1p", c_void_p), ("scale1", c_void_p), ("shift1", c_void_p), ("relu1", c_int),
+                ("W2p", c_void_p), ("scale2", c_void_p), ("shift2", c_void_p), ("P", c_int),
+                ("scores", c_void_p), ("coarse", c_void_p), ("fine", c_void_p)]
+
+
 SRC_DENSE, SRC_GATHER, SRC_GROUP = 0, 1, 2
 
 # name -> argtypes (all return int)
@@ -103,6 +110,8 @@ _SIGS = {
     "di2p_stem_x3_supported": [c_int, c_int],
     "di2p_stem_x3": [c_void_p] * 5 + [c_int] * 3 + [c_void_p],
     "di2p_point_head_x3": [ctypes.POINTER(HeadX3T), c_void_p, c_int, c_int, c_void_p],
+    "di2p_head_labels_x3_pack": [c_void_p, c_int, c_int, c_void_p, c_void_p],
+    "di2p_point_head_labels_x3": [ctypes.POINTER(HeadLabelsX3T), c_int, c_int, c_void_p],
     "di2p_bn_train_forward": [c_void_p] * 9 + [c_float, c_float, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "di2p_bn_train_backward": [c_void_p] * 6 + [c_int] + [c_void_p] * 4 + [c_int, c_int, c_int, c_void_p, c_void_p],
     "di2p_channel_sum": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
@@ -126,6 +135,7 @@ _WS_SIGS = {        # <name>_workspace_bytes helpers returning long long
     "di2p_bf16x3_packed_bytes": [c_int] * 2,
     "di2p_bf16x3_planes_bytes": [c_int] * 3,
     "di2p_head_x3_packed_bytes": [c_int],
+    "di2p_head_labels_x3_packed_bytes": [c_int, c_int],
     "di2p_stem_x3_packed_bytes": [],
 }
 EXPORTS = sorted(list(_SIGS) + ["di2p_last_error", "di2p_version", "di2p_solve_workspace_bytes", "di2p_solver_set_profile_buffer", "di2p_pnp_workspace_bytes",

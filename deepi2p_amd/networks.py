@@ -426,10 +426,59 @@ class KeypointDetector(_PackedModule):
                 p["head_x3"] = {"W0p": ops.head_x3_pack(l0[0][640:736].contiguous()), "W1p": ops.head_x3_pack(l1[0]),
                                 "ss": torch.stack((l0[1] if l0[1] is not None else ones, l0[2], l1[1] if l1[1] is not None else ones, l1[2])).contiguous(),
                                 "relu0": l0[3], "relu1": l1[3], "W2t": l2[0], "sc2": l2[1], "sh2": l2[2], "relu2": l2[3]}
+            # the fine head's labels-only tail (di2p_point_head_labels_x3: layers 1-2 + both argmaxes in one launch): layer 1 and layer 2 split
+            # once into fragment order, owned and invalidated with the weights like every derived operand
+            if (l0[0].is_cuda and l0[0].shape[1] == 256 and tuple(l1[0].shape) == (256, 256) and l2[0].shape[0] == 256 and l2[0].shape[1] >= 3
+                    and not l2[3] and not l0[0].requires_grad):
+                p["head_labels_x3"] = {"W1p": ops.head_labels_pack(l1[0]), "W2p": ops.head_labels_pack(l2[0]), "P": int(l2[0].shape[1]),
+                                       "sc1": l1[1] if l1[1] is not None else torch.ones(256, device=l1[0].device), "sh1": l1[2],
+                                       "relu1": l1[3], "sc2": l2[1], "sh2": l2[2]}
             self._packed = p
         return self._packed
 
     def forward(self, pc, intensity, sn, node_a, node_b, img):
+        p, B, N, first, second, idx_a, idx_pb, gathered = self._trunk(pc, intensity, sn, node_a, node_b, img)
+        Wt, sc, sh, act = p["per_point_pn"][0]
+        M0 = Wt.shape[1]
+        G_a, ex_w_a = gathered[0][0], gathered[0][2]
+        G_b, w_pb = gathered[1][0], gathered[1][2]
+        l1, l2 = p["per_point_pn"][1], p["per_point_pn"][2]
+        if ("head_x3" in p and self.fuse_head and _lib.get_option("head_x3") and first.shape[1] == 32 and second.shape[1] == 64
+                and idx_a.shape[-1] == 3 and idx_pb.shape[-1] == 3):
+            # coarse head, round 5: one wave-autonomous launch on the bf16 matrix instructions (exact three-way splits), node tables in LDS
+            scores = ops.point_head_x3(first, second, p["head_x3"],
+                                       [(G_a, idx_a.reshape(B, N, 3), ex_w_a), (G_b, idx_pb.reshape(B, N, 3), w_pb)], N)
+        elif M0 == 128 and l1[0].shape[1] == 128 and l2[0].shape[1] <= 4 and N % 4 == 0 and self.fuse_head:
+            # coarse head: the three layers in one launch, hidden activations stay in LDS (bit-identical to the chain below)
+            scores = ops.point_head([Src(first), Src(second)], (Wt[640:736], sc, sh, act), l1, l2, N, gathered=gathered)
+        else:
+            h = ops.pointwise_gemm([Src(first), Src(second)], Wt[640:736], M0, N, scale=sc, shift=sh, relu=act, gathered=gathered)
+            # the coarse chain is the bit-exact reference of the fused kernel (fp32 matrix instructions): not on the bf16x3 kernel
+            scores = _run_pn(h, p["per_point_pn"][1:], x3=False if M0 == 128 else None)
+        coarse = scores[:, 0:2, :]
+        if self.opt.is_fine_resolution:
+            return coarse, scores[:, 2:, :]
+        return coarse
+
+    def predict_labels(self, pc, intensity, sn, node_a, node_b, img, scores_out=None):
+        """The labels the registration back ends consume, without the score tensor: (coarse i32[B,N], fine i32[B,N]) -- argmax_channels of
+        forward()'s two outputs, up to the rounding of the fine head's layers 1-2, which run with both argmaxes as ONE launch
+        (di2p_point_head_labels_x3: bf16 matrix instructions on exact three-way splits).  scores_out: optional f32[B,2+L,N] the kernel also
+        writes the scores into.  A coarse-only model returns (argmax_channels(forward(...)), None)."""
+        if not self.opt.is_fine_resolution:
+            return ops.argmax_channels(self.forward(pc, intensity, sn, node_a, node_b, img)), None
+        p, B, N, first, second, idx_a, idx_pb, gathered = self._trunk(pc, intensity, sn, node_a, node_b, img)
+        Wt, sc, sh, act = p["per_point_pn"][0]
+        M0 = Wt.shape[1]
+        h = ops.pointwise_gemm([Src(first), Src(second)], Wt[640:736], M0, N, scale=sc, shift=sh, relu=act, gathered=gathered)
+        if "head_labels_x3" not in p:
+            raise RuntimeError("predict_labels: the fine head has no labels-only kernel for per_point_pn %s"
+                               % [tuple(l[0].shape) for l in p["per_point_pn"]])
+        return ops.point_head_labels(h, p["head_labels_x3"], N, scores_out=scores_out)
+
+    def _trunk(self, pc, intensity, sn, node_a, node_b, img):
+        """Everything of forward() up to the per-point head: the encoders, the attention / node branches and the per-node products of the
+        head's layer 0.  -> (packed operands, B, N, first, second, idx_a, idx_pb, gathered tables)."""
         ops.require_cuda(pc, intensity, sn, node_a, node_b, img)
         p = self._pack()
         B, N, Ma, Mb = pc.size(0), pc.size(2), node_a.size(2), node_b.size(2)
@@ -472,23 +521,7 @@ class KeypointDetector(_PackedModule):
         G_a = ops.pointwise_gemm([Src(up_a)], Wt[0:128], M0, Ma, transpose_out=True)     # [B,Ma,M0] node-major
         G_b = ops.pointwise_gemm([Src(up_b)], Wt[128:640], M0, Mb, transpose_out=True)
         gathered = [(G_a, idx_a, ex["w_a"]), (G_b, idx_pb, w_pb)]
-        l1, l2 = p["per_point_pn"][1], p["per_point_pn"][2]
-        if ("head_x3" in p and self.fuse_head and _lib.get_option("head_x3") and first.shape[1] == 32 and second.shape[1] == 64
-                and idx_a.shape[-1] == 3 and idx_pb.shape[-1] == 3):
-            # coarse head, round 5: one wave-autonomous launch on the bf16 matrix instructions (exact three-way splits), node tables in LDS
-            scores = ops.point_head_x3(first, second, p["head_x3"],
-                                       [(G_a, idx_a.reshape(B, N, 3), ex["w_a"]), (G_b, idx_pb.reshape(B, N, 3), w_pb)], N)
-        elif M0 == 128 and l1[0].shape[1] == 128 and l2[0].shape[1] <= 4 and N % 4 == 0 and self.fuse_head:
-            # coarse head: the three layers in one launch, hidden activations stay in LDS (bit-identical to the chain below)
-            scores = ops.point_head([Src(first), Src(second)], (Wt[640:736], sc, sh, act), l1, l2, N, gathered=gathered)
-        else:
-            h = ops.pointwise_gemm([Src(first), Src(second)], Wt[640:736], M0, N, scale=sc, shift=sh, relu=act, gathered=gathered)
-            # the coarse chain is the bit-exact reference of the fused kernel (fp32 matrix instructions): not on the bf16x3 kernel
-            scores = _run_pn(h, p["per_point_pn"][1:], x3=False if M0 == 128 else None)
-        coarse = scores[:, 0:2, :]
-        if self.opt.is_fine_resolution:
-            return coarse, scores[:, 2:, :]
-        return coarse
+        return p, B, N, first, second, idx_a, idx_pb, gathered
 
     def intermediates(self, pc, intensity, sn, node_a, node_b, img):
         """Test hook: the materialised per-stage tensors the reference would produce."""
@@ -583,6 +616,11 @@ class MMClassifer:
         """Device-resident variant of inference_pass: coarse argmax as i32 [B,N] (what the solver consumes)."""
         out = self.forward(self.pc, self.intensity, self.sn, self.node_a, self.node_b, self.img)
         return ops.argmax_channels(out[0] if self.opt.is_fine_resolution else out)
+
+    def inference_labels_fine(self):
+        """Both labels (coarse i32[B,N], fine i32[B,N]) on the inputs of set_input, through KeypointDetector.predict_labels: the fine head's
+        layers 1-2 and both argmaxes as one launch, no score tensor.  A coarse-only model gives (coarse, None)."""
+        return self.detector.predict_labels(self.pc, self.intensity, self.sn, self.node_a, self.node_b, self.img)
 
     def inference_pass(self):
         out = self.forward(self.pc, self.intensity, self.sn, self.node_a, self.node_b, self.img)

@@ -459,6 +459,59 @@ def point_head_x3(src0, src1, packed, gathered, N):
     return out
 
 
+def head_labels_pack(Wt):
+    """Wt f32[K,M] (contiguous, K % 16 == 0) -> the fragment-ordered split operand of di2p_point_head_labels_x3 (uint8 storage; rows padded to
+    a multiple of 32 with zeros)."""
+    require_cuda(Wt)
+    _chk(Wt, _f32, "head_labels_pack weights")
+    if Wt.dim() != 2 or Wt.shape[0] % 16 or Wt.shape[0] < 16:
+        raise RuntimeError("head_labels_pack needs a contiguous f32[K,M] with K % 16 == 0")
+    K, M = int(Wt.shape[0]), int(Wt.shape[1])
+    Wp = torch.empty((_lib.load().di2p_head_labels_x3_packed_bytes(K, M),), dtype=torch.uint8, device=Wt.device)
+    call("di2p_head_labels_x3_pack", ptr(Wt), K, M, ptr(Wp), stream())
+    return Wp
+
+
+def point_head_labels(y0, packed, N, scores_out=None):
+    """Layers 1-2 of the fine per-point head and both argmaxes in one launch (di2p_point_head_labels_x3).  y0: layer 0's output f32[B,256,N]
+    (unit column stride); packed: dict W1p, W2p (head_labels_pack of W1t f32[256,256] and W2t f32[256,P]), P, sc1, sh1 f32[256], relu1,
+    sc2 / sh2 f32[P] or None.  scores_out: an f32[B,P,N] tensor the kernel also writes the scores into (None: no scores).
+    -> (coarse i32[B,N], fine i32[B,N]) with the argmax semantics of argmax_channels on the same scores."""
+    require_cuda(y0, packed["W1p"], packed["W2p"], packed["sc1"], packed["sh1"], packed["sc2"], packed["sh2"], scores_out)
+    _chk(y0, _f32, "point_head_labels y0")
+    P = int(packed["P"])
+    if y0.dim() != 3 or y0.shape[1] != 256 or y0.shape[2] != N or y0.stride(2) != 1:
+        raise RuntimeError("point_head_labels: y0 must be f32[B,256,N] with unit column stride")
+    B = int(y0.shape[0])
+    # raw pointers below: the packs must be the ones made for THIS head, the small operands fp32 of the right size
+    hb = _lib.load().di2p_head_labels_x3_packed_bytes
+    if P < 3 or packed["W1p"].numel() * packed["W1p"].element_size() != hb(256, 256) or packed["W2p"].numel() * packed["W2p"].element_size() != hb(256, P):
+        raise RuntimeError("point_head_labels: W1p / W2p must be head_labels_pack of the [256,256] layer 1 and of the [256,%d] layer 2 (P >= 3)" % P)
+    for name, n in (("sc1", 256), ("sh1", 256), ("sc2", P), ("sh2", P)):
+        if packed[name] is None:
+            if name in ("sc2", "sh2"):                    # the output layer may come without scale / shift
+                continue
+            raise RuntimeError("point_head_labels: %s is required" % name)
+        _chk(packed[name], _f32, "point_head_labels " + name)
+        if packed[name].numel() != n:
+            raise RuntimeError("point_head_labels: %s holds %d values, needs %d" % (name, packed[name].numel(), n))
+    if scores_out is not None:
+        _chk(scores_out, _f32, "point_head_labels scores_out")
+        if tuple(scores_out.shape) != (B, P, N) or scores_out.device != y0.device:
+            raise RuntimeError("point_head_labels: scores_out must be f32[%d,%d,%d] on the device of y0" % (B, P, N))
+    h = _lib.HeadLabelsX3T()
+    h.y0, h.batch_stride, h.row_stride, h.K = ptr(y0), y0.stride(0), y0.stride(1), 256
+    h.W1p, h.scale1, h.shift1, h.relu1 = ptr(packed["W1p"]), ptr(packed["sc1"]), ptr(packed["sh1"]), int(bool(packed["relu1"]))
+    h.W2p, h.scale2, h.shift2, h.P = ptr(packed["W2p"]), ptr(packed["sc2"]), ptr(packed["sh2"]), P
+    coarse = torch.empty((B, N), dtype=_i32, device=y0.device)
+    fine = torch.empty((B, N), dtype=_i32, device=y0.device)
+    h.scores, h.coarse, h.fine = ptr(scores_out), ptr(coarse), ptr(fine)
+    if _lib.WORK is not None:
+        _lib.WORK["di2p_point_head_labels_x3"] = _lib.WORK.get("di2p_point_head_labels_x3", 0) + B * N * 256 * (256 + P)
+    call("di2p_point_head_labels_x3", ctypes.byref(h), B, N, stream())
+    return coarse, fine
+
+
 def point_chain_ok(srcs, layers, N):
     """Can di2p_point_chain run these layers ((Wt, scale, shift, relu) tuples; layers[0].Wt holds the rows of the dense `srcs`)?"""
     if len(layers) not in (2, 3) or len(srcs) != 1 or _lib.get_option("pw_nochain"):

@@ -79,10 +79,28 @@ class RegistrationExecutor:
     submit re-packs the kernel operands and re-captures the graphs instead of replaying against freed or stale operands.
 
     labels_override: i32[B,N] device tensor fed to the solver INSTEAD of the network's argmax (the benchmark's synthetic labels,
-    SURVEY.md 8d: random-init weights predict nothing); default None = the network's own prediction, as the reference does."""
+    SURVEY.md 8d: random-init weights predict nothing); default None = the network's own prediction, as the reference does.
+
+    PnP mode (``pipe`` a deepi2p_amd.registration_pnp.PnPPipeline; ``mm`` must have the fine head, else ValueError): the network part of a
+    step is ``mm.detector.predict_labels`` (layers 1-2 of the fine head and both argmaxes as one launch), the solve part
+    ``pipe(pc, coarse, fine, K, samples)``; ``samples`` (i32[B,iters,6]) plays the role of ``restarts`` (one draw per executor, by
+    ``pipe.draw`` when not given) and ``labels_override`` is a (coarse, fine) pair of i32[B,N].  Results: pred (coarse), fine_pred, P,
+    outlier_ratio, n_inliers, n_corr, best.  Graphs, copy streams, double buffering, weight following and ``split_solver`` work as in the
+    Gauss-Newton mode."""
 
     def __init__(self, mm, pipe, K, example_batch, n_streams=8, use_graph=True, restarts=None, labels_override=None, step_fn=None,
-                 post_fn=None, h2d_mode="copy_stream", split_solver=False, double_buffer=False):
+                 post_fn=None, h2d_mode="copy_stream", split_solver=False, double_buffer=False, samples=None):
+        from .registration_pnp import PnPPipeline
+        self.pnp = isinstance(pipe, PnPPipeline)
+        if self.pnp:
+            if not getattr(mm.opt, "is_fine_resolution", False):
+                raise ValueError("a PnPPipeline needs the fine labels: mm must be a coarse+fine MMClassifer, not a coarse-only model")
+            if labels_override is not None and (not isinstance(labels_override, (tuple, list)) or len(labels_override) != 2):
+                raise ValueError("in PnP mode labels_override is a (coarse, fine) pair of i32[B,N] device tensors")
+            if restarts is not None:
+                raise ValueError("in PnP mode the RANSAC draws are passed as `samples`, not `restarts`")
+        elif samples is not None:
+            raise ValueError("`samples` (RANSAC draws) needs a PnPPipeline; the Gauss-Newton pipeline takes `restarts`")
         self.mm, self.pipe = mm, pipe
         self.device = mm.device
         self.n_streams = max(1, int(n_streams))
@@ -94,6 +112,8 @@ class RegistrationExecutor:
             self.K64 = self.K64.unsqueeze(0).expand(B, 3, 3).contiguous()
         if tuple(self.K64.shape) != (B, 3, 3):
             raise ValueError("K must be [3,3] or [B,3,3] with B = %d frames, got %s" % (B, tuple(K.shape)))
+        if self.pnp:
+            restarts = samples
         self.restarts = restarts if restarts is not None else pipe.draw(B, self.device)
         self.step_fn = step_fn            # custom graph-capturable step: step_fn(slot, device_inputs) -> outputs dict
         self.post_fn = post_fn            # launched EAGERLY on the slot's stream after the step (work that cannot be captured, e.g. a
@@ -165,6 +185,10 @@ class RegistrationExecutor:
 
     def _net_part(self, slot):
         d = slot.dev
+        if self.pnp:
+            # both labels from one launch after layer 0 of the fine head (no score tensor)
+            coarse, fine = self.mm.detector.predict_labels(d["pc"], d["intensity"], d["sn"], d["node_a"], d["node_b"], d["img"])
+            return {"pred": coarse, "fine_pred": fine}
         logits = self.mm.detector(d["pc"], d["intensity"], d["sn"], d["node_a"], d["node_b"], d["img"])
         coarse = logits[0] if isinstance(logits, tuple) else logits
         net = {"pred": ops.argmax_channels(coarse)}                          # inference_pass (:100-117): i32 [B,N]
@@ -174,6 +198,11 @@ class RegistrationExecutor:
 
     def _solve_part(self, slot, net):
         d = slot.dev
+        if self.pnp:
+            coarse, fine = self.labels_override if self.labels_override is not None else (net["pred"], net["fine_pred"])
+            out = self.pipe(d["pc"], coarse, fine, d[K_NAME], self.restarts)      # same stream: PnP follows its classification
+            out.update(net)
+            return out
         labels = self.labels_override if self.labels_override is not None else net["pred"]
         out = self.pipe(d["pc"], labels, d[K_NAME], self.restarts)           # same stream: the pose solve follows its classification
         out.update(net)

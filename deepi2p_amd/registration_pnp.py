@@ -91,3 +91,35 @@ def solve_PnP(pc_np, coarse_predictions_np, fine_predictions_np, K_np, H, W, fin
                      method="dlt_lo" if method == "dlt_lo" else "epnp")
     ratio = float(out["outlier_ratio"][0])
     return out["P"][0].cpu().numpy(), (1 if ratio == 1.0 else ratio)
+
+
+class PnPPipeline:
+    """Device-resident labels -> pose by PnP for a batch of frames (the reference's second back end, registration_pnp.py:95-148): what
+    RegistrationPipeline is for the Gauss-Newton solve, for pipeline.RegistrationExecutor.  Fixed per pipeline: the image size, the fine
+    grid (fine_resolution_scale, the reference's 1/32), the RANSAC settings; per call: the frames, their labels, K and the draws."""
+
+    def __init__(self, H, W, fine_resolution_scale=1 / 32, iterations=500, reproj_err=0.6, method="epnp", seed=0):
+        if method not in ("epnp", "dlt_lo"):
+            raise ValueError("method must be 'epnp' or 'dlt_lo'")
+        self.H, self.W, self.scale = H, W, float(fine_resolution_scale)
+        self.W_fine = int(round(W * self.scale))
+        self.H_fine = int(round(H * self.scale))
+        self.iterations, self.reproj_err, self.method = int(iterations), float(reproj_err), method
+        self.rng = np.random.default_rng(seed)
+
+    def draw(self, F, device):
+        """RANSAC samples i32[F, iterations, 6] from the pipeline's seeded generator (draw_samples)."""
+        return torch.as_tensor(draw_samples(self.rng, F, self.iterations), device=device)
+
+    def scale_K(self, K):
+        """camera_matrix_scaling of every frame's K f64[F,3,3], on the device (no host round trip; capture-safe)."""
+        Ks = K.to(torch.float64) * self.scale
+        Ks[:, 2, 2] = 1.0
+        return Ks
+
+    def __call__(self, pc, coarse, fine, K, samples, pixels=None):
+        """pc f32[F,3,N], coarse / fine i32[F,N], K f64[F,3,3] (full-resolution camera), samples i32[F,iters,6]
+        -> dict(P f64[F,4,4], outlier_ratio f64[F], n_inliers, n_corr, best i32[F]); a frame without an accepted pose comes back as identity
+        with outlier ratio 1 (the reference's acceptance rules, registration_pnp.py:123-148, inside the kernels)."""
+        return pnp_ransac(pc, coarse, fine, self.scale_K(K), self.W_fine, samples, reproj_err=self.reproj_err, pixels=pixels,
+                          method=self.method)

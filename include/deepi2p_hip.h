@@ -241,6 +241,22 @@ typedef struct {
 long long di2p_head_x3_packed_bytes(int K);
 int di2p_head_x3_pack(const float* Wt, int K, void* Wp, void* stream);
 int di2p_point_head_x3(const di2p_head_x3_t* h, float* out, int B, int N, void* stream);
+/* The labels-only tail of the FINE per-point head (per_point_pn of fine models, 736 -> 256 -> 256 -> P = 2 + L; the two argmaxes of
+ * models/multimodal_classifier.py:100-117) in ONE launch on the bf16 matrix instructions with exact three-way fp32 splits:
+ *   y1 = relu?(scale1 * W1 y0 + shift1);  s = scale2? * W2 y1 + shift2?;  coarse = argmax(s[0:2]), fine = argmax(s[2:P])  (int32 [B,N])
+ * y0 = layer 0's output f32[B, K, N] (row stride >= N, batch stride >= K * row stride); this build runs K = 256 and any P >= 3.  Weights:
+ * di2p_head_labels_x3_pack of W1t f32[K][K] and of W2t f32[K][P] (k-major; di2p_head_labels_x3_packed_bytes(K, M) bytes each, 16-byte aligned);
+ * scale1 / shift1 f32[K] (required), scale2 / shift2 f32[P] or NULL.  scores: f32[B,P,N] or NULL (no score tensor is written).  Argmax
+ * semantics of di2p_argmax_channels on the same scores: the first maximum wins, NaN ranks above everything (the first NaN wins). */
+typedef struct {
+    const float* y0; long long batch_stride; int row_stride; int K;
+    const void* W1p; const float* scale1; const float* shift1; int relu1;
+    const void* W2p; const float* scale2; const float* shift2; int P;
+    float* scores; int32_t* coarse; int32_t* fine;
+} di2p_head_labels_x3_t;
+long long di2p_head_labels_x3_packed_bytes(int K, int P);
+int di2p_head_labels_x3_pack(const float* Wt, int K, int P, void* Wp, void* stream);
+int di2p_point_head_labels_x3(const di2p_head_labels_x3_t* h, int B, int N, void* stream);
 /* 3x3 convolutions (pad 1, stride 1 or 2) on the bf16 matrix instructions with the EXACT three-way fp32 split of both operands ("bf16x3",
  * see di2p_pointwise_gemm_x3): a direct implicit GEMM whose input patch is split once while it is staged into LDS and then serves all nine
  * taps.  Replaces cuDNN's conv+BN+ReLU(+residual) of models/resnet.py:56-72 (BasicBlock.forward) for the layers it supports; with stride 2
