@@ -93,6 +93,11 @@ _SIGS = {
     "di2p_pnp_ransac": [c_void_p] * 5 + [c_int, c_void_p, c_int, c_double, c_int, c_int, c_int, c_int] + [c_void_p] * 7,
     "di2p_draw_restarts": [ctypes.c_ulonglong, c_int, c_int, c_double, c_double, c_void_p, c_void_p, c_void_p],
     "di2p_random_choice": [ctypes.c_ulonglong, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "di2p_random_choice_ragged": [ctypes.c_ulonglong, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "di2p_voxel_down_sample": [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int] + [c_void_p] * 9,
+    "di2p_estimate_normals": [c_void_p, c_int, c_int, c_double, c_int, c_double] + [c_void_p] * 5,
+    "di2p_nearest_raw": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_double] + [c_void_p] * 5,
+    "di2p_gather_ragged": [c_void_p] * 6 + [c_int, c_int] + [c_void_p] * 4,
     "di2p_pnp_pack": [c_void_p] * 4 + [c_int, c_int, c_int] + [c_void_p] * 3,
     "di2p_pnp_ransac_epnp": [c_void_p] * 5 + [c_int, c_void_p, c_int, c_double, c_int, c_int] + [c_void_p] * 7,
     "di2p_classifier_loss": [c_void_p] * 4 + [c_int, c_int, c_int, c_float, c_float, c_float] + [c_void_p] * 5,
@@ -137,6 +142,8 @@ _WS_SIGS = {        # <name>_workspace_bytes helpers returning long long
     "di2p_head_x3_packed_bytes": [c_int],
     "di2p_head_labels_x3_packed_bytes": [c_int, c_int],
     "di2p_stem_x3_packed_bytes": [],
+    "di2p_scan_prep_workspace_bytes": [c_int, c_int],
+    "di2p_random_choice_ragged_workspace_bytes": [c_int, c_int],
 }
 EXPORTS = sorted(list(_SIGS) + ["di2p_last_error", "di2p_version", "di2p_solve_workspace_bytes", "di2p_solver_set_profile_buffer", "di2p_pnp_workspace_bytes",
                  "di2p_conv2d_workspace_bytes", "di2p_set_option", "di2p_get_option", "di2p_random_choice_workspace_bytes", "di2p_classifier_loss_workspace_bytes"] + list(_WS_SIGS))

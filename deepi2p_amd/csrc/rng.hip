@@ -49,11 +49,18 @@ __global__ __launch_bounds__(256) void draw_restarts_kernel(unsigned long long s
 // Uniform random subset in uniform random order: element i of frame b gets the 64-bit key (philox(b, i) << 32 | i); the
 // n_out smallest keys, in key order, are the choice (a random permutation's prefix, like np.random.choice(replace=False)).
 // One 1024-thread workgroup per frame sorts the keys (bitonic; LDS chunks of 8192 keys, wide strides in global scratch).
+// offsets (ragged variant, may be NULL): frame b has n_src = offsets[b+1] - offsets[b] <= P; a frame shorter than n_out takes
+// every index floor(n_out / n_src) times, then the first n_out mod n_src keys (prep.downsample's rule); an empty frame gives -1.
 __global__ __launch_bounds__(1024) void random_choice_kernel(unsigned long long seed, int stream_id, int n_src, int P, int n_out,
-                                                             unsigned long long* __restrict__ keys_all, int* __restrict__ out) {
+                                                             unsigned long long* __restrict__ keys_all, int* __restrict__ out,
+                                                             const int* __restrict__ offsets) {
     constexpr int CH = 8192;
     __shared__ unsigned long long chunk[CH];
     const int b = blockIdx.x, tid = threadIdx.x;
+    if (offsets) {
+        const int n = offsets[b + 1] - offsets[b];
+        n_src = n < 0 ? 0 : (n > n_src ? n_src : n);      // n_src: the caller's max_src
+    }
     unsigned long long* keys = keys_all + (long long)b * P;
     for (int n = tid; n < P; n += 1024) {
         unsigned long long k = ~0ull;
@@ -104,7 +111,13 @@ __global__ __launch_bounds__(1024) void random_choice_kernel(unsigned long long 
             __syncthreads();
         }
     }
-    for (int i = tid; i < n_out; i += 1024) out[(long long)b * n_out + i] = (int)(unsigned)(keys[i] & 0xffffffffull);
+    if (n_src >= n_out) {
+        for (int i = tid; i < n_out; i += 1024) out[(long long)b * n_out + i] = (int)(unsigned)(keys[i] & 0xffffffffull);
+    } else {
+        const int fixed = n_src > 0 ? (n_out / n_src) * n_src : 0;
+        for (int i = tid; i < n_out; i += 1024)
+            out[(long long)b * n_out + i] = n_src == 0 ? -1 : i < fixed ? i % n_src : (int)(unsigned)(keys[i - fixed] & 0xffffffffull);
+    }
 }
 
 // stream tag 3: the keep-mask of nn.Dropout (per_point_pn, networks_united.py:57-74; layers_pc.py:300-303,339-340): element i is kept
@@ -146,7 +159,20 @@ extern "C" int di2p_random_choice(unsigned long long seed, int stream_id, int B,
     DI2P_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "workspace must be 8-byte aligned");
     if (B == 0 || n_out == 0) return 0;
     hipLaunchKernelGGL(random_choice_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, seed, stream_id, n_src, pow2_at_least(n_src),
-                       n_out, (unsigned long long*)workspace, idx_out);
+                       n_out, (unsigned long long*)workspace, idx_out, (const int*)nullptr);
+    DI2P_RETURN_LAUNCH();
+}
+
+extern "C" long long di2p_random_choice_ragged_workspace_bytes(int B, int max_src) { return di2p_random_choice_workspace_bytes(B, max_src); }
+
+extern "C" int di2p_random_choice_ragged(unsigned long long seed, int stream_id, int B, const int32_t* offsets, int max_src, int n_out,
+                                         int32_t* idx_out, void* workspace, void* stream) {
+    DI2P_CHECK_ARG(B >= 0 && max_src >= 1 && max_src <= (1 << 20) && n_out >= 0, "bad args (1 <= max_src <= 2^20, n_out >= 0)");
+    DI2P_CHECK_ARG(B == 0 || (offsets && idx_out && workspace), "null pointer");
+    DI2P_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "workspace must be 8-byte aligned");
+    if (B == 0 || n_out == 0) return 0;
+    hipLaunchKernelGGL(random_choice_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, seed, stream_id, max_src, pow2_at_least(max_src),
+                       n_out, (unsigned long long*)workspace, idx_out, (const int*)offsets);
     DI2P_RETURN_LAUNCH();
 }
 

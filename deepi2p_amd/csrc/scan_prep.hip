@@ -1,0 +1,656 @@
+// Raw LiDAR scan preparation on the device (gfx950): the CPU stage between a Velodyne .bin scan and the network input.
+//
+// Replaces  data/kitti/kitti_pc_bin_to_npy_with_downsample_sn.py:50-74   Open3D voxel_down_sample (0.1), estimate_normals
+//                                                                        (hybrid radius 0.6 / max_nn 30), orient_normals_to_align_with_direction
+//                                                                        ([0,0,1]), cKDTree 1-NN intensity lookup
+//           data/kitti_pc_img_pose_loader.py:26-44,296-306             the loader's second voxel pass (0.3 m, averaged intensity and normals)
+//           data/kitti_pc_img_pose_loader.py:158-171,380               ragged random down-sample + the rigid transform into the camera frame
+//                                                                        (the choice itself lives in rng.hip, di2p_random_choice_ragged)
+//
+// One workspace carries the state of a batch from di2p_voxel_down_sample to di2p_estimate_normals and di2p_nearest_raw: the per-frame
+// bounds, the raw points sorted by (frame, voxel key), and the fp64 centroids (Open3D works on its double points; so do the later stages).
+// All key and mean arithmetic is fp64 with FMA contraction off for this file (build.py), so it equals numpy value for value.
+// Sorting: rocPRIM's stable device radix sort, temporary storage from the workspace.  Stability makes the summation order (ascending
+// input index inside a voxel) and therefore the bits reproducible.
+#include "common.h"
+
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+namespace {
+
+constexpr int AXIS_BITS = 21;
+constexpr int AXIS_MAX = (1 << AXIS_BITS) - 1;
+constexpr int MAX_FRAME_POINTS = 1 << 20;
+constexpr unsigned long long PAD_KEY = (1ull << 63) - 1;
+constexpr int NN_MAX = 64;
+constexpr int NN_CAP = 1024;          // LDS candidate buffer of one query (entries); compacted to the best max_nn when full
+constexpr int ST_OK = 0, ST_TOO_MANY = 1, ST_SPAN = 2, ST_OFFSETS = 3;
+
+__device__ __forceinline__ unsigned long long compose_key(long long ix, long long iy, long long iz) {
+    return ((unsigned long long)ix << (2 * AXIS_BITS)) | ((unsigned long long)iy << AXIS_BITS) | (unsigned long long)iz;
+}
+
+__device__ __forceinline__ long long clamp_axis(double f) {
+    return f < 0.0 ? 0 : (f > (double)AXIS_MAX ? AXIS_MAX : (long long)f);
+}
+
+// largest b in [0, B) with off[b] <= i (off non-decreasing)
+__device__ __forceinline__ int frame_of(const int* __restrict__ off, int B, long long i) {
+    int lo = 0, hi = B - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if ((long long)off[mid] <= i) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ double d2_of(double ax, double ay, double az, double bx, double by, double bz) {
+    const double dx = ax - bx, dy = ay - by, dz = az - bz;
+    return __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
+}
+
+// ---------------------------------------------------------------- workspace layout
+struct Layout {
+    size_t minb, imax, fstat, pass, nvox;                  // per frame: f64[B*3], f32[B], i32[B], i32[B]; i32[1]
+    size_t pfr, key, iota, k1, i1, f1, f2, i2, k2;         // per raw point (cap)
+    size_t head, scan, vstart, vfr, cen;                   // per voxel (cap + 1)
+    size_t ck, ci2, ck2, cpos;                             // cell sort of the centroids
+    size_t tmp, tmp_bytes, total;
+};
+
+size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+size_t sort_tmp_bound(int cap) { return (size_t)24 * cap + ((size_t)1 << 20); }
+
+Layout layout(int B, int cap) {
+    Layout L;
+    size_t o = 0;
+    const size_t n = (size_t)cap, n1 = (size_t)cap + 1;
+    auto take = [&](size_t bytes) { const size_t r = o; o = align256(o + bytes); return r; };
+    L.minb = take(8 * 3 * (size_t)B); L.imax = take(4 * (size_t)B); L.fstat = take(4 * (size_t)B); L.pass = take(4 * (size_t)B); L.nvox = take(4);
+    L.pfr = take(4 * n); L.key = take(8 * n); L.iota = take(4 * n); L.k1 = take(8 * n); L.i1 = take(4 * n);
+    L.f1 = take(4 * n); L.f2 = take(4 * n); L.i2 = take(4 * n); L.k2 = take(8 * n);
+    L.head = take(4 * n1); L.scan = take(4 * n1); L.vstart = take(4 * n1); L.vfr = take(4 * n1); L.cen = take(8 * 3 * n);
+    L.ck = take(8 * n); L.ci2 = take(4 * n); L.ck2 = take(8 * n); L.cpos = take(8 * 3 * n);
+    L.tmp_bytes = sort_tmp_bound(cap);
+    L.tmp = take(L.tmp_bytes);
+    L.total = o;
+    return L;
+}
+
+template <class T> T* at(void* ws, size_t off) { return (T*)((char*)ws + off); }
+
+// ---------------------------------------------------------------- stage 1: voxel grid
+// One workgroup per frame: bounds, maximum intensity, status.  min_bound = min - voxel/2 (Open3D VoxelDownSample).
+__global__ __launch_bounds__(256) void frame_bounds_kernel(const float* __restrict__ pts, const int* __restrict__ off, int B, int cap,
+                                                           int max_frame_points, double voxel, double max_extent, int min_points,
+                                                           double* __restrict__ minb, float* __restrict__ imax, int* __restrict__ fstat,
+                                                           int* __restrict__ pass, int* __restrict__ status) {
+    __shared__ float s[7][256];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int s0 = off[b], s1 = off[b + 1];
+    const bool offsets_ok = s0 >= 0 && s1 >= s0 && s1 <= cap && off[0] == 0;
+    const int n = offsets_ok ? s1 - s0 : 0;
+    const bool scan_ok = offsets_ok && n <= max_frame_points;
+    float mn[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, mx[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
+    float im = -__builtin_inff();
+    if (scan_ok) {
+        for (int i = s0 + tid; i < s1; i += 256) {
+            const float4 p = *(const float4*)(pts + 4 * (long long)i);
+            mn[0] = fminf(mn[0], p.x); mn[1] = fminf(mn[1], p.y); mn[2] = fminf(mn[2], p.z);
+            mx[0] = fmaxf(mx[0], p.x); mx[1] = fmaxf(mx[1], p.y); mx[2] = fmaxf(mx[2], p.z);
+            im = fmaxf(im, p.w);
+        }
+    }
+    for (int c = 0; c < 3; ++c) { s[c][tid] = mn[c]; s[3 + c][tid] = mx[c]; }
+    s[6][tid] = im;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) {
+            for (int c = 0; c < 3; ++c) { s[c][tid] = fminf(s[c][tid], s[c][tid + o]); s[3 + c][tid] = fmaxf(s[3 + c][tid], s[3 + c][tid + o]); }
+            s[6][tid] = fmaxf(s[6][tid], s[6][tid + o]);
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        int st = !offsets_ok ? ST_OFFSETS : (n > max_frame_points ? ST_TOO_MANY : ST_OK);
+        for (int c = 0; c < 3; ++c) {
+            const double lo = n > 0 && st == ST_OK ? __dsub_rn((double)s[c][0], __dmul_rn(voxel, 0.5)) : 0.0;
+            minb[3 * b + c] = lo;
+            if (n > 0 && st == ST_OK) {
+                const double ext = (double)s[3 + c][0] - (double)s[c][0];
+                const double top = floor(((double)s[3 + c][0] - lo) / voxel);
+                if (!(ext <= max_extent) || !(top <= (double)AXIS_MAX)) st = ST_SPAN;
+            }
+        }
+        imax[b] = n > 0 ? s[6][0] : 0.0f;
+        fstat[b] = st;
+        pass[b] = n <= min_points;
+        if (status) status[b] = st;
+    }
+}
+
+// Voxel key of every raw point (original order) and its frame; positions past the batch sort last (frame B).
+__global__ __launch_bounds__(256) void point_keys_kernel(const float* __restrict__ pts, const int* __restrict__ off, int B, int cap, double voxel,
+                                                         const double* __restrict__ minb, const int* __restrict__ fstat,
+                                                         unsigned* __restrict__ pfr, unsigned long long* __restrict__ key, int* __restrict__ iota) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= cap) return;
+    iota[i] = (int)i;
+    const int total = min(max(off[B], 0), cap);
+    if (i >= total) { pfr[i] = (unsigned)B; key[i] = PAD_KEY; return; }
+    const int b = frame_of(off, B, i);
+    pfr[i] = (unsigned)b;
+    if (fstat[b] != ST_OK) { key[i] = 0; return; }
+    const float4 p = *(const float4*)(pts + 4 * i);
+    const long long ix = clamp_axis(floor(((double)p.x - minb[3 * b + 0]) / voxel));
+    const long long iy = clamp_axis(floor(((double)p.y - minb[3 * b + 1]) / voxel));
+    const long long iz = clamp_axis(floor(((double)p.z - minb[3 * b + 2]) / voxel));
+    key[i] = compose_key(ix, iy, iz);
+}
+
+__global__ __launch_bounds__(256) void gather_frames_kernel(const unsigned* __restrict__ elem_frame, const int* __restrict__ idx,
+                                                            unsigned* __restrict__ out, int n) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j < n) out[j] = elem_frame[idx[j]];
+}
+
+__global__ __launch_bounds__(256) void gather_keys_kernel(const unsigned long long* __restrict__ key, const int* __restrict__ idx,
+                                                          unsigned long long* __restrict__ out, int n) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j < n) out[j] = key[idx[j]];
+}
+
+// head[j] = 1 where sorted position j starts an output point (a new voxel; every point of a pass-through frame)
+__global__ __launch_bounds__(256) void heads_kernel(const int* __restrict__ off, int B, int cap, const unsigned* __restrict__ sfr,
+                                                    const unsigned long long* __restrict__ skey, const int* __restrict__ fstat,
+                                                    const int* __restrict__ pass, int* __restrict__ head) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j > cap) return;
+    const int total = min(max(off[B], 0), cap);
+    int h = 0;
+    if (j < total) {
+        const unsigned b = sfr[j];
+        if (b < (unsigned)B && fstat[b] == ST_OK)
+            h = pass[b] ? 1 : (j == 0 || j == off[b] || skey[j] != skey[j - 1]);
+    }
+    head[j] = h;
+}
+
+__global__ __launch_bounds__(256) void voxel_index_kernel(const int* __restrict__ off, int B, int cap, const unsigned* __restrict__ sfr,
+                                                          const int* __restrict__ head, const int* __restrict__ scan, int* __restrict__ vstart,
+                                                          unsigned* __restrict__ vfr, int* __restrict__ out_off, int* __restrict__ nvox) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    const int total = min(max(off[B], 0), cap);
+    if (j < total && head[j]) { vstart[scan[j]] = j; vfr[scan[j]] = sfr[j]; }
+    if (j == total) { vstart[scan[j]] = total; *nvox = scan[j]; }
+    if (j <= B) out_off[j] = scan[min(max(off[j], 0), total)];
+}
+
+// One thread per output point: the fp64 mean of the voxel's members in ascending input index (Open3D AccumulatedPoint: sum, then
+// / double(n)); intensity as the loader's fake colour i / max averaged, then * max; normals averaged and not renormalised.
+__global__ __launch_bounds__(256) void voxel_mean_kernel(const float* __restrict__ pts, const float* __restrict__ nrm_in, const int* __restrict__ off,
+                                                         const int* __restrict__ out_off, const int* __restrict__ nvox_p, int cap,
+                                                         const int* __restrict__ vstart, const unsigned* __restrict__ vfr,
+                                                         const int* __restrict__ sidx, const unsigned long long* __restrict__ skey,
+                                                         const unsigned long long* __restrict__ key, const float* __restrict__ imax,
+                                                         const int* __restrict__ pass, double* __restrict__ cen, float* __restrict__ out_pts,
+                                                         float* __restrict__ out_int, float* __restrict__ out_nrm, long long* __restrict__ out_key) {
+    const int nvox = *nvox_p;
+    for (int v = blockIdx.x * 256 + threadIdx.x; v < nvox && v < cap; v += gridDim.x * 256) {
+        const int b = (int)vfr[v];
+        double sx = 0.0, sy = 0.0, sz = 0.0, sc = 0.0, nx = 0.0, ny = 0.0, nz = 0.0;
+        int cnt;
+        unsigned long long k;
+        const double mxi = (double)imax[b];
+        if (pass[b]) {
+            const long long gi = (long long)off[b] + (v - out_off[b]);
+            const float4 p = *(const float4*)(pts + 4 * gi);
+            cen[3 * (long long)v + 0] = (double)p.x; cen[3 * (long long)v + 1] = (double)p.y; cen[3 * (long long)v + 2] = (double)p.z;
+            out_pts[3 * (long long)v + 0] = p.x; out_pts[3 * (long long)v + 1] = p.y; out_pts[3 * (long long)v + 2] = p.z;
+            if (out_int) out_int[v] = p.w;
+            if (out_nrm)
+                for (int c = 0; c < 3; ++c) out_nrm[3 * (long long)v + c] = nrm_in[3 * gi + c];
+            if (out_key) out_key[v] = (long long)key[gi];
+            continue;
+        }
+        const int s = vstart[v], e = vstart[v + 1];
+        cnt = e - s;
+        k = skey[s];
+        for (int j = s; j < e; ++j) {
+            const long long gi = sidx[j];
+            const float4 p = *(const float4*)(pts + 4 * gi);
+            sx = __dadd_rn(sx, (double)p.x); sy = __dadd_rn(sy, (double)p.y); sz = __dadd_rn(sz, (double)p.z);
+            if (out_int) sc = __dadd_rn(sc, (double)p.w / mxi);
+            if (out_nrm) {
+                nx = __dadd_rn(nx, (double)nrm_in[3 * gi + 0]); ny = __dadd_rn(ny, (double)nrm_in[3 * gi + 1]);
+                nz = __dadd_rn(nz, (double)nrm_in[3 * gi + 2]);
+            }
+        }
+        const double dn = (double)cnt;
+        const double mx = sx / dn, my = sy / dn, mz = sz / dn;
+        cen[3 * (long long)v + 0] = mx; cen[3 * (long long)v + 1] = my; cen[3 * (long long)v + 2] = mz;
+        out_pts[3 * (long long)v + 0] = (float)mx; out_pts[3 * (long long)v + 1] = (float)my; out_pts[3 * (long long)v + 2] = (float)mz;
+        if (out_int) out_int[v] = (float)__dmul_rn(sc / dn, mxi);
+        if (out_nrm) {
+            out_nrm[3 * (long long)v + 0] = (float)(nx / dn); out_nrm[3 * (long long)v + 1] = (float)(ny / dn);
+            out_nrm[3 * (long long)v + 2] = (float)(nz / dn);
+        }
+        if (out_key) out_key[v] = (long long)k;
+    }
+}
+
+// ---------------------------------------------------------------- stage 2: normals
+// Grid key of every centroid: cell = radius * (1 + 2^-20) (slightly larger than r: a rounding at a cell border can never hide a
+// neighbour from the 27-cell scan).  Frame from the voxel offsets; positions past the batch sort last.
+__global__ __launch_bounds__(256) void cell_keys_kernel(const double* __restrict__ cen, const int* __restrict__ out_off, int B, int cap,
+                                                        const int* __restrict__ nvox_p, const double* __restrict__ minb, double cell,
+                                                        unsigned* __restrict__ cfr, unsigned long long* __restrict__ ck, int* __restrict__ iota) {
+    const int v = blockIdx.x * 256 + threadIdx.x;
+    if (v >= cap) return;
+    iota[v] = v;
+    if (v >= *nvox_p) { cfr[v] = (unsigned)B; ck[v] = PAD_KEY; return; }
+    const int b = frame_of(out_off, B, v);
+    cfr[v] = (unsigned)b;
+    ck[v] = compose_key(clamp_axis(floor((cen[3 * (long long)v + 0] - minb[3 * b + 0]) / cell)),
+                        clamp_axis(floor((cen[3 * (long long)v + 1] - minb[3 * b + 1]) / cell)),
+                        clamp_axis(floor((cen[3 * (long long)v + 2] - minb[3 * b + 2]) / cell)));
+}
+
+__global__ __launch_bounds__(256) void cell_positions_kernel(const double* __restrict__ cen, const int* __restrict__ ci2, const int* __restrict__ nvox_p,
+                                                             double* __restrict__ cpos) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= *nvox_p) return;
+    const long long v = ci2[j];
+    for (int c = 0; c < 3; ++c) cpos[3 * (long long)j + c] = cen[3 * v + c];
+}
+
+__device__ __forceinline__ double wave_sum(double x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x = __dadd_rn(x, __shfl_xor(x, o, 64));
+    return x;
+}
+
+// (d2 bits, index) lexicographic order; d2 >= 0 so the bit pattern orders like the value
+__device__ __forceinline__ bool nn_less(unsigned long long da, int ia, unsigned long long db, int ib) {
+    return da < db || (da == db && ia < ib);
+}
+
+// bitonic sort of n2 (power of two >= cnt) entries of the LDS list, padding [cnt, n2) with +inf first; one wave
+__device__ void nn_sort(unsigned long long* sd, int* si, int cnt, int lane) {
+    int n2 = 64;
+    while (n2 < cnt) n2 <<= 1;
+    for (int i = cnt + lane; i < n2; i += 64) { sd[i] = ~0ull; si[i] = 0x7fffffff; }
+    __syncthreads();
+    for (int k = 2; k <= n2; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = lane; t < n2 / 2; t += 64) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+                const int l = i + j;
+                const bool up = (i & k) == 0;
+                const unsigned long long a = sd[i], c = sd[l];
+                const int ia = si[i], ic = si[l];
+                if (nn_less(c, ic, a, ia) == up) { sd[i] = c; sd[l] = a; si[i] = ic; si[l] = ia; }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// eigenvector of the smallest eigenvalue of a symmetric 3x3 matrix (cyclic Jacobi, fp64, registers only)
+__device__ void smallest_eigvec(double a00, double a01, double a02, double a11, double a12, double a22, double& nx, double& ny, double& nz) {
+    double A[3][3] = {{a00, a01, a02}, {a01, a11, a12}, {a02, a12, a22}};
+    double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+    for (int sweep = 0; sweep < 24; ++sweep) {
+        if (A[0][1] == 0.0 && A[0][2] == 0.0 && A[1][2] == 0.0) break;
+#pragma unroll
+        for (int pq = 0; pq < 3; ++pq) {
+            const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2;
+            if (A[p][q] != 0.0) {
+                const double theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
+                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+#pragma unroll
+                for (int r = 0; r < 3; ++r) {          // A <- A J
+                    const double arp = A[r][p], arq = A[r][q];
+                    A[r][p] = c * arp - s * arq;
+                    A[r][q] = s * arp + c * arq;
+                }
+#pragma unroll
+                for (int r = 0; r < 3; ++r) {          // A <- J^T A
+                    const double apr = A[p][r], aqr = A[q][r];
+                    A[p][r] = c * apr - s * aqr;
+                    A[q][r] = s * apr + c * aqr;
+                }
+                A[p][q] = 0.0; A[q][p] = 0.0;
+#pragma unroll
+                for (int r = 0; r < 3; ++r) {          // V <- V J
+                    const double vrp = V[r][p], vrq = V[r][q];
+                    V[r][p] = c * vrp - s * vrq;
+                    V[r][q] = s * vrp + c * vrq;
+                }
+            }
+        }
+    }
+    int m = 0;
+    if (A[1][1] < A[m][m]) m = 1;
+    if (A[2][2] < (m == 0 ? A[0][0] : A[1][1])) m = 2;
+    nx = m == 0 ? V[0][0] : m == 1 ? V[0][1] : V[0][2];
+    ny = m == 0 ? V[1][0] : m == 1 ? V[1][1] : V[1][2];
+    nz = m == 0 ? V[2][0] : m == 1 ? V[2][1] : V[2][2];
+}
+
+// One wave (workgroup of 64) per query centroid, persistent over the batch.  The 27 neighbour cells (9 key ranges of 3 z-adjacent cells)
+// are located by binary search in the frame's cell-sorted keys (18 lanes in parallel), their members streamed 64 at a time; candidates with d2 < r2 that beat the
+// current max_nn-th best (d2, index) are appended to an LDS list, which is sorted and cut back to max_nn whenever it fills.  The list
+// never spills and the selection is exact: the result is the max_nn smallest (d2, index) pairs inside the ball.
+__global__ __launch_bounds__(64) void normals_kernel(const double* __restrict__ cen, const double* __restrict__ cpos, const int* __restrict__ ci2,
+                                                     const unsigned long long* __restrict__ ck2, const int* __restrict__ out_off, int B,
+                                                     const int* __restrict__ nvox_p, const double* __restrict__ minb, double cell, double r2,
+                                                     int max_nn, float* __restrict__ normals, int* __restrict__ nn_count, int* __restrict__ nn_idx) {
+    __shared__ unsigned long long sd[NN_CAP];
+    __shared__ int si[NN_CAP];
+    const int lane = threadIdx.x;
+    const int nvox = *nvox_p;
+    for (int jq = blockIdx.x; jq < nvox; jq += gridDim.x) {
+        const int v = ci2[jq];              // queries in cell order: neighbouring workgroups read the same cells
+        const int b = frame_of(out_off, B, v);
+        const int fs = out_off[b], fe = out_off[b + 1];
+        const double qx = cen[3 * (long long)v + 0], qy = cen[3 * (long long)v + 1], qz = cen[3 * (long long)v + 2];
+        // the three z-neighbour cells of an (x, y) column are one key range: 9 ranges, lanes 0-8 find their starts, 9-17 their ends
+        int pos = fs;
+        if (lane < 18) {
+            const int r = lane % 9;
+            const long long cx = (long long)floor((qx - minb[3 * b + 0]) / cell) + r % 3 - 1;
+            const long long cy = (long long)floor((qy - minb[3 * b + 1]) / cell) + r / 3 - 1;
+            const long long cz = (long long)floor((qz - minb[3 * b + 2]) / cell);
+            if (cx >= 0 && cy >= 0 && cx <= AXIS_MAX && cy <= AXIS_MAX) {
+                const bool upper = lane >= 9;
+                const unsigned long long k = upper ? compose_key(cx, cy, cz + 1 < AXIS_MAX ? cz + 1 : AXIS_MAX) : compose_key(cx, cy, cz > 0 ? cz - 1 : 0);
+                int lo = fs, hi = fe;
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (upper ? ck2[mid] <= k : ck2[mid] < k) lo = mid + 1; else hi = mid;
+                }
+                pos = lo;
+            }
+        }
+        int cnt = 0;
+        unsigned long long thr_d = ~0ull;
+        int thr_i = 0x7fffffff;
+        for (int c = 0; c < 9; ++c) {
+            const int s = __shfl(pos, c, 64), e = __shfl(pos, c + 9, 64);
+            for (int base = s; base < e; base += 64) {
+                const int j = base + lane;
+                bool acc = false;
+                unsigned long long db = 0;
+                int li = 0;
+                if (j < e) {
+                    const double d2 = d2_of(cpos[3 * (long long)j + 0], cpos[3 * (long long)j + 1], cpos[3 * (long long)j + 2], qx, qy, qz);
+                    db = (unsigned long long)__double_as_longlong(d2);
+                    li = ci2[j] - fs;
+                    acc = d2 < r2 && nn_less(db, li, thr_d, thr_i);
+                }
+                const unsigned long long m = __ballot(acc);
+                if (acc) {
+                    const int pos = cnt + __popcll(m & ((1ull << lane) - 1));
+                    sd[pos] = db; si[pos] = li;
+                }
+                cnt += __popcll(m);
+                __syncthreads();
+                if (cnt > NN_CAP - 64) {
+                    nn_sort(sd, si, cnt, lane);
+                    if (cnt >= max_nn) { thr_d = sd[max_nn - 1]; thr_i = si[max_nn - 1]; cnt = max_nn; }
+                    __syncthreads();
+                }
+            }
+        }
+        nn_sort(sd, si, cnt, lane);
+        const int k = cnt < max_nn ? cnt : max_nn;
+        if (nn_idx)
+            for (int t = lane; t < max_nn; t += 64) nn_idx[(long long)v * max_nn + t] = t < k ? si[t] : -1;
+        if (nn_count && lane == 0) nn_count[v] = k;
+        double px = 0.0, py = 0.0, pz = 0.0;
+        if (lane < k) {
+            const long long g = (long long)fs + si[lane];
+            px = cen[3 * g + 0]; py = cen[3 * g + 1]; pz = cen[3 * g + 2];
+        }
+        const double dk = (double)k;
+        const double mx = wave_sum(px) / dk, my = wave_sum(py) / dk, mz = wave_sum(pz) / dk;
+        const double ex = lane < k ? px - mx : 0.0, ey = lane < k ? py - my : 0.0, ez = lane < k ? pz - mz : 0.0;
+        const double cxx = wave_sum(ex * ex), cxy = wave_sum(ex * ey), cxz = wave_sum(ex * ez);
+        const double cyy = wave_sum(ey * ey), cyz = wave_sum(ey * ez), czz = wave_sum(ez * ez);
+        double nx = 0.0, ny = 0.0, nz = 0.0;
+        if (k >= 3 && (cxx != 0.0 || cxy != 0.0 || cxz != 0.0 || cyy != 0.0 || cyz != 0.0 || czz != 0.0))
+            smallest_eigvec(cxx, cxy, cxz, cyy, cyz, czz, nx, ny, nz);
+        // orient_normals_to_align_with_direction([0,0,1]): a zero normal becomes the direction, n . dir < 0 flips
+        if (nx == 0.0 && ny == 0.0 && nz == 0.0) { nz = 1.0; }
+        else if (nz < 0.0) { nx = -nx; ny = -ny; nz = -nz; }
+        if (lane == 0) {
+            normals[3 * (long long)v + 0] = (float)nx; normals[3 * (long long)v + 1] = (float)ny; normals[3 * (long long)v + 2] = (float)nz;
+        }
+        __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------- stage 3: 1-NN in the raw scan
+__device__ __forceinline__ void scan_voxel(const float* __restrict__ pts, const int* __restrict__ sidx, const unsigned long long* __restrict__ skey,
+                                           int fs, int fe, unsigned long long k, double qx, double qy, double qz, double& best, int& bi) {
+    int lo = fs, hi = fe;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (skey[mid] < k) lo = mid + 1; else hi = mid; }
+    for (int j = lo; j < fe && skey[j] == k; ++j) {
+        const int gi = sidx[j];
+        const float4 p = *(const float4*)(pts + 4 * (long long)gi);
+        const double d2 = d2_of((double)p.x, (double)p.y, (double)p.z, qx, qy, qz);
+        if (d2 < best || (d2 == best && gi < bi)) { best = d2; bi = gi; }
+    }
+}
+
+// One thread per centroid: own voxel first, then every voxel the ball of the best distance so far touches (bounds widened by 1e-9
+// relative + 1e-9 absolute against rounding), ties -> the lower raw index.  Exact.
+__global__ __launch_bounds__(256) void nearest_raw_kernel(const float* __restrict__ pts, const int* __restrict__ off, const int* __restrict__ out_off,
+                                                          int B, const int* __restrict__ nvox_p, const double* __restrict__ cen,
+                                                          const double* __restrict__ minb, double voxel, const int* __restrict__ sidx,
+                                                          const unsigned long long* __restrict__ skey, int* __restrict__ nn_idx,
+                                                          float* __restrict__ nn_int, double* __restrict__ nn_d2) {
+    const int nvox = *nvox_p;
+    for (int v = blockIdx.x * 256 + threadIdx.x; v < nvox; v += gridDim.x * 256) {
+        const int b = frame_of(out_off, B, v);
+        const int fs = off[b], fe = off[b + 1];
+        const double q[3] = {cen[3 * (long long)v + 0], cen[3 * (long long)v + 1], cen[3 * (long long)v + 2]};
+        long long own[3];
+        for (int c = 0; c < 3; ++c) own[c] = clamp_axis(floor((q[c] - minb[3 * b + c]) / voxel));
+        double best = __builtin_inf();
+        int bi = 0x7fffffff;
+        const unsigned long long kown = compose_key(own[0], own[1], own[2]);
+        scan_voxel(pts, sidx, skey, fs, fe, kown, q[0], q[1], q[2], best, bi);
+        long long lo[3], hi[3];
+        const double rad = best < __builtin_inf() ? sqrt(best) * (1.0 + 1e-9) + 1e-9 : 0.0;
+        for (int c = 0; c < 3; ++c) {
+            if (best < __builtin_inf()) {
+                lo[c] = clamp_axis(floor((q[c] - rad - minb[3 * b + c]) / voxel));
+                hi[c] = clamp_axis(floor((q[c] + rad - minb[3 * b + c]) / voxel));
+            } else {             // (not reached for a centroid of this frame: its own voxel holds its members)
+                lo[c] = own[c] > 2 ? own[c] - 2 : 0;
+                hi[c] = own[c] + 2 < AXIS_MAX ? own[c] + 2 : AXIS_MAX;
+            }
+        }
+        for (long long x = lo[0]; x <= hi[0]; ++x)
+            for (long long y = lo[1]; y <= hi[1]; ++y)
+                for (long long z = lo[2]; z <= hi[2]; ++z) {
+                    const unsigned long long k = compose_key(x, y, z);
+                    if (k != kown) scan_voxel(pts, sidx, skey, fs, fe, k, q[0], q[1], q[2], best, bi);
+                }
+        const bool found = bi != 0x7fffffff;
+        if (nn_idx) nn_idx[v] = found ? bi - fs : -1;
+        if (nn_int) nn_int[v] = found ? pts[4 * (long long)bi + 3] : 0.0f;
+        if (nn_d2) nn_d2[v] = best;
+    }
+}
+
+// ---------------------------------------------------------------- stage 4: ragged gather (+ rigid transform)
+__global__ __launch_bounds__(256) void gather_ragged_kernel(const float* __restrict__ pts, const float* __restrict__ inten, const float* __restrict__ nrm,
+                                                            const int* __restrict__ off, const int* __restrict__ idx, const double* __restrict__ T,
+                                                            int n_out, float* __restrict__ pc, float* __restrict__ out_int, float* __restrict__ sn) {
+    const int b = blockIdx.y, n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= n_out) return;
+    const int i = idx[(long long)b * n_out + n];
+    const bool ok = i >= 0 && i < off[b + 1] - off[b];
+    const long long g = (long long)off[b] + (ok ? i : 0);
+    double p[3] = {0.0, 0.0, 0.0}, s[3] = {0.0, 0.0, 0.0};
+    float it = 0.0f;
+    if (ok) {
+        for (int c = 0; c < 3; ++c) p[c] = (double)pts[3 * g + c];
+        if (nrm) for (int c = 0; c < 3; ++c) s[c] = (double)nrm[3 * g + c];
+        if (inten) it = inten[g];
+    }
+    const long long o3 = (long long)b * 3 * n_out + n;
+    if (T && ok) {
+        const double* M = T + 16 * (long long)b;
+        for (int r = 0; r < 3; ++r) {
+            pc[o3 + (long long)r * n_out] = (float)(((M[4 * r] * p[0] + M[4 * r + 1] * p[1]) + M[4 * r + 2] * p[2]) + M[4 * r + 3]);
+            if (sn) sn[o3 + (long long)r * n_out] = (float)((M[4 * r] * s[0] + M[4 * r + 1] * s[1]) + M[4 * r + 2] * s[2]);
+        }
+    } else {
+        for (int r = 0; r < 3; ++r) {
+            pc[o3 + (long long)r * n_out] = (float)p[r];
+            if (sn) sn[o3 + (long long)r * n_out] = (float)s[r];
+        }
+    }
+    if (out_int) out_int[(long long)b * n_out + n] = it;
+}
+
+int frame_bits(int B) { int bits = 1; while ((1ll << bits) <= B) ++bits; return bits; }
+
+// Stable sort of `cap` elements by (frame, 63-bit key): a stable radix sort on the key, then a stable one on the frame of each element
+// (LSD order).  idx_out = original positions, key_out = their keys, fr_out = their frames.
+hipError_t sort_by_frame_key(void* ws, const Layout& L, int B, int cap, const unsigned long long* key_in, const unsigned* elem_frame,
+                             int* idx_out, unsigned long long* key_out, unsigned* fr_out, hipStream_t st) {
+    void* tmp = at<void>(ws, L.tmp);
+    size_t need1 = 0, need2 = 0;
+    hipError_t e;
+    e = rocprim::radix_sort_pairs(nullptr, need1, key_in, at<unsigned long long>(ws, L.k1), at<int>(ws, L.iota), at<int>(ws, L.i1), cap, 0, 63, st);
+    if (e != hipSuccess) return e;
+    e = rocprim::radix_sort_pairs(nullptr, need2, at<unsigned>(ws, L.f1), fr_out, at<int>(ws, L.i1), idx_out, cap, 0, frame_bits(B), st);
+    if (e != hipSuccess) return e;
+    if (need1 > L.tmp_bytes || need2 > L.tmp_bytes) return hipErrorInvalidValue;
+    size_t sz = L.tmp_bytes;
+    e = rocprim::radix_sort_pairs(tmp, sz, key_in, at<unsigned long long>(ws, L.k1), at<int>(ws, L.iota), at<int>(ws, L.i1), cap, 0, 63, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(gather_frames_kernel, dim3(di2p_cdiv(cap, 256)), dim3(256), 0, st, elem_frame, at<int>(ws, L.i1), at<unsigned>(ws, L.f1), cap);
+    sz = L.tmp_bytes;
+    e = rocprim::radix_sort_pairs(tmp, sz, at<unsigned>(ws, L.f1), fr_out, at<int>(ws, L.i1), idx_out, cap, 0, frame_bits(B), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(gather_keys_kernel, dim3(di2p_cdiv(cap, 256)), dim3(256), 0, st, key_in, idx_out, key_out, cap);
+    return hipGetLastError();
+}
+
+int persistent_grid(int per_cu) { return di2p_cu_count() * per_cu; }
+
+}  // namespace
+
+extern "C" long long di2p_scan_prep_workspace_bytes(int B, int cap) {
+    if (B < 0 || cap < 0) return 0;
+    return (long long)layout(B, cap).total;
+}
+
+extern "C" int di2p_voxel_down_sample(const float* points, const int32_t* offsets, int B, int cap, int max_frame_points, double voxel,
+                                      double max_extent, int min_points, const float* normals_in, int32_t* out_offsets, float* out_points,
+                                      float* out_intensity, float* out_normals, int64_t* out_keys, int32_t* status, void* workspace,
+                                      void* stream) {
+    DI2P_CHECK_ARG(B >= 0 && cap >= 0, "bad sizes (B >= 0, cap >= 0)");
+    DI2P_CHECK_ARG(voxel > 0.0 && voxel < 1e30, "voxel size must be positive and finite");
+    DI2P_CHECK_ARG(max_frame_points >= 0 && max_frame_points <= MAX_FRAME_POINTS, "max_frame_points above 2^20 points per frame");
+    DI2P_CHECK_ARG(max_extent >= 0.0 && max_extent / voxel < (double)AXIS_MAX - 2.0, "voxel index span above 2^21 per axis (max_extent / voxel)");
+    DI2P_CHECK_ARG(!out_normals || normals_in, "out_normals needs normals_in");
+    DI2P_CHECK_ARG(B == 0 || (points && offsets && out_offsets && out_points && workspace), "null pointer");
+    DI2P_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
+    if (B == 0) return 0;
+    const Layout L = layout(B, cap);
+    hipStream_t st = (hipStream_t)stream;
+    void* ws = workspace;
+    hipLaunchKernelGGL(frame_bounds_kernel, dim3(B), dim3(256), 0, st, points, offsets, B, cap, max_frame_points, voxel, max_extent, min_points,
+                       at<double>(ws, L.minb), at<float>(ws, L.imax), at<int>(ws, L.fstat), at<int>(ws, L.pass), status);
+    if (cap > 0) {
+        hipLaunchKernelGGL(point_keys_kernel, dim3(di2p_cdiv(cap, 256)), dim3(256), 0, st, points, offsets, B, cap, voxel, at<double>(ws, L.minb),
+                           at<int>(ws, L.fstat), at<unsigned>(ws, L.pfr), at<unsigned long long>(ws, L.key), at<int>(ws, L.iota));
+        const hipError_t e = sort_by_frame_key(ws, L, B, cap, at<unsigned long long>(ws, L.key), at<unsigned>(ws, L.pfr), at<int>(ws, L.i2),
+                                               at<unsigned long long>(ws, L.k2), at<unsigned>(ws, L.f2), st);
+        if (e != hipSuccess) { di2p_set_error("di2p_voxel_down_sample: sort failed: %s", hipGetErrorString(e)); return (int)e; }
+    }
+    hipLaunchKernelGGL(heads_kernel, dim3(di2p_cdiv(cap + 1, 256)), dim3(256), 0, st, offsets, B, cap, at<unsigned>(ws, L.f2),
+                       at<unsigned long long>(ws, L.k2), at<int>(ws, L.fstat), at<int>(ws, L.pass), at<int>(ws, L.head));
+    size_t need = 0;
+    hipError_t e = rocprim::exclusive_scan(nullptr, need, at<int>(ws, L.head), at<int>(ws, L.scan), 0, (size_t)cap + 1, rocprim::plus<int>(), st);
+    if (e == hipSuccess && need > L.tmp_bytes) e = hipErrorInvalidValue;
+    if (e == hipSuccess) {
+        need = L.tmp_bytes;
+        e = rocprim::exclusive_scan(at<void>(ws, L.tmp), need, at<int>(ws, L.head), at<int>(ws, L.scan), 0, (size_t)cap + 1, rocprim::plus<int>(), st);
+    }
+    if (e != hipSuccess) { di2p_set_error("di2p_voxel_down_sample: scan failed: %s", hipGetErrorString(e)); return (int)e; }
+    hipLaunchKernelGGL(voxel_index_kernel, dim3(di2p_cdiv(cap + 1 > B + 1 ? cap + 1 : B + 1, 256)), dim3(256), 0, st, offsets, B, cap,
+                       at<unsigned>(ws, L.f2), at<int>(ws, L.head), at<int>(ws, L.scan), at<int>(ws, L.vstart), at<unsigned>(ws, L.vfr),
+                       out_offsets, at<int>(ws, L.nvox));
+    if (cap > 0)
+        hipLaunchKernelGGL(voxel_mean_kernel, dim3(min(di2p_cdiv(cap, 256), persistent_grid(8))), dim3(256), 0, st, points, normals_in, offsets,
+                           out_offsets, at<int>(ws, L.nvox), cap, at<int>(ws, L.vstart), at<unsigned>(ws, L.vfr), at<int>(ws, L.i2),
+                           at<unsigned long long>(ws, L.k2), at<unsigned long long>(ws, L.key), at<float>(ws, L.imax), at<int>(ws, L.pass),
+                           at<double>(ws, L.cen), out_points, out_intensity, out_normals, (long long*)out_keys);
+    DI2P_RETURN_LAUNCH();
+}
+
+extern "C" int di2p_estimate_normals(const int32_t* voxel_offsets, int B, int cap, double radius, int max_nn, double max_extent, float* normals,
+                                     int32_t* nn_count, int32_t* nn_idx, void* workspace, void* stream) {
+    DI2P_CHECK_ARG(B >= 0 && cap >= 0, "bad sizes (B >= 0, cap >= 0)");
+    DI2P_CHECK_ARG(radius > 0.0 && radius < 1e30, "radius must be positive and finite");
+    DI2P_CHECK_ARG(max_nn >= 1 && max_nn <= NN_MAX, "max_nn must be in [1, 64]");
+    DI2P_CHECK_ARG(max_extent >= 0.0 && max_extent / radius < (double)AXIS_MAX - 4.0, "grid cell index span above 2^21 per axis (max_extent / radius)");
+    DI2P_CHECK_ARG(B == 0 || (voxel_offsets && normals && workspace), "null pointer");
+    DI2P_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
+    if (B == 0 || cap == 0) return 0;
+    const Layout L = layout(B, cap);
+    hipStream_t st = (hipStream_t)stream;
+    void* ws = workspace;
+    const double cell = radius * (1.0 + 1.0 / 1048576.0);
+    // cell keys into L.ck, frames into L.pfr (the raw frames are no longer needed: the raw sort result lives in i2 / k2 / f2)
+    hipLaunchKernelGGL(cell_keys_kernel, dim3(di2p_cdiv(cap, 256)), dim3(256), 0, st, at<double>(ws, L.cen), voxel_offsets, B, cap, at<int>(ws, L.nvox),
+                       at<double>(ws, L.minb), cell, at<unsigned>(ws, L.pfr), at<unsigned long long>(ws, L.ck), at<int>(ws, L.iota));
+    // the frame-sorted output goes to f1's twin: reuse L.head (i32, cap + 1) for the sorted frames; it is not read after stage 1
+    const hipError_t e = sort_by_frame_key(ws, L, B, cap, at<unsigned long long>(ws, L.ck), at<unsigned>(ws, L.pfr), at<int>(ws, L.ci2),
+                                           at<unsigned long long>(ws, L.ck2), at<unsigned>(ws, L.head), st);
+    if (e != hipSuccess) { di2p_set_error("di2p_estimate_normals: sort failed: %s", hipGetErrorString(e)); return (int)e; }
+    hipLaunchKernelGGL(cell_positions_kernel, dim3(di2p_cdiv(cap, 256)), dim3(256), 0, st, at<double>(ws, L.cen), at<int>(ws, L.ci2),
+                       at<int>(ws, L.nvox), at<double>(ws, L.cpos));
+    hipLaunchKernelGGL(normals_kernel, dim3(min(cap, persistent_grid(32))), dim3(64), 0, st, at<double>(ws, L.cen), at<double>(ws, L.cpos),
+                       at<int>(ws, L.ci2), at<unsigned long long>(ws, L.ck2), voxel_offsets, B, at<int>(ws, L.nvox), at<double>(ws, L.minb), cell,
+                       radius * radius, max_nn, normals, nn_count, nn_idx);
+    DI2P_RETURN_LAUNCH();
+}
+
+extern "C" int di2p_nearest_raw(const float* points, const int32_t* offsets, const int32_t* voxel_offsets, int B, int cap, double voxel,
+                                int32_t* nn_idx, float* nn_intensity, double* nn_dist2, void* workspace, void* stream) {
+    DI2P_CHECK_ARG(B >= 0 && cap >= 0, "bad sizes (B >= 0, cap >= 0)");
+    DI2P_CHECK_ARG(voxel > 0.0 && voxel < 1e30, "voxel size must be positive and finite");
+    DI2P_CHECK_ARG(B == 0 || (points && offsets && voxel_offsets && workspace), "null pointer");
+    DI2P_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
+    if (B == 0 || cap == 0) return 0;
+    const Layout L = layout(B, cap);
+    void* ws = workspace;
+    hipLaunchKernelGGL(nearest_raw_kernel, dim3(min(di2p_cdiv(cap, 256), persistent_grid(8))), dim3(256), 0, (hipStream_t)stream, points, offsets,
+                       voxel_offsets, B, at<int>(ws, L.nvox), at<double>(ws, L.cen), at<double>(ws, L.minb), voxel, at<int>(ws, L.i2),
+                       at<unsigned long long>(ws, L.k2), nn_idx, nn_intensity, nn_dist2);
+    DI2P_RETURN_LAUNCH();
+}
+
+extern "C" int di2p_gather_ragged(const float* points, const float* intensity, const float* normals, const int32_t* offsets, const int32_t* idx,
+                                  const double* transform, int B, int n_out, float* pc, float* intensity_out, float* sn, void* stream) {
+    DI2P_CHECK_ARG(B >= 0 && n_out >= 0, "bad sizes");
+    DI2P_CHECK_ARG(B == 0 || n_out == 0 || (points && offsets && idx && pc), "null pointer");
+    DI2P_CHECK_ARG(!intensity_out || intensity, "intensity_out needs intensity");
+    DI2P_CHECK_ARG(!sn || normals, "sn needs normals");
+    if (B == 0 || n_out == 0) return 0;
+    hipLaunchKernelGGL(gather_ragged_kernel, dim3(di2p_cdiv(n_out, 256), B), dim3(256), 0, (hipStream_t)stream, points, intensity, normals, offsets,
+                       idx, transform, n_out, pc, intensity_out, sn);
+    DI2P_RETURN_LAUNCH();
+}

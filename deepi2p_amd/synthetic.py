@@ -225,3 +225,73 @@ def random_state_dict(opt, seed=0):
         else:
             sd[key] = 0.1 * torch.randn(shape, generator=gen)
     return sd
+
+
+# ----------------------------------------------------------------------------------------
+# Raw Velodyne scans (the input of deepi2p_amd.scan_prep): no KITTI .bin files are available, so tests and
+# tools/bench_scan_prep.py ray-cast an HDL-64-like sensor into a seeded scene.
+# ----------------------------------------------------------------------------------------
+def _ray_box(o, d, lo, hi):
+    """slab test of rays o + t d (d [n,3]) against an axis-aligned box; -> entry t (inf on a miss)"""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        inv = 1.0 / d
+        t0 = (lo[None] - o[None]) * inv
+        t1 = (hi[None] - o[None]) * inv
+    tmin = np.nanmax(np.minimum(t0, t1), axis=1)
+    tmax = np.nanmin(np.maximum(t0, t1), axis=1)
+    return np.where((tmax >= tmin) & (tmin > 0.0), tmin, np.inf)
+
+
+def _ray_pole(o, d, cx, cy, radius, z0, z1):
+    """vertical cylinder (centre cx, cy) between heights z0 and z1; -> entry t (inf on a miss)"""
+    ox, oy = o[0] - cx, o[1] - cy
+    a = d[:, 0] ** 2 + d[:, 1] ** 2
+    bq = 2.0 * (ox * d[:, 0] + oy * d[:, 1])
+    c = ox * ox + oy * oy - radius * radius
+    disc = bq * bq - 4.0 * a * c
+    with np.errstate(invalid="ignore", divide="ignore"):
+        t = (-bq - np.sqrt(disc)) / (2.0 * a)
+    z = o[2] + t * d[:, 2]
+    ok = (disc >= 0) & (t > 0) & (z >= z0) & (z <= z1)
+    return np.where(ok, t, np.inf)
+
+
+def make_velodyne_scan(rng, beams=64, azimuths=1800, max_range=120.0, dropout=0.03, range_sigma=0.02):
+    """One raw scan in the velodyne frame (x forward, y left, z up; sensor at the origin, 1.73 m above a ground plane):
+    f32[n, 4] rows (x, y, z, intensity) like a KITTI .bin, n ~ 100-130 k for the defaults.  HDL-64-like elevations from -24.8 to
+    +2 degrees; the scene is the ground, a handful of boxes and poles and far walls; per-surface intensity in [0, 1], Gaussian range
+    noise, randomly dropped returns and no-hit rays (nothing within max_range) removed."""
+    elev = np.deg2rad(np.linspace(-24.8, 2.0, beams))
+    azim = np.linspace(-np.pi, np.pi, azimuths, endpoint=False) + rng.uniform(0, 2 * np.pi / azimuths)
+    ee, aa = np.meshgrid(elev, azim, indexing="ij")
+    d = np.stack([np.cos(ee) * np.cos(aa), np.cos(ee) * np.sin(aa), np.sin(ee)], axis=-1).reshape(-1, 3)
+    o = np.zeros(3)
+    hits = [np.where(d[:, 2] < 0, -1.73 / np.minimum(d[:, 2], -1e-12), np.inf)]     # ground z = -1.73
+    refl = [0.25]
+    for _ in range(int(rng.integers(6, 10))):                                       # boxes: cars, buildings
+        c = np.array([rng.uniform(-40, 40), rng.uniform(-40, 40)])
+        if np.hypot(*c) < 6.0:
+            c *= 6.0 / max(np.hypot(*c), 1e-6)
+        half = np.array([rng.uniform(0.8, 6.0), rng.uniform(0.8, 6.0)])
+        hgt = rng.uniform(1.2, 8.0)
+        hits.append(_ray_box(o, d, np.array([c[0] - half[0], c[1] - half[1], -1.73]), np.array([c[0] + half[0], c[1] + half[1], -1.73 + hgt])))
+        refl.append(rng.uniform(0.1, 0.9))
+    for _ in range(int(rng.integers(4, 9))):                                        # poles
+        r = rng.uniform(5, 30)
+        a = rng.uniform(-np.pi, np.pi)
+        hits.append(_ray_pole(o, d, r * np.cos(a), r * np.sin(a), rng.uniform(0.08, 0.3), -1.73, rng.uniform(2.0, 6.0)))
+        refl.append(rng.uniform(0.3, 1.0))
+    wx, wy = rng.uniform(45, 70), rng.uniform(45, 70)                               # far walls on three sides, 10 m high
+    for lo, hi in (([wx, -wy, -1.73], [wx + 1, wy, 8.27]), ([-wx - 1, wy, -1.73], [wx, wy + 1, 8.27]),
+                   ([-wx - 1, -wy - 1, -1.73], [wx, -wy, 8.27])):
+        hits.append(_ray_box(o, d, np.array(lo), np.array(hi)))
+        refl.append(rng.uniform(0.05, 0.5))
+    T = np.stack(hits, axis=1)
+    which = np.argmin(T, axis=1)
+    t = T[np.arange(T.shape[0]), which]
+    keep = (t < max_range) & (rng.random(t.shape[0]) >= dropout)
+    t, which, dk = t[keep], which[keep], d[keep]
+    t = t + rng.normal(0.0, range_sigma, t.shape[0])
+    pts = dk * t[:, None]
+    inten = np.clip(np.asarray(refl)[which] + rng.normal(0.0, 0.05, t.shape[0]), 0.0, 1.0)
+    return np.concatenate([pts, inten[:, None]], axis=1).astype(np.float32)

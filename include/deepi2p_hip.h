@@ -407,6 +407,51 @@ long long di2p_random_choice_workspace_bytes(int B, int n_src);
 int di2p_random_choice(unsigned long long seed, int stream_id, int B, int n_src, int n_out, int32_t* idx_out, void* workspace,
                        void* stream);
 
+/* (additive, after ABI 7) di2p_random_choice_ragged: the same draw per frame with n_src = offsets[b+1] - offsets[b] read on the device (<= max_src, the
+ *   caller's per-frame capacity): frame b equals di2p_random_choice's frame b for that n_src; a frame shorter than n_out takes every index
+ *   floor(n_out / n_src) times, then the first n_out mod n_src of its draw (prep.downsample's rule); an empty frame gives -1.
+ *   workspace: di2p_random_choice_ragged_workspace_bytes(B, max_src). */
+long long di2p_random_choice_ragged_workspace_bytes(int B, int max_src);
+int di2p_random_choice_ragged(unsigned long long seed, int stream_id, int B, const int32_t* offsets, int max_src, int n_out, int32_t* idx_out,
+                              void* workspace, void* stream);
+
+/* ---- (additive, after ABI 7; detect by symbol) raw LiDAR scan preparation (csrc/scan_prep.hip) -------------------------------------------------------------------
+ * Replaces data/kitti/kitti_pc_bin_to_npy_with_downsample_sn.py:50-74 (Open3D voxel_down_sample, estimate_normals with a hybrid
+ * radius / max_nn search, orient_normals_to_align_with_direction([0,0,1]), cKDTree 1-NN intensity) and the loader's second voxel pass
+ * and random down-sample (data/kitti_pc_img_pose_loader.py:26-44,158-171,296-306,380).
+ * A batch is ragged: points f32[total,4] (KITTI .bin rows x, y, z, intensity), offsets i32[B+1] (device, offsets[0] = 0), cap >= total the
+ * fixed capacity every per-point / per-output-point buffer is sized for.  Coordinates must be finite (non-finite input is outside the
+ * contract).  Outputs are ragged too, with device offsets: out_offsets i32[B+1]; output point j of frame b is row out_offsets[b] + j.
+ * ONE workspace of di2p_scan_prep_workspace_bytes(B, cap) bytes (256-byte aligned) carries a batch through the three calls, in order:
+ * di2p_voxel_down_sample first, then di2p_estimate_normals and / or di2p_nearest_raw with the same B, cap and out_offsets.
+ *
+ * di2p_voxel_down_sample: Open3D VoxelDownSample, deterministic.  Per frame min_bound = min - voxel/2, voxel index floor((p - min_bound) /
+ *   voxel) in fp64; one output point per occupied voxel in ascending (ix, iy, iz), the fp64 mean of its members summed in ascending input
+ *   index; out_intensity = mean(i / max_frame(i)) * max_frame(i) (the loader's fake colour); out_normals (needs normals_in f32[total,3]) the
+ *   plain mean, not renormalised; out_keys i64 = ix << 42 | iy << 21 | iz.  Frames with at most min_points points are copied unchanged
+ *   (the loader's "> 2 * input_pt_num" rule; 0 = every frame is voxelised).  status i32[B] (may be NULL): 0 ok, 1 more than
+ *   max_frame_points (<= 2^20) points, 2 a bounding-box edge above max_extent or a voxel index above 2^21 - 1, 3 bad offsets; such a
+ *   frame has no output points.  max_extent / voxel must stay below 2^21 - 2.  out_intensity / out_normals / out_keys / status may be NULL.
+ * di2p_estimate_normals: per output point of the voxel call, the <= max_nn (<= 64) nearest output points of its frame with d^2 < radius^2
+ *   (fp64, the point itself included), the eigenvector of the smallest eigenvalue of their covariance, (0,0,1) for fewer than 3 neighbours
+ *   or a zero covariance, flipped so that n_z >= 0.  normals f32[cap,3]; nn_count i32[cap] and nn_idx i32[cap,max_nn] (frame-local
+ *   output indices by ascending (d^2, index), -1 padded) may be NULL.  max_extent / radius must stay below 2^21 - 4.
+ * di2p_nearest_raw: per output point, the nearest raw point of its frame (exact fp64 d^2, ties -> lower index): nn_idx i32[cap]
+ *   (frame-local raw index), nn_intensity f32[cap] its intensity, nn_dist2 f64[cap] (each may be NULL).  voxel as in the voxel call.
+ * di2p_gather_ragged: out[b,:,n] = src[offsets[b] + idx[b,n]] for points f32[total,3] / intensity f32[total] / normals f32[total,3] into
+ *   pc f32[B,3,n_out], intensity_out f32[B,1,n_out], sn f32[B,3,n_out]; idx < 0 gives zeros.  transform f64[B,4,4] (may be NULL): points
+ *   by [R|t], normals by R, in fp64. */
+long long di2p_scan_prep_workspace_bytes(int B, int cap);
+int di2p_voxel_down_sample(const float* points, const int32_t* offsets, int B, int cap, int max_frame_points, double voxel, double max_extent,
+                           int min_points, const float* normals_in, int32_t* out_offsets, float* out_points, float* out_intensity,
+                           float* out_normals, int64_t* out_keys, int32_t* status, void* workspace, void* stream);
+int di2p_estimate_normals(const int32_t* voxel_offsets, int B, int cap, double radius, int max_nn, double max_extent, float* normals,
+                          int32_t* nn_count, int32_t* nn_idx, void* workspace, void* stream);
+int di2p_nearest_raw(const float* points, const int32_t* offsets, const int32_t* voxel_offsets, int B, int cap, double voxel, int32_t* nn_idx,
+                     float* nn_intensity, double* nn_dist2, void* workspace, void* stream);
+int di2p_gather_ragged(const float* points, const float* intensity, const float* normals, const int32_t* offsets, const int32_t* idx,
+                       const double* transform, int B, int n_out, float* pc, float* intensity_out, float* sn, void* stream);
+
 /* ---- training-side head (losses and optimiser; the backward kernels follow below) ----------------
  * di2p_classifier_loss: the losses of models/multimodal_classifier.py:189-191 and d loss / d scores in one pass:
  *   coarse f32[B,2,N] with FocalLoss(alpha, gamma, 'mean') * coarse_loss_alpha (models/focal_loss.py:55-112), fine f32[B,L,N]
