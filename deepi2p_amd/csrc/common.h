@@ -62,7 +62,7 @@ enum Di2pOption {
     DI2P_OPT_HEAD_REG,              // 1: di2p_point_head runs the wave-autonomous kernel (one persistent 8-wave workgroup per compute unit: faster alone, slower beside other streams' kernels) instead of the LDS-tile kernel (bit-identical)
     DI2P_OPT_CONV_S2SCALAR,         // 1: stride-2 convolutions stage their operand with four dword loads per row (rounds 1-3) instead of aligned 8-float windows (bit-identical)
     DI2P_OPT_CONV_X3,               // bit mask of the 3x3 layers the host layer runs on di2p_conv3x3_x3 where it supports their shape (bf16 MFMA, exact three-way splits): bit s-1 = stride-1 layers of ResNet stage s, bit 4 = the stride-2 layers with their 1x1 downsample branch; 0: Winograd / direct fp32-MFMA kernels only (read by networks.py)
-    DI2P_OPT_CONV_X3_CFG,           // >= 0: force tile configuration 0..3 of di2p_conv3x3_x3 (default -1: cheapest by a cost model)
+    DI2P_OPT_CONV_X3_CFG,           // >= 0: force tile configuration 0..3 of di2p_conv3x3_x3 where the call passes cfg = -1 (default -1: cheapest by a cost model)
     DI2P_OPT_HEAD_X3,               // 1 (default): the host layer runs the coarse per-point head on di2p_point_head_x3 (bf16 MFMA, exact three-way splits, wave-autonomous); 0: di2p_point_head (fp32 MFMA, LDS tile; bit-identical to the three separate launches) (read by networks.py)
     DI2P_OPT_HEAD_X3_TAB,           // 1 (default): di2p_point_head_x3 keeps the frame's two node tables in LDS, one workgroup of eight waves (two per SIMD, 256 registers) per compute unit; 2: the same with four waves (one per SIMD, 512 registers); 0: gathers the tables from memory (no LDS: shares its compute units)
     DI2P_OPT_STEM_X3,               // 1 (default): the host layer runs conv1 + bn1 + relu + max-pool of the image branch as ONE launch of di2p_stem_x3 (bf16 MFMA, exact three-way splits) where it supports the image size; 0: di2p_conv7x7s2_stem + di2p_maxpool3x3s2 (fp32 MFMA) (read by networks.py)
@@ -74,3 +74,6 @@ enum Di2pOption {
 };
 long long di2p_opt(int id);
 int di2p_cu_count();      // compute units of the current device (cached per device)
+// (head_x3.hip) the bf16x3 split of Wt f32[K][M] (K % 16 == 0) in the A-fragment order of 32-row tiles, rows past M zero: the 3 KB entry of
+// (row tile t, K-step s) at t * tile_stride + s * step_stride; launch only
+void di2p_pack_a32(const float* Wt, int K, int M, int tiles, int tile_stride, int step_stride, void* Wp, void* stream);

@@ -9,8 +9,8 @@
 //   weights: split ONCE per checkpoint (di2p_bf16x3_pack of the tap-major [9 Cin][Cout] matrix: [K/8][Mp][3] x 8 bf16) and read straight
 //            from L2 as MFMA A fragments (a wave owns its Cout rows: nothing to share through LDS), one K-step ahead;
 //   activations: fp32 NCHW in memory.  A workgroup owns NSEG consecutive SEGMENTS (MF = 32 or 16 consecutive pixels of one output row) of
-//            one frame and MT output channels.  Per chunk of CK input channels (one K-step: 16 on v_mfma_f32_32x32x16_bf16, 32 on
-//            v_mfma_f32_16x16x32_bf16) the input PATCH under those segments (their rows plus the halo, zero padded) is split ONCE while it
+//            one frame and MT output channels.  Per chunk of CK input channels (one K-step: 16 on the 32 x 32 x 16 bf16 instruction, 32
+//            on the 16 x 16 x 32 one) the input PATCH under those segments (their rows plus the halo, zero padded) is split ONCE while it
 //            is staged into LDS -- [channel group of 8][patch position][plane] x 16 bytes, so that one ds_read_b128 is a B fragment -- and
 //            then serves all nine taps and every Cout tile of the workgroup: the inner loop is matrix instructions, 16-byte LDS reads and
 //            one address add per read (the pointwise bf16x3 kernel re-splits per 128-row workgroup: 9 vector instructions per MFMA; here
@@ -25,47 +25,26 @@
 
 #include <type_traits>
 
+#include "bf16x3.h"
 #include "common.h"
 
 namespace {
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using bf16x3::u32x4_t;
 
+// the matrix-instruction tile: 32 x 32 x 16 or 16 x 16 x 32 (bf16x3::mma picks the instruction by the accumulator type)
 template <int MF> struct Mma;
 template <> struct Mma<32> {
-    typedef f32x16 acc_t;
+    typedef bf16x3::f32x16 acc_t;
     static constexpr int NACC = 16, KS = 16;
-    static __device__ __forceinline__ acc_t mma(const u32x4_t& a, const u32x4_t& b, const acc_t& c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-    }
     // accumulator register r of lane (column nl, k-group cl) = row:
     static __device__ __forceinline__ int row(int r, int cl) { return (r & 3) + 8 * (r >> 2) + 4 * cl; }
 };
 template <> struct Mma<16> {
-    typedef f32x4 acc_t;
+    typedef bf16x3::f32x4 acc_t;
     static constexpr int NACC = 4, KS = 32;
-    static __device__ __forceinline__ acc_t mma(const u32x4_t& a, const u32x4_t& b, const acc_t& c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-    }
     static __device__ __forceinline__ int row(int r, int cl) { return r + 4 * cl; }
 };
-
-__device__ __forceinline__ float cx_hi16(float x) { return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, x) & 0xffff0000u); }
-__device__ __forceinline__ unsigned cx_pack_hi(float x0, float x1) {      // bf16(x0) in the low half, bf16(x1) in the high half (truncation)
-    return __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, x1), __builtin_bit_cast(unsigned, x0), 0x07060302u);
-}
-// eight consecutive input channels of one pixel -> the three planes of one LDS entry
-__device__ __forceinline__ void cx_split8(const float (&f)[8], u32x4_t& p1, u32x4_t& p2, u32x4_t& p3) {
-    float r[8], q[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { r[i] = f[i] - cx_hi16(f[i]); q[i] = r[i] - cx_hi16(r[i]); }
-    p1 = u32x4_t{cx_pack_hi(f[0], f[1]), cx_pack_hi(f[2], f[3]), cx_pack_hi(f[4], f[5]), cx_pack_hi(f[6], f[7])};
-    p2 = u32x4_t{cx_pack_hi(r[0], r[1]), cx_pack_hi(r[2], r[3]), cx_pack_hi(r[4], r[5]), cx_pack_hi(r[6], r[7])};
-    p3 = u32x4_t{cx_pack_hi(q[0], q[1]), cx_pack_hi(q[2], q[3]), cx_pack_hi(q[4], q[5]), cx_pack_hi(q[6], q[7])};
-}
 
 #ifndef DI2P_CX_CLK
 #define DI2P_CX_CLK 0
@@ -83,11 +62,10 @@ struct CxArgs {
 // WM x WN waves; STRIDE 1 / 2; DS: also the 1x1 / stride-2 convolution of the same input (centre tap, own weights and accumulators);
 // DBUF: two patch buffers.  ITEMS: (patch position, channel group) pairs a thread stages per chunk.  PWT: the patch row length W + 2 as a
 // compile-time constant (the nine tap offsets are then immediates of the LDS reads), 0: run-time (one address add per read).
-// SA: the five small products of a K-step go to a SECOND accumulator set.  The bf16 matrix instructions align every product to the largest
-// addend (normally the accumulator) and TRUNCATE what falls below its last bit (tools/probe_mfma_rounding.hip: 1 + 0.75 ulp -> 1 when the
-// 0.75 ulp is a product of the same instruction): small products added to a large accumulator lose their low bits, with a bias.  Kept apart,
-// they meet an accumulator 2^-8 times smaller.  Measured against fp64 on the four stride-1 shapes: rms error 3.6e-7 -> 1.5e-7 (K = 576) ...
-// 9.1e-7 -> 3.6e-7 (K = 4608), below both fp32-MFMA kernels (4.2e-7 ... 6.3e-7); same speed.  Every shipped instance has it on.
+// SA: the five small products of a K-step go to a SECOND accumulator set.  Added to a large accumulator, small products lose their low bits
+// with a bias (the bf16 matrix instructions truncate, bf16x3.h).  Kept apart, they meet an accumulator 2^-8 times smaller.  Measured against
+// fp64 on the four stride-1 shapes: rms error 3.6e-7 -> 1.5e-7 (K = 576) ... 9.1e-7 -> 3.6e-7 (K = 4608), below both fp32-MFMA kernels
+// (4.2e-7 ... 6.3e-7); same speed.  Every shipped instance has it on.
 #if DI2P_CX_CLK
 // experiment: where a wave's lifetime goes (s_memtime stamps summed over all waves): [0] set-up + first patch + first weights up to the first
 // barrier, [1] the chunks' taps, [2] the chunks' closing barriers, [3] epilogue, [7] waves
@@ -164,10 +142,10 @@ __global__ __launch_bounds__(256, 1) void conv3x3_x3_kernel(const CxArgs a) {
         float f[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) f[i] = g_ok[it] ? raw[it][i] : 0.0f;
-        u32x4_t p1, p2, p3;
-        cx_split8(f, p1, p2, p3);
+        u32x4_t p0, p1, p2;
+        bf16x3::split8(f, p0, p1, p2);
         u32x4_t* d = lds + buf * BUF + l_off[it];
-        d[0] = p1; d[1] = p2; d[2] = p3;
+        d[0] = p0; d[1] = p1; d[2] = p2;
     };
     // ---- weights: A fragments from memory; lane = (row nl of the tile, channel group cl of the K-step)
     int a_off[TM];
@@ -234,7 +212,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_x3_kernel(const CxArgs a) {
     auto tap_mma = [&](int slot, int set, int tap) __attribute__((always_inline)) {
 #define DI2P_CX_PROD(ACC, QA, QB)                                                                                                       \
     _Pragma("unroll") for (int i = 0; i < TM; ++i) _Pragma("unroll") for (int j = 0; j < TN; ++j)                                       \
-        ACC[i][j] = M::mma(af[slot][i][QA], bf[set][j][QB], ACC[i][j]);
+        ACC[i][j] = bf16x3::mma(af[slot][i][QA], bf[set][j][QB], ACC[i][j]);
         if constexpr (SA) {
             DI2P_CX_PROD(accs, 2, 0) DI2P_CX_PROD(accs, 1, 1) DI2P_CX_PROD(accs, 0, 2) DI2P_CX_PROD(accs, 1, 0) DI2P_CX_PROD(accs, 0, 1)
         } else {
@@ -246,7 +224,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_x3_kernel(const CxArgs a) {
             if (tap == 4) {
 #define DI2P_CX_PROD(QA, QB)                                                                                                            \
     _Pragma("unroll") for (int i = 0; i < TM; ++i) _Pragma("unroll") for (int j = 0; j < TN; ++j)                                       \
-        acc_ds[i][j] = M::mma(af_ds[i][QA], bf[set][j][QB], acc_ds[i][j]);
+        acc_ds[i][j] = bf16x3::mma(af_ds[i][QA], bf[set][j][QB], acc_ds[i][j]);
                 DI2P_CX_PROD(2, 0) DI2P_CX_PROD(1, 1) DI2P_CX_PROD(0, 2) DI2P_CX_PROD(1, 0) DI2P_CX_PROD(0, 1) DI2P_CX_PROD(0, 0)
 #undef DI2P_CX_PROD
             }
@@ -490,22 +468,24 @@ const char* cx_size_limit(int B, int Cin, int H, int W, int Cout, const CxPlan* 
 
 }  // namespace
 
-// 1 if di2p_conv3x3_x3 can run this layer (some tile configuration fits its shape and the LDS, and the sizes fit the kernels' offsets), else 0.
-extern "C" int di2p_conv3x3_x3_supported(int B, int Cin, int H, int W, int Cout, int stride) {
-    if (B < 1 || Cin < 16 || H < 1 || W < 1 || Cout < 1 || (stride != 1 && stride != 2)) return 0;
+// 1 if di2p_conv3x3_x3 can run this layer with tile configuration `cfg` (-1: the knob conv_x3_cfg, whose default -1 is the cheapest by a
+// cost model; it fits the layer's shape and the LDS, and the sizes fit the kernels' offsets), else 0.
+extern "C" int di2p_conv3x3_x3_supported(int B, int Cin, int H, int W, int Cout, int stride, int cfg) {
+    if (B < 1 || Cin < 16 || H < 1 || W < 1 || Cout < 1 || (stride != 1 && stride != 2) || cfg < -1 || cfg > 3) return 0;
     if (stride == 2 && (H % 2 || W % 2)) return 0;
-    const CxPlan best = cx_best(B, Cin, H, W, Cout, stride, di2p_opt(DI2P_OPT_CONV_X3_CFG), nullptr);
+    const CxPlan best = cx_best(B, Cin, H, W, Cout, stride, cfg >= 0 ? cfg : di2p_opt(DI2P_OPT_CONV_X3_CFG), nullptr);
     return best.cfg >= 0 && cx_size_limit(B, Cin, H, W, Cout, &best) == nullptr ? 1 : 0;
 }
 
 // y f32[B,Cout,OH,OW] = relu?( scale * conv3x3(x f32[B,Cin,H,W]; pad 1, stride 1|2) + shift + residual ), weights Wp = di2p_bf16x3_pack of
 // the tap-major matrix Wt[(kh*3+kw)*Cin + ci][Cout].  Optional second output of the SAME input (stride 2 only): y_ds f32[B,Cout,OH,OW] =
 // scale_ds * conv1x1/stride-2(x) + shift_ds with Wp_ds = di2p_bf16x3_pack of Wt_ds[Cin][Cout] (the BasicBlock's downsample branch,
-// models/resnet.py:160-164,62-63).
+// models/resnet.py:160-164,62-63).  cfg: the tile configuration, as for di2p_conv3x3_x3_supported.
 extern "C" int di2p_conv3x3_x3(const float* x, const void* Wp, const float* scale, const float* shift, const float* residual, float* y, int B,
                                int Cin, int H, int W, int Cout, int stride, int relu, const void* Wp_ds, const float* scale_ds,
-                               const float* shift_ds, float* y_ds, void* stream) {
+                               const float* shift_ds, float* y_ds, int cfg, void* stream) {
     DI2P_CHECK_ARG(x && Wp && scale && shift && y, "null pointer");
+    DI2P_CHECK_ARG(cfg >= -1 && cfg <= 3, "cfg is a tile configuration 0..3 or -1 (the knob conv_x3_cfg)");
     DI2P_CHECK_ARG(B >= 0 && Cin >= 16 && H >= 1 && W >= 1 && Cout >= 1 && (stride == 1 || stride == 2), "bad shape");
     DI2P_CHECK_ARG(stride == 1 || (H % 2 == 0 && W % 2 == 0), "stride 2 needs even H and W");
     DI2P_CHECK_ARG(((uintptr_t)Wp & 15) == 0 && ((uintptr_t)Wp_ds & 15) == 0, "packed weights must be 16-byte aligned");
@@ -518,7 +498,7 @@ extern "C" int di2p_conv3x3_x3(const float* x, const void* Wp, const float* scal
     }
     if (B == 0) return 0;
     int inst = -1;
-    const CxPlan best = cx_best(B, Cin, H, W, Cout, stride, di2p_opt(DI2P_OPT_CONV_X3_CFG), &inst);
+    const CxPlan best = cx_best(B, Cin, H, W, Cout, stride, cfg >= 0 ? cfg : di2p_opt(DI2P_OPT_CONV_X3_CFG), &inst);
     DI2P_CHECK_ARG(best.cfg >= 0, "no kernel instance fits this shape (needs OW % 32 == 0 and Cin % 16 == 0, or OW % 16 == 0 and Cin % 32 == 0, and a patch that fits the LDS)");
     CxArgs a{};
     a.x = x; a.Wp = (const u32x4_t*)Wp; a.scale = scale; a.shift = shift; a.residual = residual; a.y = y;

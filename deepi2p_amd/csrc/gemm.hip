@@ -5,6 +5,7 @@
 // models/layers_pc.py:808-813, models/networks_united.py:139-197): concatenation, gather-by-index
 // and group-broadcast are done by the B-operand loader, BN/bias/ReLU/max-over-K/interpolated-add by
 // the epilogue, so none of those intermediates ever exists in HBM.
+#include "bf16x3.h"
 #include "mfma_tile.h"
 
 #include <stdint.h>
@@ -131,24 +132,9 @@ struct LoaderConcat4 {
     __device__ __forceinline__ void fix(float4&, int, const Info&) const {}
 };
 
-// bf16x3 (see the section of that name below): the exact three-way split of fp32 values into truncated bf16 terms
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float x3_hi16(float x) { return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, x) & 0xffff0000u); }
-// the bf16 (high halves) of two floats in one word: low half <- x0, high half <- x1
-__device__ __forceinline__ unsigned x3_pack_hi(float x0, float x1) {
-    return __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, x1), __builtin_bit_cast(unsigned, x0), 0x07060302u);
-}
-// four consecutive k of one column -> three planes of 4 x bf16
-__device__ __forceinline__ void x3_split4(float f0, float f1, float f2, float f3, u32x2_t& p1, u32x2_t& p2, u32x2_t& p3) {
-    const float r0 = f0 - x3_hi16(f0), r1 = f1 - x3_hi16(f1), r2 = f2 - x3_hi16(f2), r3 = f3 - x3_hi16(f3);
-    const float q0 = r0 - x3_hi16(r0), q1 = r1 - x3_hi16(r1), q2 = r2 - x3_hi16(r2), q3 = r3 - x3_hi16(r3);
-    p1 = u32x2_t{x3_pack_hi(f0, f1), x3_pack_hi(f2, f3)};
-    p2 = u32x2_t{x3_pack_hi(r0, r1), x3_pack_hi(r2, r3)};
-    p3 = u32x2_t{x3_pack_hi(q0, q1), x3_pack_hi(q2, q3)};
-}
+// bf16x3 (see the section of that name below and bf16x3.h): the exact three-way split of fp32 values into truncated bf16 terms
+using bf16x3::u32x4_t;
+using bf16x3::u32x2_t;
 
 struct EpiDev {
     const float* scale;
@@ -336,7 +322,7 @@ struct EpiPointwiseT {
             const int m = mrow0 + 8 * g;
             if (m < M) {
                 u32x2_t p1, p2, p3;
-                x3_split4(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3], p1, p2, p3);
+                bf16x3::split4(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3], p1, p2, p3);
                 u32x2_t* q = p + (long long)(m >> 2) * N;
                 q[0] = p1; q[ps] = p2; q[2 * ps] = p3;
             }
@@ -932,15 +918,10 @@ void launch_pw_vec(bool dense, const SrcDev& s, const float* Wt, float* Y, int B
 
 
 // ----------------------------------------------------------------------------------------------------------------------------------
-// "bf16x3": fp32 contractions through bf16 matrix instructions with an EXACT three-way operand split.
-//   x = x1 + x2 + x3 (three truncated bf16 terms of 8 significand bits each: 24 bits, nothing is lost), and
-//   a * b = a1 b1 + (a1 b2 + a2 b1) + (a1 b3 + a2 b2 + a3 b1) + terms below 2^-24 |a| |b|        -- six bf16 products, fp32 accumulation,
-// smallest terms first.  v_mfma_f32_32x32x16_bf16 does K = 16 in 32 cycles where v_mfma_f32_32x32x2_f32 needs 8 x 64: six of them are
-// 2.67x the fp32-MFMA rate.  Against an fp64 contraction the result is as accurate as the fp32-MFMA kernel's (the dropped terms are below the
-// rounding of the fp32 accumulation; tests/test_gpu_contractions.py asserts err_bf16x3 <= err_fp32mfma on the golden operands).
+// "bf16x3": fp32 contractions through bf16 matrix instructions with an EXACT three-way operand split (the arithmetic, and why it is exact:
+// bf16x3.h); tests/test_gpu_contractions.py asserts err_bf16x3 <= err_fp32mfma against fp64 on the golden operands.
 // Used for the GEMM-shaped layers (K >= 128, M % 128 == 0: the kNN-fusion layers and the node-level PointNets); narrow point layers are
-// memory-bound and stay on the fp32 kernels.  Non-finite inputs: x = +-inf splits into (inf, NaN, NaN), i.e. the output is NaN where the
-// fp32 kernel gives +-inf or NaN -- non-finite either way.
+// memory-bound and stay on the fp32 kernels.
 //   weights: split ONCE (di2p_bf16x3_pack) into [Kp/8][Mp][3] x 8 bf16 (Kp = K rounded up to 32, Mp = M rounded up to 128, zero filled) and read
 //            straight from L2 as MFMA A fragments;
 //   activations: fp32 in memory, loaded through the SAME loaders as the fp32 kernels and split while they are staged into LDS
@@ -971,10 +952,10 @@ __global__ __launch_bounds__(256, 2) void pointwise_gemm_x3_kernel(SrcDev srcs, 
     };
     auto sstore = [&](int buf) {
         u32x2_t p1[4], p2[4], p3[4];
-        x3_split4(st[0].x, st[1].x, st[2].x, st[3].x, p1[0], p2[0], p3[0]);
-        x3_split4(st[0].y, st[1].y, st[2].y, st[3].y, p1[1], p2[1], p3[1]);
-        x3_split4(st[0].z, st[1].z, st[2].z, st[3].z, p1[2], p2[2], p3[2]);
-        x3_split4(st[0].w, st[1].w, st[2].w, st[3].w, p1[3], p2[3], p3[3]);
+        bf16x3::split4(st[0].x, st[1].x, st[2].x, st[3].x, p1[0], p2[0], p3[0]);
+        bf16x3::split4(st[0].y, st[1].y, st[2].y, st[3].y, p1[1], p2[1], p3[1]);
+        bf16x3::split4(st[0].z, st[1].z, st[2].z, st[3].z, p1[2], p2[2], p3[2]);
+        bf16x3::split4(st[0].w, st[1].w, st[2].w, st[3].w, p1[3], p2[3], p3[3]);
         u32x4_t* d1 = reinterpret_cast<u32x4_t*>(&Bs[buf][0][skg][shh][4 * cq]);
         u32x4_t* d2 = reinterpret_cast<u32x4_t*>(&Bs[buf][1][skg][shh][4 * cq]);
         u32x4_t* d3 = reinterpret_cast<u32x4_t*>(&Bs[buf][2][skg][shh][4 * cq]);
@@ -1015,7 +996,7 @@ __global__ __launch_bounds__(256, 2) void pointwise_gemm_x3_kernel(SrcDev srcs, 
         // smallest terms first; four independent accumulators between two matrix instructions of one chain
 #define DI2P_X3_PROD(QA, QB)                                                                                                          \
     _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int j = 0; j < 2; ++j)                                      \
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, af[sub][i][QA]), __builtin_bit_cast(bf16x8_t, bf[j][QB]), acc[i][j], 0, 0, 0);
+        acc[i][j] = bf16x3::mma(af[sub][i][QA], bf[j][QB], acc[i][j]);
         DI2P_X3_PROD(2, 0) DI2P_X3_PROD(1, 1) DI2P_X3_PROD(0, 2)
         DI2P_X3_PROD(1, 0) DI2P_X3_PROD(0, 1)
         DI2P_X3_PROD(0, 0)
@@ -1123,7 +1104,7 @@ __global__ __launch_bounds__(256, 2) void pointwise_gemm_x3p_kernel(const u32x4_
         DI2P_MFMA_BEGIN();
 #define DI2P_X3_PROD(QA, QB)                                                                                                          \
     _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int j = 0; j < 2; ++j)                                      \
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, af[sub][i][QA]), __builtin_bit_cast(bf16x8_t, bf[j][QB]), acc[i][j], 0, 0, 0);
+        acc[i][j] = bf16x3::mma(af[sub][i][QA], bf[j][QB], acc[i][j]);
         DI2P_X3_PROD(2, 0) DI2P_X3_PROD(1, 1) DI2P_X3_PROD(0, 2)
         DI2P_X3_PROD(1, 0) DI2P_X3_PROD(0, 1)
         DI2P_X3_PROD(0, 0)
@@ -1237,7 +1218,7 @@ __global__ __launch_bounds__(512, 1) void pointwise_gemm_x3p8_kernel(const u32x4
         DI2P_MFMA_BEGIN();
 #define DI2P_X3_PROD(QA, QB)                                                                                                          \
     _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int j = 0; j < 2; ++j)                                      \
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, af[i][QA]), __builtin_bit_cast(bf16x8_t, bf[j][QB]), acc[i][j], 0, 0, 0);
+        acc[i][j] = bf16x3::mma(af[i][QA], bf[j][QB], acc[i][j]);
         DI2P_X3_PROD(2, 0) DI2P_X3_PROD(1, 1) DI2P_X3_PROD(0, 2)
         DI2P_X3_PROD(1, 0) DI2P_X3_PROD(0, 1)
         DI2P_X3_PROD(0, 0)
@@ -1293,10 +1274,11 @@ __global__ __launch_bounds__(256) void bf16x3_pack_kernel(const float* __restric
                 a = MODE == 1 ? Wt[((long long)m * ci_n + c) * 9 + tap] : Wt[((long long)c * M + m) * 9 + 8 - tap];
             }
         }
-        const float a1 = x3_hi16(a), r1 = a - a1, a2 = x3_hi16(r1), r2 = r1 - a2;
-        d[0 * ps + i] = (unsigned short)(__builtin_bit_cast(unsigned, a1) >> 16);
-        d[1 * ps + i] = (unsigned short)(__builtin_bit_cast(unsigned, a2) >> 16);
-        d[2 * ps + i] = (unsigned short)(__builtin_bit_cast(unsigned, r2) >> 16);
+        float p0, p1, p2;
+        bf16x3::split(a, p0, p1, p2);
+        d[0 * ps + i] = bf16x3::bits(p0);
+        d[1 * ps + i] = bf16x3::bits(p1);
+        d[2 * ps + i] = bf16x3::bits(p2);
     }
 }
 
@@ -1320,13 +1302,15 @@ __global__ __launch_bounds__(256) void bf16x3_pack_conv_kernel(const float* __re
         }
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) {
+        // bf16x3::split8 written out on v[.][tap] (through split8 the compiler allocates registers differently)
         float r[8], q[8];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) { r[i] = v[i][tap] - x3_hi16(v[i][tap]); q[i] = r[i] - x3_hi16(r[i]); }
+        for (int i = 0; i < 8; ++i) { r[i] = v[i][tap] - bf16x3::hi16(v[i][tap]); q[i] = r[i] - bf16x3::hi16(r[i]); }
         u32x4_t* d = reinterpret_cast<u32x4_t*>(Wp + ((long long)(tap * c8n + c8) * Mp + m) * 24);          // three 16-byte stores per entry
-        d[0] = u32x4_t{x3_pack_hi(v[0][tap], v[1][tap]), x3_pack_hi(v[2][tap], v[3][tap]), x3_pack_hi(v[4][tap], v[5][tap]), x3_pack_hi(v[6][tap], v[7][tap])};
-        d[1] = u32x4_t{x3_pack_hi(r[0], r[1]), x3_pack_hi(r[2], r[3]), x3_pack_hi(r[4], r[5]), x3_pack_hi(r[6], r[7])};
-        d[2] = u32x4_t{x3_pack_hi(q[0], q[1]), x3_pack_hi(q[2], q[3]), x3_pack_hi(q[4], q[5]), x3_pack_hi(q[6], q[7])};
+        d[0] = u32x4_t{bf16x3::pack_hi(v[0][tap], v[1][tap]), bf16x3::pack_hi(v[2][tap], v[3][tap]), bf16x3::pack_hi(v[4][tap], v[5][tap]),
+                       bf16x3::pack_hi(v[6][tap], v[7][tap])};
+        d[1] = u32x4_t{bf16x3::pack_hi(r[0], r[1]), bf16x3::pack_hi(r[2], r[3]), bf16x3::pack_hi(r[4], r[5]), bf16x3::pack_hi(r[6], r[7])};
+        d[2] = u32x4_t{bf16x3::pack_hi(q[0], q[1]), bf16x3::pack_hi(q[2], q[3]), bf16x3::pack_hi(q[4], q[5]), bf16x3::pack_hi(q[6], q[7])};
     }
 }
 

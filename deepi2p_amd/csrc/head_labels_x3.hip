@@ -25,13 +25,13 @@
 // scan with a strict comparison.
 #include <stdint.h>
 
+#include "bf16x3.h"
 #include "common.h"
 
 namespace {
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using bf16x3::u32x4_t;
+using bf16x3::f32x16;
 
 constexpr int HL_K = 256;                  // hidden width (input and output of layer 1, input of layer 2)
 constexpr int HL_KS = HL_K / 16;           // K-steps of one layer
@@ -48,21 +48,6 @@ struct HlArgs {
     int N, nblk, total;                                  // nblk = 64-point tiles per frame; total = B * nblk
 };
 
-__device__ __forceinline__ float hl_hi16(float x) { return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, x) & 0xffff0000u); }
-__device__ __forceinline__ unsigned hl_pack_hi(float x0, float x1) {
-    return __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, x1), __builtin_bit_cast(unsigned, x0), 0x07060302u);
-}
-// x = p0 + p1 + p2 exactly, each p a bf16 (the upper half of an fp32)
-__device__ __forceinline__ void hl_split(float x, float& p0, float& p1, float& p2) {
-    p0 = hl_hi16(x);
-    const float r = x - p0;
-    p1 = hl_hi16(r);
-    p2 = r - p1;
-}
-__device__ __forceinline__ f32x16 hl_mma(const u32x4_t& a, const u32x4_t& b, const f32x16& c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
-
 // (v, i) ranks above (w, j): NaN above every number (the lower channel among NaNs), else the larger value, else the lower channel.
 // An empty slot is (-inf, INT_MAX): every real candidate ranks above it.
 __device__ __forceinline__ bool hl_better(float v, int i, float w, int j) {
@@ -76,12 +61,12 @@ __device__ __forceinline__ void hl_take(float& bv, int& bi, float v, int i) {
 
 // One K-step of the six products (small terms first, like head_x3.hip): acc += A (3 planes) x B (3 planes)
 __device__ __forceinline__ f32x16 hl_kstep(const u32x4_t (&a)[3], const u32x4_t (&b)[3], f32x16 acc) {
-    acc = hl_mma(a[2], b[0], acc);
-    acc = hl_mma(a[1], b[1], acc);
-    acc = hl_mma(a[1], b[0], acc);
-    acc = hl_mma(a[0], b[2], acc);
-    acc = hl_mma(a[0], b[1], acc);
-    acc = hl_mma(a[0], b[0], acc);
+    acc = bf16x3::mma(a[2], b[0], acc);
+    acc = bf16x3::mma(a[1], b[1], acc);
+    acc = bf16x3::mma(a[1], b[0], acc);
+    acc = bf16x3::mma(a[0], b[2], acc);
+    acc = bf16x3::mma(a[0], b[1], acc);
+    acc = bf16x3::mma(a[0], b[0], acc);
     return acc;
 }
 
@@ -154,11 +139,11 @@ __global__ __launch_bounds__(HL_NW * 64, 1) void point_head_labels_x3_kernel(con
         for (int i = 0; i < 4; ++i) {
             float p0[8], p1[8], p2[8];
 #pragma unroll
-            for (int e = 0; e < 8; ++e) hl_split(xr[i][e], p0[e], p1[e], p2[e]);
+            for (int e = 0; e < 8; ++e) bf16x3::split(xr[i][e], p0[e], p1[e], p2[e]);
             const int f = tid + 512 * i;
-            planes[0 * HL_PLANE_U4 + f] = u32x4_t{hl_pack_hi(p0[0], p0[1]), hl_pack_hi(p0[2], p0[3]), hl_pack_hi(p0[4], p0[5]), hl_pack_hi(p0[6], p0[7])};
-            planes[1 * HL_PLANE_U4 + f] = u32x4_t{hl_pack_hi(p1[0], p1[1]), hl_pack_hi(p1[2], p1[3]), hl_pack_hi(p1[4], p1[5]), hl_pack_hi(p1[6], p1[7])};
-            planes[2 * HL_PLANE_U4 + f] = u32x4_t{hl_pack_hi(p2[0], p2[1]), hl_pack_hi(p2[2], p2[3]), hl_pack_hi(p2[4], p2[5]), hl_pack_hi(p2[6], p2[7])};
+            planes[0 * HL_PLANE_U4 + f] = u32x4_t{bf16x3::pack_hi(p0[0], p0[1]), bf16x3::pack_hi(p0[2], p0[3]), bf16x3::pack_hi(p0[4], p0[5]), bf16x3::pack_hi(p0[6], p0[7])};
+            planes[1 * HL_PLANE_U4 + f] = u32x4_t{bf16x3::pack_hi(p1[0], p1[1]), bf16x3::pack_hi(p1[2], p1[3]), bf16x3::pack_hi(p1[4], p1[5]), bf16x3::pack_hi(p1[6], p1[7])};
+            planes[2 * HL_PLANE_U4 + f] = u32x4_t{bf16x3::pack_hi(p2[0], p2[1]), bf16x3::pack_hi(p2[2], p2[3]), bf16x3::pack_hi(p2[4], p2[5]), bf16x3::pack_hi(p2[6], p2[7])};
         }
     };
 
@@ -185,13 +170,13 @@ __global__ __launch_bounds__(HL_NW * 64, 1) void point_head_labels_x3_kernel(con
                     const int row = 32 * wave + 8 * g + 4 * h + q;
                     float v = acc1[j][4 * g + q] * a.sc1[row] + a.sh1[row];
                     if (a.relu1) v = fmaxf(v, 0.0f);
-                    hl_split(v, p[0][q], p[1][q], p[2][q]);
+                    bf16x3::split(v, p[0][q], p[1][q], p[2][q]);
                 }
                 const int s = 2 * wave + (g >> 1);
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl) {
                     uint2* dst = reinterpret_cast<uint2*>(planes + (pl * HL_KS + s) * 2 * 64 + j * 64 + nl + 32 * (g & 1)) + h;
-                    *dst = make_uint2(hl_pack_hi(p[pl][0], p[pl][1]), hl_pack_hi(p[pl][2], p[pl][3]));
+                    *dst = make_uint2(bf16x3::pack_hi(p[pl][0], p[pl][1]), bf16x3::pack_hi(p[pl][2], p[pl][3]));
                 }
             }
         // the next tile's y0 flies under layer 2
@@ -256,25 +241,6 @@ __global__ __launch_bounds__(HL_NW * 64, 1) void point_head_labels_x3_kernel(con
     }
 }
 
-// Wt f32[K][M] (k-major) -> fragment order [ceil(M / 32) row tiles][K / 16][3 planes][64 lanes] x 8 bf16: lane (row i = lane & 31, half = lane >> 5)
-// of row tile t holds k = 16 s + 8 half + 0..7 of row 32 t + i; rows M .. 32 ceil(M / 32) - 1 are zero.  One thread per (tile, K-step, lane).
-__global__ __launch_bounds__(256) void head_labels_x3_pack_kernel(const float* __restrict__ Wt, unsigned short* __restrict__ Wp, int K, int M, int tiles) {
-    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int ks = K / 16;
-    if (t >= (long long)tiles * ks * 64) return;
-    const int lane = (int)(t & 63), s = (int)((t >> 6) % ks), tile = (int)((t >> 6) / ks);
-    const int row = 32 * tile + (lane & 31), k0 = 16 * s + 8 * (lane >> 5);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const float v = row < M ? Wt[(long long)(k0 + e) * M + row] : 0.0f;
-        float pl[3];
-        hl_split(v, pl[0], pl[1], pl[2]);
-#pragma unroll
-        for (int p = 0; p < 3; ++p)
-            Wp[((((long long)tile * ks + s) * 3 + p) * 64 + lane) * 8 + e] = (unsigned short)(__builtin_bit_cast(unsigned, pl[p]) >> 16);
-    }
-}
-
 }  // namespace
 
 extern "C" long long di2p_head_labels_x3_packed_bytes(int K, int P) {
@@ -287,9 +253,8 @@ extern "C" int di2p_head_labels_x3_pack(const float* Wt, int K, int P, void* Wp,
     DI2P_CHECK_ARG(Wt && Wp, "null pointer");
     DI2P_CHECK_ARG(K >= 16 && K % 16 == 0 && P >= 1, "needs K % 16 == 0 and P >= 1");
     DI2P_CHECK_ARG(((uintptr_t)Wp & 15) == 0, "packed weights must be 16-byte aligned");
-    const int tiles = (P + 31) / 32;
-    hipLaunchKernelGGL(head_labels_x3_pack_kernel, dim3(di2p_cdiv((long long)tiles * (K / 16) * 64, 256)), dim3(256), 0, (hipStream_t)stream, Wt,
-                       (unsigned short*)Wp, K, P, tiles);
+    // fragment order [ceil(P / 32) row tiles][K / 16][3 planes][64 lanes] x 8 bf16, rows P .. 32 ceil(P / 32) - 1 zero
+    di2p_pack_a32(Wt, K, P, (P + 31) / 32, K / 16, 1, Wp, stream);
     DI2P_RETURN_LAUNCH();
 }
 

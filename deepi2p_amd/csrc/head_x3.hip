@@ -18,13 +18,13 @@
 
 #include <type_traits>
 
+#include "bf16x3.h"
 #include "common.h"
 
 namespace {
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using bf16x3::u32x4_t;
+using bf16x3::f32x16;
 
 constexpr int HX_M = 128, HX_TM = 4, HX_TROW = HX_M + 4;      // table row stride in LDS (floats): 528 B, 16-byte aligned, off the 512-byte period
 
@@ -37,22 +37,6 @@ struct HxArgs {
     float* out;                                                                 // f32[B, P, N]
     int relu0, relu1, relu2, P, N, nblk, total, parts;                          // nblk = 32-point blocks per frame; total = B * nblk; TAB_LDS: workgroups per frame
 };
-
-__device__ __forceinline__ float hx_hi16(float x) { return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, x) & 0xffff0000u); }
-__device__ __forceinline__ unsigned hx_pack_hi(float x0, float x1) {
-    return __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, x1), __builtin_bit_cast(unsigned, x0), 0x07060302u);
-}
-__device__ __forceinline__ void hx_split8(const float (&f)[8], u32x4_t (&p)[3]) {
-    float r[8], q[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { r[i] = f[i] - hx_hi16(f[i]); q[i] = r[i] - hx_hi16(r[i]); }
-    p[0] = u32x4_t{hx_pack_hi(f[0], f[1]), hx_pack_hi(f[2], f[3]), hx_pack_hi(f[4], f[5]), hx_pack_hi(f[6], f[7])};
-    p[1] = u32x4_t{hx_pack_hi(r[0], r[1]), hx_pack_hi(r[2], r[3]), hx_pack_hi(r[4], r[5]), hx_pack_hi(r[6], r[7])};
-    p[2] = u32x4_t{hx_pack_hi(q[0], q[1]), hx_pack_hi(q[2], q[3]), hx_pack_hi(q[4], q[5]), hx_pack_hi(q[6], q[7])};
-}
-__device__ __forceinline__ f32x16 hx_mma(const u32x4_t& a, const u32x4_t& b, const f32x16& c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
 
 // TAB_LDS: the frame's node tables in LDS (one 8-wave workgroup per compute unit, two waves per SIMD); KS0 = K0 / 16 K-steps of layer 0; NW waves
 // SYNC (TAB_LDS only): the workgroup's waves take every K-step together (one s_barrier each), so that the 12 KB weight panel of a K-step is
@@ -167,7 +151,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void point_head_x3_kernel(const HxAr
         };
         // ks_next < 0: nothing to request
         auto kstep = [&](int slot, const u32x4_t (&bf)[3], const __amdgpu_buffer_rsrc_t& wr, int ks_next) __attribute__((always_inline)) {
-#define DI2P_HX_PROD(QA, QB) _Pragma("unroll") for (int i = 0; i < HX_TM; ++i) acc[i] = hx_mma(af[slot][i][QA], bf[QB], acc[i]);
+#define DI2P_HX_PROD(QA, QB) _Pragma("unroll") for (int i = 0; i < HX_TM; ++i) acc[i] = bf16x3::mma(af[slot][i][QA], bf[QB], acc[i]);
             if constexpr (SYNC) __builtin_amdgcn_s_barrier();
             if constexpr (DEEP) {
                 if (ks_next >= 0) { a_load(slot ^ 1, wr, ks_next, 2); a_load(slot ^ 1, wr, ks_next, 1); a_load(slot ^ 1, wr, ks_next, 0); }
@@ -187,11 +171,11 @@ __global__ __launch_bounds__(NW * 64, MINW) void point_head_x3_kernel(const HxAr
             // the split of K-step s + 1 (about fifty vector instructions) rides between the matrix instructions of K-step s: two fragment sets,
             // one scheduling region per K-step laid out as "one matrix instruction, two vector instructions"
             u32x4_t bfr[2][3];
-            hx_split8(xall[0], bfr[0]);
+            bf16x3::split8(xall[0], bfr[0][0], bfr[0][1], bfr[0][2]);
 #pragma unroll
             for (int s = 0; s < KS0; ++s) {
                 __builtin_amdgcn_sched_barrier(0);
-                if (s + 1 < KS0) hx_split8(xall[s + 1], bfr[(s + 1) & 1]);
+                if (s + 1 < KS0) bf16x3::split8(xall[s + 1], bfr[(s + 1) & 1][0], bfr[(s + 1) & 1][1], bfr[(s + 1) & 1][2]);
                 kstep(s & 1, bfr[s & 1], w0r, s + 1 < KS0 ? s + 1 : -1);
 #pragma unroll
                 for (int u = 0; u < 6 * HX_TM; ++u) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, 3, 0); }
@@ -273,11 +257,11 @@ __global__ __launch_bounds__(NW * 64, MINW) void point_head_x3_kernel(const HxAr
             for (int r = 0; r < 16; ++r) acc[i][r] = 0.0f;
         {
             u32x4_t bfr[2][3];
-            hx_split8(f1[0], bfr[0]);
+            bf16x3::split8(f1[0], bfr[0][0], bfr[0][1], bfr[0][2]);
 #pragma unroll
             for (int s = 0; s < 2 * HX_TM; ++s) {
                 __builtin_amdgcn_sched_barrier(0);
-                if (s + 1 < 2 * HX_TM) hx_split8(f1[s + 1], bfr[(s + 1) & 1]);
+                if (s + 1 < 2 * HX_TM) bf16x3::split8(f1[s + 1], bfr[(s + 1) & 1][0], bfr[(s + 1) & 1][1], bfr[(s + 1) & 1][2]);
                 kstep(s & 1, bfr[s & 1], w1r, s + 1 < 2 * HX_TM ? s + 1 : -1);
 #pragma unroll
                 for (int u = 0; u < 6 * HX_TM; ++u) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, 3, 0); }
@@ -334,25 +318,33 @@ __global__ __launch_bounds__(NW * 64, MINW) void point_head_x3_kernel(const HxAr
     }
 }
 
-// Wt f32[K][128] (k-major) -> fragment order [K / 16][4 row tiles][3 planes][64 lanes] x 8 bf16: lane (row i = lane & 31, half = lane >> 5) of
-// row tile t holds k = 16 s + 8 half + 0..7 of row 32 t + i.  One thread per (K-step, tile, lane).
-__global__ __launch_bounds__(256) void head_x3_pack_kernel(const float* __restrict__ Wt, unsigned short* __restrict__ Wp, int K) {
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= (K / 16) * HX_TM * 64) return;
-    const int lane = t & 63, tile = (t >> 6) & 3, s = t >> 8;
+// Wt f32[K][M] (k-major) -> fragment order, one 3 KB entry [3 planes][64 lanes] x 8 bf16 per (row tile t, K-step s), at t * tile_stride +
+// s * step_stride: lane (row i = lane & 31, half = lane >> 5) of row tile t holds k = 16 s + 8 half + 0..7 of row 32 t + i; rows past M are
+// zero.  One thread per (tile, K-step, lane).  The weights of di2p_point_head_x3 ([K-step][tile]) and di2p_point_head_labels_x3 ([tile][K-step]).
+__global__ __launch_bounds__(256) void pack_a32_kernel(const float* __restrict__ Wt, unsigned short* __restrict__ Wp, int K, int M, int tiles,
+                                                       int tile_stride, int step_stride) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int ks = K / 16;
+    if (t >= (long long)tiles * ks * 64) return;
+    const int lane = (int)(t & 63), s = (int)((t >> 6) % ks), tile = (int)((t >> 6) / ks);
     const int row = 32 * tile + (lane & 31), k0 = 16 * s + 8 * (lane >> 5);
+    unsigned short* d = Wp + (((long long)tile * tile_stride + (long long)s * step_stride) * 3 * 64 + lane) * 8;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-        const float v = Wt[(long long)(k0 + e) * HX_M + row];
-        const float a1 = hx_hi16(v), r1 = v - a1, a2 = hx_hi16(r1), r2 = r1 - a2;
-        const float pl[3] = {a1, a2, r2};
+        const float v = row < M ? Wt[(long long)(k0 + e) * M + row] : 0.0f;
+        float pl[3];
+        bf16x3::split(v, pl[0], pl[1], pl[2]);
 #pragma unroll
-        for (int p = 0; p < 3; ++p)
-            Wp[((((long long)s * HX_TM + tile) * 3 + p) * 64 + lane) * 8 + e] = (unsigned short)(__builtin_bit_cast(unsigned, pl[p]) >> 16);
+        for (int p = 0; p < 3; ++p) d[p * 64 * 8 + e] = bf16x3::bits(pl[p]);
     }
 }
 
 }  // namespace
+
+void di2p_pack_a32(const float* Wt, int K, int M, int tiles, int tile_stride, int step_stride, void* Wp, void* stream) {
+    hipLaunchKernelGGL(pack_a32_kernel, dim3(di2p_cdiv((long long)tiles * (K / 16) * 64, 256)), dim3(256), 0, (hipStream_t)stream, Wt,
+                       (unsigned short*)Wp, K, M, tiles, tile_stride, step_stride);
+}
 
 extern "C" long long di2p_head_x3_packed_bytes(int K) { return K >= 16 && K % 16 == 0 ? (long long)(K / 16) * HX_TM * 3 * 1024 : 0; }
 
@@ -360,8 +352,7 @@ extern "C" long long di2p_head_x3_packed_bytes(int K) { return K >= 16 && K % 16
 extern "C" int di2p_head_x3_pack(const float* Wt, int K, void* Wp, void* stream) {
     DI2P_CHECK_ARG(Wt && Wp && K >= 16 && K % 16 == 0, "needs K % 16 == 0 (and 128 output channels)");
     DI2P_CHECK_ARG(((uintptr_t)Wp & 15) == 0, "packed weights must be 16-byte aligned");
-    hipLaunchKernelGGL(head_x3_pack_kernel, dim3(di2p_cdiv((long long)(K / 16) * HX_TM * 64, 256)), dim3(256), 0, (hipStream_t)stream, Wt,
-                       (unsigned short*)Wp, K);
+    di2p_pack_a32(Wt, K, HX_M, HX_TM, 1, HX_TM, Wp, stream);
     DI2P_RETURN_LAUNCH();
 }
 

@@ -3,7 +3,7 @@
 // gemm.hip ("bf16x3": six bf16 products per fp32 product, fp32 accumulation).  The 64 x OH x OW activation between the convolution and the
 // pool (168 MB per 32-frame step at 160 x 512: written by stem.hip, read back by the pool kernel) never leaves the compute unit.
 //
-//   K layout: k = ((ci, ky) pair, kx padded 7 -> 8 with a zero weight): 21 pairs; one K-step of v_mfma_f32_32x32x16_bf16 is two pairs (the lane's
+//   K layout: k = ((ci, ky) pair, kx padded 7 -> 8 with a zero weight): 21 pairs; one K-step of the 32 x 32 x 16 bf16 MFMA is two pairs (the lane's
 //            k-group = lane / 32 picks the pair), 11 K-steps (the 22nd pair has zero weights).  A lane's eight consecutive k of a B fragment
 //            are then eight CONSECUTIVE input columns 2 ox - 3 ... 2 ox + 4 of one input row and channel: with the input rows kept in LDS as
 //            three bf16 planes, left-padded by 3, a B fragment is 16 bytes at byte offset 4 ox of a row -- no im2col, no parity split.
@@ -20,23 +20,18 @@
 //            instructions of row cr + 1; two barriers per row (tile free / tile and ring complete).
 #include <stdint.h>
 
+#include "bf16x3.h"
 #include "common.h"
 
 namespace {
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using bf16x3::u32x4_t;
+using bf16x3::u32x2_t;
+using bf16x3::f32x16;
 
 constexpr int SX_CO = 64, SX_PAIRS = 21, SX_KSTEPS = 11, SX_RING = 9, SX_ITEMS = 4;
 constexpr int SX_WP_BYTES = SX_KSTEPS * 2 * 3 * 64 * 16;
 constexpr int SX_OOB = 0x40000000;
-
-__device__ __forceinline__ float sx_hi16(float x) { return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, x) & 0xffff0000u); }
-__device__ __forceinline__ unsigned sx_pack_hi(float x0, float x1) {      // bf16(x0) in the low half, bf16(x1) in the high half (truncation)
-    return __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, x1), __builtin_bit_cast(unsigned, x0), 0x07060302u);
-}
 
 struct SxArgs {
     const float* x; const u32x4_t* Wp; const float* scale; const float* shift; float* y;
@@ -52,17 +47,18 @@ __global__ __launch_bounds__(256) void stem_x3_pack_kernel(const float* __restri
     if (t >= SX_KSTEPS * 2 * 64) return;
     const int lane = t & 63, mt = (t >> 6) & 1, s = t >> 7;
     const int c = mt * 32 + (lane & 31), p = 2 * s + (lane >> 5);
+    // bf16x3::split8 written out, fused with the loads (through split8 the compiler allocates registers differently)
     float f[8], r[8], q[8];
 #pragma unroll
     for (int kx = 0; kx < 8; ++kx) {
         f[kx] = (p < SX_PAIRS && kx < 7) ? w[(c * SX_PAIRS + p) * 7 + kx] : 0.0f;
-        r[kx] = f[kx] - sx_hi16(f[kx]);
-        q[kx] = r[kx] - sx_hi16(r[kx]);
+        r[kx] = f[kx] - bf16x3::hi16(f[kx]);
+        q[kx] = r[kx] - bf16x3::hi16(r[kx]);
     }
     u32x4_t* d = Wp + (long long)(s * 2 + mt) * 3 * 64 + lane;
-    d[0] = u32x4_t{sx_pack_hi(f[0], f[1]), sx_pack_hi(f[2], f[3]), sx_pack_hi(f[4], f[5]), sx_pack_hi(f[6], f[7])};
-    d[64] = u32x4_t{sx_pack_hi(r[0], r[1]), sx_pack_hi(r[2], r[3]), sx_pack_hi(r[4], r[5]), sx_pack_hi(r[6], r[7])};
-    d[128] = u32x4_t{sx_pack_hi(q[0], q[1]), sx_pack_hi(q[2], q[3]), sx_pack_hi(q[4], q[5]), sx_pack_hi(q[6], q[7])};
+    d[0] = u32x4_t{bf16x3::pack_hi(f[0], f[1]), bf16x3::pack_hi(f[2], f[3]), bf16x3::pack_hi(f[4], f[5]), bf16x3::pack_hi(f[6], f[7])};
+    d[64] = u32x4_t{bf16x3::pack_hi(r[0], r[1]), bf16x3::pack_hi(r[2], r[3]), bf16x3::pack_hi(r[4], r[5]), bf16x3::pack_hi(r[6], r[7])};
+    d[128] = u32x4_t{bf16x3::pack_hi(q[0], q[1]), bf16x3::pack_hi(q[2], q[3]), bf16x3::pack_hi(q[4], q[5]), bf16x3::pack_hi(q[6], q[7])};
 }
 
 __global__ __launch_bounds__(256, 1) void stem_x3_kernel(const SxArgs a) {
@@ -117,15 +113,16 @@ __global__ __launch_bounds__(256, 1) void stem_x3_kernel(const SxArgs a) {
         const int s0 = (irow_new + 18) % SX_RING, s1 = (irow_new + 19) % SX_RING;
 #pragma unroll
         for (int it = 0; it < SX_ITEMS; ++it) {
+            // bf16x3::split4 written out (its order of the eight subtractions schedules this loop differently)
             const float* f = raw[it];
             float r[4], q[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) { r[e] = f[e] - sx_hi16(f[e]); q[e] = r[e] - sx_hi16(r[e]); }
+            for (int e = 0; e < 4; ++e) { r[e] = f[e] - bf16x3::hi16(f[e]); q[e] = r[e] - bf16x3::hi16(r[e]); }
             const int off = st_ok[it] ? (st_rr[it] ? s1 : s0) * slotb + st_l[it] : dump;
             const int pl = st_ok[it] ? rowb : 0;
-            *reinterpret_cast<u32x2_t*>(smem + off) = u32x2_t{sx_pack_hi(f[0], f[1]), sx_pack_hi(f[2], f[3])};
-            *reinterpret_cast<u32x2_t*>(smem + off + pl) = u32x2_t{sx_pack_hi(r[0], r[1]), sx_pack_hi(r[2], r[3])};
-            *reinterpret_cast<u32x2_t*>(smem + off + 2 * pl) = u32x2_t{sx_pack_hi(q[0], q[1]), sx_pack_hi(q[2], q[3])};
+            *reinterpret_cast<u32x2_t*>(smem + off) = u32x2_t{bf16x3::pack_hi(f[0], f[1]), bf16x3::pack_hi(f[2], f[3])};
+            *reinterpret_cast<u32x2_t*>(smem + off + pl) = u32x2_t{bf16x3::pack_hi(r[0], r[1]), bf16x3::pack_hi(r[2], r[3])};
+            *reinterpret_cast<u32x2_t*>(smem + off + 2 * pl) = u32x2_t{bf16x3::pack_hi(q[0], q[1]), bf16x3::pack_hi(q[2], q[3])};
         }
     };
 
@@ -232,8 +229,7 @@ __global__ __launch_bounds__(256, 1) void stem_x3_kernel(const SxArgs a) {
         auto mma = [&](int slot, int set) __attribute__((always_inline)) {
 #define DI2P_SX_PROD(QA, QB)                                                                                                            \
     _Pragma("unroll") for (int mt = 0; mt < 2; ++mt) _Pragma("unroll") for (int j = 0; j < 2; ++j)                                      \
-        acc[mt][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, af[slot][mt][QA]),                            \
-                                                             __builtin_bit_cast(bf16x8_t, bf[set][j][QB]), acc[mt][j], 0, 0, 0);
+        acc[mt][j] = bf16x3::mma(af[slot][mt][QA], bf[set][j][QB], acc[mt][j]);
             DI2P_SX_PROD(2, 0) DI2P_SX_PROD(1, 1) DI2P_SX_PROD(0, 2) DI2P_SX_PROD(1, 0) DI2P_SX_PROD(0, 1) DI2P_SX_PROD(0, 0)
 #undef DI2P_SX_PROD
         };

@@ -594,17 +594,18 @@ def conv2d(x, Wt, scale, shift, KH, KW, stride, pad, relu, residual=None, tap_ma
     return y
 
 
-def conv3x3_x3_supported(x_shape, Cout, stride):
-    """True if di2p_conv3x3_x3 has a kernel instance for this layer shape (x_shape = (B, Cin, H, W))."""
+def conv3x3_x3_supported(x_shape, Cout, stride, cfg=-1):
+    """True if di2p_conv3x3_x3 has a kernel instance for this layer shape (x_shape = (B, Cin, H, W)) in tile configuration cfg (0..3;
+    -1: the knob conv_x3_cfg, by default the cheapest)."""
     B, Cin, H, W = (int(v) for v in x_shape)
-    return bool(_lib.load().di2p_conv3x3_x3_supported(B, Cin, H, W, int(Cout), int(stride)))
+    return bool(_lib.load().di2p_conv3x3_x3_supported(B, Cin, H, W, int(Cout), int(stride), int(cfg)))
 
 
-def conv3x3_x3(x, Wp, Cout, scale, shift, stride, relu, residual=None, downsample=None):
+def conv3x3_x3(x, Wp, Cout, scale, shift, stride, relu, residual=None, downsample=None, cfg=-1):
     """3x3 / pad 1 convolution on the bf16 matrix instructions with exact three-way fp32 splits (di2p_conv3x3_x3):
     y = relu?(scale * conv(x) + shift + residual).  Wp = bf16x3_pack(tap-major Wt[9 Cin, Cout]).  stride 2 takes
     downsample = (Wp_ds, scale_ds, shift_ds) -- the BasicBlock's 1x1 / stride-2 branch of the same input (resnet.py:160-164) -- and
-    returns (y, y_ds)."""
+    returns (y, y_ds).  cfg: the tile configuration, as for conv3x3_x3_supported."""
     require_cuda(x, Wp, scale, shift, residual)
     _chk(x, _f32, "conv3x3_x3 input")
     if x.dim() != 4:
@@ -637,7 +638,7 @@ def conv3x3_x3(x, Wp, Cout, scale, shift, stride, relu, residual=None, downsampl
     if _lib.WORK is not None:
         _lib.WORK["di2p_conv3x3_x3"] = _lib.WORK.get("di2p_conv3x3_x3", 0) + B * Cout * Cin * (9 + (1 if downsample is not None else 0)) * OH * OW
     call("di2p_conv3x3_x3", ptr(x), ptr(Wp), ptr(scale), ptr(shift), ptr(residual), ptr(y), B, Cin, H, W, Cout, int(stride), int(bool(relu)),
-         ptr(Wd), ptr(sd), ptr(hd), ptr(yd), stream())
+         ptr(Wd), ptr(sd), ptr(hd), ptr(yd), int(cfg), stream())
     return (y, yd) if downsample is not None else y
 
 

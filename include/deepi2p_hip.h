@@ -264,12 +264,14 @@ int di2p_point_head_labels_x3(const di2p_head_labels_x3_t* h, int B, int N, void
  *   Wp    = di2p_bf16x3_pack of the tap-major matrix Wt[(kh*3+kw)*Cin + ci][Cout] (K = 9 Cin, M = Cout);
  *   Wp_ds = di2p_bf16x3_pack of Wt_ds[Cin][Cout] (stride 2: required; stride 1: must be NULL);
  *   y     f32[B,Cout,OH,OW] = relu?(scale * conv3x3(x f32[B,Cin,H,W]) + shift + residual);  y_ds = scale_ds * conv1x1/s2(x) + shift_ds.
- * di2p_conv3x3_x3_supported: 1 if a kernel instance exists for the shape (OW % 32 == 0 and Cin % 16 == 0, or OW % 16 == 0 and
- * Cin % 32 == 0; the input patch of a tile must fit the LDS), else 0 -- the caller then uses di2p_conv3x3_winograd / di2p_conv2d. */
-int di2p_conv3x3_x3_supported(int B, int Cin, int H, int W, int Cout, int stride);
+ *   cfg   = the tile configuration: 0..3 forces one, -1 takes the knob "conv_x3_cfg" (whose default -1 is the cheapest by a cost model).
+ * di2p_conv3x3_x3_supported: 1 if a kernel instance of configuration cfg exists for the shape (OW % 32 == 0 and Cin % 16 == 0, or
+ * OW % 16 == 0 and Cin % 32 == 0; the input patch of a tile must fit the LDS), else 0 -- the caller then uses di2p_conv3x3_winograd /
+ * di2p_conv2d.  (ABI 8: cfg added to both.) */
+int di2p_conv3x3_x3_supported(int B, int Cin, int H, int W, int Cout, int stride, int cfg);
 int di2p_conv3x3_x3(const float* x, const void* Wp, const float* scale, const float* shift, const float* residual, float* y, int B,
                     int Cin, int H, int W, int Cout, int stride, int relu, const void* Wp_ds, const float* scale_ds,
-                    const float* shift_ds, float* y_ds, void* stream);
+                    const float* shift_ds, float* y_ds, int cfg, void* stream);
 /* The ResNet stem (7x7 / stride 2 / pad 3, 3 -> 64 channels, models/resnet.py:137-139,197-199) as a direct kernel: the filter bank and
  * the input row segments of a workgroup are staged once (columns de-interleaved by parity), then 168 MFMAs per wave without a barrier.
  *   di2p_stem_pack: weight f32[64,3,7,7] -> Wp f32[168,64] (taps padded 7 -> 8 per row), once per checkpoint load.

@@ -45,8 +45,9 @@ def test_argument_errors_are_reported_not_crashed():
     _lib.call("di2p_index_max_forward", None, None, None, 0, 4, 10, 8, None, None)
 
 
-def test_host_side_shape_queries_of_the_bf16x3_entry_points():
-    """Pure host logic behind the C ABI (no device needed): which shapes the round-5 kernels take, and the sizes of their packed operands."""
+def test_host_side_shape_queries_of_the_bf16x3_entry_points_with_cfg():
+    """Pure host logic behind the C ABI (no device needed): which shapes the round-5 kernels take, and the sizes of their packed operands.
+    ABI 8: di2p_conv3x3_x3_supported takes the tile configuration (-1: the knob conv_x3_cfg, by default the cost model's choice)."""
     from deepi2p_amd import _lib
     lib = _lib.load()
     # stem + pool in one launch: H % 4 == 0, W % 128 == 0, W <= 512 (include/deepi2p_hip.h)
@@ -60,9 +61,13 @@ def test_host_side_shape_queries_of_the_bf16x3_entry_points():
     # the seven 3x3 layer shapes of ResNet-34 at 160 x 512 have a bf16x3 instance; odd sizes under stride 2 and Cin < 16 do not
     for Cin, H, W, Cout, s in ((64, 40, 128, 64, 1), (128, 20, 64, 128, 1), (256, 10, 32, 256, 1), (512, 5, 16, 512, 1),
                                (64, 40, 128, 128, 2), (128, 20, 64, 256, 2), (256, 10, 32, 512, 2)):
-        assert lib.di2p_conv3x3_x3_supported(32, Cin, H, W, Cout, s) == 1, (Cin, H, W, Cout, s)
-    assert lib.di2p_conv3x3_x3_supported(32, 64, 41, 128, 128, 2) == 0 and lib.di2p_conv3x3_x3_supported(32, 8, 40, 128, 64, 1) == 0
-    assert lib.di2p_conv3x3_x3_supported(1, 64, 40, 128, 64, 1) == lib.di2p_conv3x3_x3_supported(64, 64, 40, 128, 64, 1) == 1     # batch independent
+        assert lib.di2p_conv3x3_x3_supported(32, Cin, H, W, Cout, s, -1) == 1, (Cin, H, W, Cout, s)
+    assert lib.di2p_conv3x3_x3_supported(32, 64, 41, 128, 128, 2, -1) == 0 and lib.di2p_conv3x3_x3_supported(32, 8, 40, 128, 64, 1, -1) == 0
+    assert lib.di2p_conv3x3_x3_supported(1, 64, 40, 128, 64, 1, -1) == lib.di2p_conv3x3_x3_supported(64, 64, 40, 128, 64, 1, -1) == 1     # batch independent
+    # a forced configuration answers for itself: 0 and 1 tile 32-pixel segments (OW = 16 does not divide), 2 and 3 16-pixel ones
+    assert lib.di2p_conv3x3_x3_supported(32, 512, 5, 16, 512, 1, 0) == lib.di2p_conv3x3_x3_supported(32, 512, 5, 16, 512, 1, 1) == 0
+    assert lib.di2p_conv3x3_x3_supported(32, 512, 5, 16, 512, 1, 2) == lib.di2p_conv3x3_x3_supported(32, 512, 5, 16, 512, 1, 3) == 1
+    assert lib.di2p_conv3x3_x3_supported(32, 64, 40, 128, 64, 1, 4) == lib.di2p_conv3x3_x3_supported(32, 64, 40, 128, 64, 1, -2) == 0
 
 
 def test_no_cpu_fallback_paths():

@@ -28,6 +28,33 @@ def _packed(d):
             "sc1": d["sc1"], "sh1": d["sh1"], "relu1": True, "sc2": None, "sh2": d["sh2"]}
 
 
+def _pack_model(Wt, tile_major):
+    """NumPy model of the 32-row A-fragment order of both head packers: the bf16x3 split by masking to the upper 16 bits, rows past M zero;
+    entry (row tile t, K-step s) = [3 planes][64 lanes][8], lane i + 32 half holds k = 16 s + 8 half + 0..7 of row 32 t + i; entries
+    [tile][K-step] (di2p_head_labels_x3_pack) or [K-step][tile] (di2p_head_x3_pack)."""
+    K, M = Wt.shape
+    T = -(-M // 32)
+    W = np.zeros((K, 32 * T), np.float32)
+    W[:, :M] = Wt
+    p0 = W.view(np.uint32) & 0xFFFF0000
+    r = W - p0.view(np.float32)
+    p1 = r.view(np.uint32) & 0xFFFF0000
+    p2 = (r - p1.view(np.float32)).view(np.uint32)
+    planes = (np.stack([p0, p1, p2]) >> 16).astype(np.uint16).reshape(3, K // 16, 2, 8, T, 32)      # [plane][s][half][e][t][i]
+    return np.ascontiguousarray(planes.transpose((4, 1, 0, 2, 5, 3) if tile_major else (1, 4, 0, 2, 5, 3))).tobytes()
+
+
+@pytest.mark.parametrize("which,K,M", [("head_x3", 96, 128), ("head_x3", 128, 128), ("labels", 256, 82), ("labels", 256, 256),
+                                       ("labels", 256, 1402)])
+def test_head_packers_match_the_documented_layout(dev, which, K, M):
+    """di2p_head_x3_pack and di2p_head_labels_x3_pack write the 32-row A-fragment order of the split weights, byte for byte."""
+    from deepi2p_amd import ops
+    Wt = torch.randn(K, M, generator=torch.Generator().manual_seed(K + M)) * 3
+    pack = ops.head_x3_pack if which == "head_x3" else ops.head_labels_pack
+    got = pack(Wt.to(dev).contiguous()).cpu().numpy().tobytes()
+    assert got == _pack_model(Wt.numpy(), tile_major=which == "labels")
+
+
 def _run(d, packed, with_scores=True):
     from deepi2p_amd import ops
     B, _, N = d["y0"].shape
