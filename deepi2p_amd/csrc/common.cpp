@@ -64,6 +64,14 @@ int di2p_cu_count() {
     return n;
 }
 
+int di2p_allow_dynamic_lds(const void* kernel, size_t bytes, const char* who) {
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess) return 0;
+    di2p_set_error("%s: %zu bytes of dynamic LDS refused: %s", who, bytes, hipGetErrorString(e));
+    (void)hipGetLastError();
+    return -1;
+}
+
 long long di2p_opt(int id) {
     std::call_once(g_opt_once, opts_init);
     return g_opt[id];

@@ -74,6 +74,9 @@ enum Di2pOption {
 };
 long long di2p_opt(int id);
 int di2p_cu_count();      // compute units of the current device (cached per device)
+// The opt-in a kernel needs for more than 64 KB of dynamic LDS (per device and cheap: made before every such launch, never cached).
+// Refused: sets "<who>: <bytes> bytes of dynamic LDS refused: <hip error>", clears the sticky error and returns non-zero.
+int di2p_allow_dynamic_lds(const void* kernel, size_t bytes, const char* who);
 // (head_x3.hip) the bf16x3 split of Wt f32[K][M] (K % 16 == 0) in the A-fragment order of 32-row tiles, rows past M zero: the 3 KB entry of
 // (row tile t, K-step s) at t * tile_stride + s * step_stride; launch only
 void di2p_pack_a32(const float* Wt, int K, int M, int tiles, int tile_stride, int step_stride, void* Wp, void* stream);

@@ -392,10 +392,11 @@ CxPlan cx_plan(int ci, int B, int Cin, int H, int W, int Cout, int stride) {
 }
 
 template <int MF, int TM, int TN, int WM, int WN, int STRIDE, bool DS, bool DBUF, int ITEMS, int PWT, bool SA>
-void cx_launch_one(const CxArgs& a, int grid, size_t lds, hipStream_t st) {
+int cx_launch_one(const CxArgs& a, int grid, size_t lds, hipStream_t st) {
     auto k = conv3x3_x3_kernel<MF, TM, TN, WM, WN, STRIDE, DS, DBUF, ITEMS, PWT, SA>;
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (di2p_allow_dynamic_lds((const void*)k, lds, "di2p_conv3x3_x3")) return -1;
     hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, st, a);
+    return 0;
 }
 
 // The instantiated kernels.  Each row: configuration, stride, double-buffered patch, ITEMS, PWT (0 = any patch row length; a plan that
@@ -424,16 +425,14 @@ int cx_find_instance(int cfg, int stride, int dbuf, int need, int pw) {
     return best;
 }
 
-bool cx_launch(int inst, const CxPlan& p, const CxArgs& a, int grid, hipStream_t st) {
+// 0: launched; 1: no kernel instance; -1: LDS opt-in refused (error set)
+int cx_launch(int inst, const CxPlan& p, const CxArgs& a, int grid, hipStream_t st) {
     int i = 0;
 #define DI2P_CX_CASE(CFG, MF, TM, TN, WM, WN, STRIDE, DBUF, ITEMS, PWT)                                                                \
-    if (inst == i++) {                                                                                                                 \
-        cx_launch_one<MF, TM, TN, WM, WN, STRIDE, STRIDE == 2, DBUF != 0, ITEMS, PWT, true>(a, grid, (size_t)p.lds, st);              \
-        return true;                                                                                                                    \
-    }
+    if (inst == i++) return cx_launch_one<MF, TM, TN, WM, WN, STRIDE, STRIDE == 2, DBUF != 0, ITEMS, PWT, true>(a, grid, (size_t)p.lds, st);
     DI2P_CX_INSTANCES(DI2P_CX_CASE)
 #undef DI2P_CX_CASE
-    return false;
+    return 1;
 }
 
 // the cheapest runnable plan of a layer (cfg = -1: none); `force` >= 0 restricts it to one configuration
@@ -510,7 +509,8 @@ extern "C" int di2p_conv3x3_x3(const float* x, const void* Wp, const float* scal
     const long long grid = (long long)B * best.tiles_per_frame * best.n_mt;
     DI2P_CHECK_ARG(cx_size_limit(B, Cin, H, W, Cout, &best) == nullptr, "too many workgroups");
     hipStream_t st = (hipStream_t)stream;
-    const bool ok = cx_launch(inst, best, a, (int)grid, st);
-    DI2P_CHECK_ARG(ok, "internal: no kernel instance for the plan");
+    const int rc = cx_launch(inst, best, a, (int)grid, st);
+    if (rc < 0) return -1;
+    DI2P_CHECK_ARG(rc == 0, "internal: no kernel instance for the plan");
     DI2P_RETURN_LAUNCH();
 }

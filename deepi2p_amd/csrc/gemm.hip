@@ -930,6 +930,111 @@ void launch_pw_vec(bool dense, const SrcDev& s, const float* Wt, float* Y, int B
 // Workgroup 128 x 128, 4 waves of 64 x 64 (2 x 2 MFMA tiles), K-step 32, 48 KB of LDS, two workgroups per CU.
 constexpr int X3_BM = 128, X3_BN = 128, X3_BK = 32, X3_KG = X3_BK / 8;
 
+// ---- what the three bf16x3 pointwise kernels share: one K loop.  They differ only in how a K-step's operands reach LDS / registers (their
+// gload / sstore, and for the 256-row kernel where the A fragments are read from).
+
+__device__ __forceinline__ void x3_clear(f32x16 (&acc)[2][2]) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+}
+
+// A fragments straight from memory: [Kp/8][Mp][3] x 16 bytes; kg = the lane's k-group (k-group of the sub-step + half), row = its row of tile 0
+__device__ __forceinline__ void x3_aload(const u32x4_t* __restrict__ Wp, int Mp, int kg, int row, u32x4_t (&af)[2][3]) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const u32x4_t* p = Wp + ((long long)kg * Mp + row + i * 32) * 3;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) af[i][q] = p[q];
+    }
+}
+
+// B fragments of the k16 sub-step `sub` from one staged K-step, bq = [plane][k-group of 8][k-half][column] x 8 bytes; n = the lane's column of tile 0
+__device__ __forceinline__ void x3_bfrag(const u32x2_t* bq, int sub, int half, int n, u32x4_t (&bf)[2][3]) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const u32x2_t* r = bq + ((q * X3_KG + 2 * sub + half) * 2) * X3_BN + n + j * 32;
+            const u32x2_t lo = r[0], hi = r[X3_BN];
+            bf[j][q] = u32x4_t{lo.x, lo.y, hi.x, hi.y};
+        }
+}
+
+// the six products of a k16 sub-step on the 2 x 2 tiles: smallest terms first; four independent accumulators between two matrix
+// instructions of one chain
+__device__ __forceinline__ void x3_products(f32x16 (&acc)[2][2], const u32x4_t (&af)[2][3], const u32x4_t (&bf)[2][3]) {
+    constexpr int QA[6] = {2, 1, 0, 1, 0, 0}, QB[6] = {0, 1, 2, 0, 1, 0};
+    DI2P_MFMA_BEGIN();
+#pragma unroll
+    for (int p = 0; p < 6; ++p)
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) acc[i][j] = bf16x3::mma(af[i][QA[p]], bf[j][QB[p]], acc[i][j]);
+    DI2P_MFMA_END();
+}
+
+// The double-buffered K loop over T K-steps of two k16 sub-steps: gload(t) requests K-step t's operands into registers, sstore(buf) puts them
+// into LDS buffer buf, substep(buf, sub, next_kg, has_next) multiplies (and first requests the A fragments of the NEXT sub-step, k-group
+// next_kg, where the kernel reads them from memory: prefetch0 requests those of the first).
+template <class GLoad, class SStore, class Prefetch0, class Substep>
+__device__ __forceinline__ void x3_k_loop(int T, GLoad gload, SStore sstore, Prefetch0 prefetch0, Substep substep) {
+    gload(0);
+    sstore(0);
+    prefetch0();
+    __syncthreads();
+    // steady state without branches (a branch arm without loads turns every wait of the other arm into vmcnt(0))
+    for (int t = 0; t + 1 < T; ++t) {
+        const int buf = t & 1;
+        gload(t + 1);
+        substep(buf, 0, t * X3_KG + 2, true);
+        substep(buf, 1, t * X3_KG + 4, true);
+        sstore(buf ^ 1);
+        __syncthreads();
+    }
+    substep((T - 1) & 1, 0, (T - 1) * X3_KG + 2, true);
+    substep((T - 1) & 1, 1, 0, false);
+}
+
+// Every tile's operand loads (gathered rows, scale, shift: 16 bytes each) and arithmetic first, then every tile's stores: loads that follow
+// a store to memory the compiler cannot tell apart are not moved above it -- tile by tile, each tile's round trips came one after the other
+template <bool PLANES>
+__device__ __forceinline__ void x3_epilogue_tiles(const EpiDev& epi, float* Y, int b, int M, int N, int m_blk, int n_blk, int wm, int wn,
+                                                  const f32x16 (&acc)[2][2]) {
+    const int l31 = threadIdx.x & 31, half = (threadIdx.x >> 5) & 1;
+    EpiPointwiseT<-1, -1, PLANES> ep{epi, Y, b, M, N};
+    float v[2][2][16];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            ep.template apply_pre<true>(m_blk + wm * 64 + i * 32 + 4 * half, min(n_blk + wn * 64 + j * 32 + l31, N - 1), acc[i][j], nullptr, v[i][j]);
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) ep.store(m_blk + wm * 64 + i * 32 + 4 * half, n_blk + wn * 64 + j * 32 + l31, v[i][j]);
+}
+
+// The K loop of the two 128-row kernels: A fragments from memory in two register stages (row = the lane's row of tile 0), B fragments from
+// the staged K-steps Bs[buffer] (n = the lane's column of tile 0)
+template <class GLoad, class SStore>
+__device__ __forceinline__ void x3_k_loop_amem(int T, const u32x4_t* __restrict__ Wp, int Mp, int row, int half, const u32x2_t (&Bs)[2][3][X3_KG][2][X3_BN],
+                                               int n, GLoad gload, SStore sstore, f32x16 (&acc)[2][2]) {
+    u32x4_t af[2][2][3];                                     // [stage][tile i][plane]
+    x3_k_loop(T, gload, sstore, [&] { x3_aload(Wp, Mp, half, row, af[0]); },
+              // one k16 sub-step: B fragments from LDS, the A fragments of the NEXT sub-step requested first
+              [&](int buf, int sub, int next_kg, bool has_next) __attribute__((always_inline)) {
+                  if (has_next) x3_aload(Wp, Mp, next_kg + half, row, af[sub ^ 1]);
+                  u32x4_t bf[2][3];
+                  x3_bfrag(&Bs[buf][0][0][0][0], sub, half, n, bf);
+                  x3_products(acc, af[sub], bf);
+              });
+}
+
 template <bool DENSE, bool PLANES = false>
 __global__ __launch_bounds__(256, 2) void pointwise_gemm_x3_kernel(SrcDev srcs, const u32x4_t* __restrict__ Wp, float* __restrict__ Y, int M, int K,
                                                                     int N, int Mp, EpiDev epi) {
@@ -963,74 +1068,10 @@ __global__ __launch_bounds__(256, 2) void pointwise_gemm_x3_kernel(SrcDev srcs, 
         d2[0] = u32x4_t{p2[0].x, p2[0].y, p2[1].x, p2[1].y}; d2[1] = u32x4_t{p2[2].x, p2[2].y, p2[3].x, p2[3].y};
         d3[0] = u32x4_t{p3[0].x, p3[0].y, p3[1].x, p3[1].y}; d3[1] = u32x4_t{p3[2].x, p3[2].y, p3[3].x, p3[3].y};
     };
-    // A fragments straight from memory: [Kp/8][Mp][3] x 16 bytes; lane = row (l31), k-group (half)
-    u32x4_t af[2][2][3];                                     // [stage][tile i][plane]
-    auto aload = [&](int kg_global, int stg) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const u32x4_t* p = Wp + ((long long)(kg_global + half) * Mp + m_blk + wm * 64 + i * 32 + l31) * 3;
-#pragma unroll
-            for (int q = 0; q < 3; ++q) af[stg][i][q] = p[q];
-        }
-    };
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-    // one k16 sub-step: B fragments from LDS, the A fragments of the NEXT sub-step requested first
-    auto substep = [&](int buf, int sub, int next_kg, bool has_next) __attribute__((always_inline)) {
-        if (has_next) aload(next_kg, sub ^ 1);
-        u32x4_t bf[2][3];
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                const int n = wn * 64 + j * 32 + l31;
-                const u32x2_t lo = Bs[buf][q][2 * sub + half][0][n], hi = Bs[buf][q][2 * sub + half][1][n];
-                bf[j][q] = u32x4_t{lo.x, lo.y, hi.x, hi.y};
-            }
-        DI2P_MFMA_BEGIN();
-        // smallest terms first; four independent accumulators between two matrix instructions of one chain
-#define DI2P_X3_PROD(QA, QB)                                                                                                          \
-    _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int j = 0; j < 2; ++j)                                      \
-        acc[i][j] = bf16x3::mma(af[sub][i][QA], bf[j][QB], acc[i][j]);
-        DI2P_X3_PROD(2, 0) DI2P_X3_PROD(1, 1) DI2P_X3_PROD(0, 2)
-        DI2P_X3_PROD(1, 0) DI2P_X3_PROD(0, 1)
-        DI2P_X3_PROD(0, 0)
-#undef DI2P_X3_PROD
-        DI2P_MFMA_END();
-    };
-    gload(0);
-    sstore(0);
-    aload(0, 0);
-    __syncthreads();
-    // steady state without branches (a branch arm without loads turns every wait of the other arm into vmcnt(0))
-    for (int t = 0; t + 1 < T; ++t) {
-        const int buf = t & 1;
-        gload(t + 1);
-        substep(buf, 0, t * X3_KG + 2, true);
-        substep(buf, 1, t * X3_KG + 4, true);
-        sstore(buf ^ 1);
-        __syncthreads();
-    }
-    substep((T - 1) & 1, 0, (T - 1) * X3_KG + 2, true);
-    substep((T - 1) & 1, 1, 0, false);
-    // every tile's operand loads (gathered rows, scale, shift: 16 bytes each) and arithmetic first, then every tile's stores: loads that follow
-    // a store to memory the compiler cannot tell apart are not moved above it -- tile by tile, each tile's round trips came one after the other
-    EpiPointwiseT<-1, -1, PLANES> ep{epi, Y, b, M, N};
-    float v[2][2][16];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-            ep.template apply_pre<true>(m_blk + wm * 64 + i * 32 + 4 * half, min(n_blk + wn * 64 + j * 32 + l31, N - 1), acc[i][j], nullptr, v[i][j]);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) ep.store(m_blk + wm * 64 + i * 32 + 4 * half, n_blk + wn * 64 + j * 32 + l31, v[i][j]);
+    x3_clear(acc);
+    x3_k_loop_amem(T, Wp, Mp, m_blk + wm * 64 + l31, half, Bs, wn * 64 + l31, gload, sstore, acc);
+    x3_epilogue_tiles<PLANES>(epi, Y, b, M, N, m_blk, n_blk, wm, wn, acc);
 }
 
 // The same contraction with the activations given ALREADY SPLIT: three bf16 planes [B][3][K/4][N] x 8 bytes (4 consecutive k of one column),
@@ -1074,70 +1115,10 @@ __global__ __launch_bounds__(256, 2) void pointwise_gemm_x3p_kernel(const u32x4_
 #pragma unroll
         for (int i = 0; i < 6; ++i) d[i * 64] = st[i];
     };
-    u32x4_t af[2][2][3];                                     // [stage][tile i][plane]
-    auto aload = [&](int kg_global, int stg) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const u32x4_t* p = Wp + ((long long)(kg_global + half) * Mp + m_blk + wm * 64 + i * 32 + l31) * 3;
-#pragma unroll
-            for (int q = 0; q < 3; ++q) af[stg][i][q] = p[q];
-        }
-    };
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-    auto substep = [&](int buf, int sub, int next_kg, bool has_next) __attribute__((always_inline)) {
-        if (has_next) aload(next_kg, sub ^ 1);
-        u32x4_t bf[2][3];
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                const int n = wn * 64 + j * 32 + l31;
-                const u32x2_t lo = Bs[buf][q][2 * sub + half][0][n], hi = Bs[buf][q][2 * sub + half][1][n];
-                bf[j][q] = u32x4_t{lo.x, lo.y, hi.x, hi.y};
-            }
-        DI2P_MFMA_BEGIN();
-#define DI2P_X3_PROD(QA, QB)                                                                                                          \
-    _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int j = 0; j < 2; ++j)                                      \
-        acc[i][j] = bf16x3::mma(af[sub][i][QA], bf[j][QB], acc[i][j]);
-        DI2P_X3_PROD(2, 0) DI2P_X3_PROD(1, 1) DI2P_X3_PROD(0, 2)
-        DI2P_X3_PROD(1, 0) DI2P_X3_PROD(0, 1)
-        DI2P_X3_PROD(0, 0)
-#undef DI2P_X3_PROD
-        DI2P_MFMA_END();
-    };
-    gload(0);
-    sstore(0);
-    aload(0, 0);
-    __syncthreads();
-    for (int t = 0; t + 1 < T; ++t) {
-        const int buf = t & 1;
-        gload(t + 1);
-        substep(buf, 0, t * X3_KG + 2, true);
-        substep(buf, 1, t * X3_KG + 4, true);
-        sstore(buf ^ 1);
-        __syncthreads();
-    }
-    substep((T - 1) & 1, 0, (T - 1) * X3_KG + 2, true);
-    substep((T - 1) & 1, 1, 0, false);
-    // every tile's operand loads (gathered rows, scale, shift: 16 bytes each) and arithmetic first, then every tile's stores: loads that follow
-    // a store to memory the compiler cannot tell apart are not moved above it -- tile by tile, each tile's round trips came one after the other
-    EpiPointwiseT<-1, -1, PLANES> ep{epi, Y, b, M, N};
-    float v[2][2][16];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-            ep.template apply_pre<true>(m_blk + wm * 64 + i * 32 + 4 * half, min(n_blk + wn * 64 + j * 32 + l31, N - 1), acc[i][j], nullptr, v[i][j]);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) ep.store(m_blk + wm * 64 + i * 32 + 4 * half, n_blk + wn * 64 + j * 32 + l31, v[i][j]);
+    x3_clear(acc);
+    x3_k_loop_amem(T, Wp, Mp, m_blk + wm * 64 + l31, half, Bs, wn * 64 + l31, gload, sstore, acc);
+    x3_epilogue_tiles<PLANES>(epi, Y, b, M, N, m_blk, n_blk, wm, wn, acc);
 }
 
 // The planes-source kernel with BOTH operands staged through LDS: a 256 x 128 tile, eight waves (4 x 2 of 64 x 64), one workgroup per
@@ -1193,63 +1174,21 @@ __global__ __launch_bounds__(512, 1) void pointwise_gemm_x3p8_kernel(const u32x4
         for (int i = 0; i < 3; ++i) d[X3P8_A_EL + (i * 8 + wave) * 64 + lane] = sb[i];
     };
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-    auto substep = [&](int buf, int sub) __attribute__((always_inline)) {
+    x3_clear(acc);
+    auto substep = [&](int buf, int sub, int, bool) __attribute__((always_inline)) {
         const u32x4_t* d = lds8 + buf * X3P8_BUF_EL;
-        const u32x2_t* bq = reinterpret_cast<const u32x2_t*>(d + X3P8_A_EL);
         u32x4_t af[2][3], bf[2][3];
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int q = 0; q < 3; ++q) af[i][q] = d[((2 * sub + half) * 256 + wm * 64 + i * 32 + l31) * 3 + q];
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                const int n = wn * 64 + j * 32 + l31;
-                const u32x2_t lo = bq[(q * 8 + (2 * sub + half) * 2) * X3_BN + n], hi = bq[(q * 8 + (2 * sub + half) * 2 + 1) * X3_BN + n];
-                bf[j][q] = u32x4_t{lo.x, lo.y, hi.x, hi.y};
-            }
-        DI2P_MFMA_BEGIN();
-#define DI2P_X3_PROD(QA, QB)                                                                                                          \
-    _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int j = 0; j < 2; ++j)                                      \
-        acc[i][j] = bf16x3::mma(af[i][QA], bf[j][QB], acc[i][j]);
-        DI2P_X3_PROD(2, 0) DI2P_X3_PROD(1, 1) DI2P_X3_PROD(0, 2)
-        DI2P_X3_PROD(1, 0) DI2P_X3_PROD(0, 1)
-        DI2P_X3_PROD(0, 0)
-#undef DI2P_X3_PROD
-        DI2P_MFMA_END();
+        x3_bfrag(reinterpret_cast<const u32x2_t*>(d + X3P8_A_EL), sub, half, wn * 64 + l31, bf);
+        x3_products(acc, af, bf);
     };
-    gload(0);
-    sstore(0);
-    __syncthreads();
-    for (int t = 0; t + 1 < T; ++t) {
-        const int buf = t & 1;
-        gload(t + 1);
-        substep(buf, 0);
-        substep(buf, 1);
-        sstore(buf ^ 1);
-        __syncthreads();
-    }
-    substep((T - 1) & 1, 0);
-    substep((T - 1) & 1, 1);
-    EpiPointwiseT<-1, -1, PLANES> ep{epi, Y, b, M, N};
-    float v[2][2][16];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-            ep.template apply_pre<true>(m_blk + wm * 64 + i * 32 + 4 * half, min(n_blk + wn * 64 + j * 32 + l31, N - 1), acc[i][j], nullptr, v[i][j]);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) ep.store(m_blk + wm * 64 + i * 32 + 4 * half, n_blk + wn * 64 + j * 32 + l31, v[i][j]);
+    x3_k_loop(T, gload, sstore, [] {}, substep);          // both operands come through LDS: no fragment prefetch
+    x3_epilogue_tiles<PLANES>(epi, Y, b, M, N, m_blk, n_blk, wm, wn, acc);
 }
+
 
 // Wt f32 [K][M] (k-major, what the fp32 kernels read) -> [Kp/8][Mp][3][8] bf16, zero filled outside K x M.  One thread per (k-group, m).
 // MODE 0: Wt is the [K][M] matrix itself.  MODE 1 / 2: Wt is a 3 x 3 filter bank W[Cout][Cin][3][3] and the matrix is its tap-major form for
@@ -1343,60 +1282,90 @@ using Cfg64x128 = TileCfg<2, 2, 1, 2>;
 using Cfg32x128 = TileCfg<1, 4, 1, 1>;
 using Cfg64x64 = TileCfg<2, 2, 1, 1>;
 
+// ---- host struct -> device struct with the argument checks, once for every pointwise entry point (`who`: its name, for the message)
+#define PW_CHECK(cond, msg) do { if (!(cond)) { di2p_set_error("%s: %s", who, msg); return -1; } } while (0)
+
+// di2p_src_t[n_src] -> s; dense: every source is DENSE and 16-byte addressable.  k_name: what the caller calls the channel sum ("K", "K0").
+static int pw_sources(const char* who, const di2p_src_t* srcs, int n_src, int K, const char* k_name, SrcDev& s, bool& dense) {
+    s = SrcDev{};
+    dense = true;
+    int ctot = 0;
+    for (int i = 0; i < DI2P_MAX_SRC; ++i) {
+        if (i < n_src) {
+            PW_CHECK(srcs[i].ptr && srcs[i].channels > 0, "bad source");
+            PW_CHECK(srcs[i].mode != DI2P_SRC_GATHER || srcs[i].gidx, "gather source without index");
+            PW_CHECK(srcs[i].mode != DI2P_SRC_GROUP || srcs[i].group >= 1, "group source without group");
+            PW_CHECK((long long)srcs[i].channels * srcs[i].row_stride < (1ll << 31), "per-frame source extent must fit 31 bits");
+            s.ptr[i] = srcs[i].ptr; s.gidx[i] = srcs[i].gidx; s.batch_stride[i] = srcs[i].batch_stride;
+            s.row_stride[i] = srcs[i].row_stride; s.mode[i] = srcs[i].mode; s.group[i] = srcs[i].group > 0 ? srcs[i].group : 1;
+            ctot += srcs[i].channels;
+            dense = dense && srcs[i].mode == DI2P_SRC_DENSE && srcs[i].row_stride % 4 == 0 && srcs[i].batch_stride % 4 == 0 && aligned16(srcs[i].ptr);
+        }
+        s.c_end[i] = ctot;
+    }
+    s.n_src = n_src;
+    alias_absent_sources(s, n_src);
+    if (ctot != K) { di2p_set_error("%s: source channels do not sum to %s", who, k_name); return -1; }
+    return 0;
+}
+
+// di2p_epilogue_t (may be NULL) -> e.  x3: the entry point's kernels read scale / shift / batch_bias as float4 (apply_pre<true>) and can write
+// split planes -- the bf16x3 entry points, which require M % 4 == 0 themselves; the others read those rows as scalars and reject planes_out.
+// Gathered rows are read as float4 by every kernel.
+static int pw_epilogue(const char* who, const di2p_epilogue_t* epi, float* Y, int M, int N, bool x3, EpiDev& e) {
+    e = EpiDev{};
+    e.group_max = 1;
+    if (epi) {
+        e.scale = epi->scale; e.shift = epi->shift; e.batch_bias = epi->batch_bias; e.relu = epi->relu;
+        e.group_max = epi->group_max > 1 ? epi->group_max : 1;
+        e.transpose_out = epi->transpose_out;
+        // the full-size output goes to Y, or to the planes; the group maxima to group_max_out when given, else to Y (which then holds nothing else)
+        e.gmax_out = epi->group_max > 1 ? epi->group_max_out : nullptr;
+        e.gmax_dst = e.gmax_out ? e.gmax_out : Y;
+        for (int t = 0; t < 2; ++t) {
+            e.g_table[t] = epi->g_table[t]; e.g_idx[t] = epi->g_idx[t]; e.g_w[t] = epi->g_w[t]; e.g_nodes[t] = epi->g_nodes[t];
+            e.g_k[t] = e.g_table[t] ? epi->g_k[t] : 0;
+            PW_CHECK(e.g_k[t] >= 0 && e.g_k[t] <= DI2P_MAX_GK, "g_k must be in [0, DI2P_MAX_GK]");
+            PW_CHECK(!e.g_table[t] || (e.g_idx[t] && e.g_k[t] >= 1 && e.g_nodes[t] >= 1), "gathered table without index / k / nodes");
+            PW_CHECK(aligned16(e.g_table[t]), "gathered tables must be 16-byte aligned");
+        }
+        if (x3) {
+            e.planes = (u32x2_t*)epi->planes_out;
+            PW_CHECK(aligned16(e.scale) && aligned16(e.shift) && aligned16(e.batch_bias), "scale, shift and batch_bias must be 16-byte aligned");
+            PW_CHECK(!e.transpose_out || e.group_max == 1, "transpose_out excludes group_max");
+            PW_CHECK(!e.planes || (!e.transpose_out && aligned16(e.planes)), "planes_out excludes transpose_out and must be 16-byte aligned");
+            PW_CHECK(!e.planes || (long long)3 * M * N * 2 < (1ll << 31), "planes_out: a frame's planes must fit 31 bits");
+        } else {
+            PW_CHECK(!(e.g_table[0] || e.g_table[1]) || (M % 4 == 0 && M >= 4), "gathered tables need M % 4 == 0");
+            PW_CHECK(!e.transpose_out || (M % 4 == 0 && e.group_max == 1), "transpose_out needs M % 4 == 0 and no group_max");
+            PW_CHECK(!epi->planes_out, "planes_out: only the bf16x3 entry points write split planes");
+        }
+    }
+    if (x3) PW_CHECK(Y || (e.planes && (e.group_max == 1 || e.gmax_out)), "Y may be NULL only when planes_out takes the full-size output");
+    if (e.group_max > 1) {
+        const int g = e.group_max;
+        PW_CHECK((g & (g - 1)) == 0 && g <= 32 && N % g == 0, "group_max must be a power of two <= 32 dividing N");
+    }
+    return 0;
+}
+#undef PW_CHECK
+
 extern "C" int di2p_pointwise_gemm(const di2p_src_t* srcs, int n_src, const float* Wt, float* Y, int B, int M, int K, int N,
                                    const di2p_epilogue_t* epi, void* stream) {
     DI2P_CHECK_ARG(srcs && n_src >= 1 && n_src <= DI2P_MAX_SRC, "1..3 sources");
     DI2P_CHECK_ARG(B >= 0 && M >= 1 && K >= 1 && N >= 0, "bad size");
     DI2P_CHECK_ARG((long long)K * M < (1ll << 31), "weight too large");
     if (B == 0 || N == 0) return 0;
-    SrcDev s{};
-    int ctot = 0;
-    for (int i = 0; i < DI2P_MAX_SRC; ++i) {
-        if (i < n_src) {
-            DI2P_CHECK_ARG(srcs[i].ptr && srcs[i].channels > 0, "bad source");
-            DI2P_CHECK_ARG(srcs[i].mode != DI2P_SRC_GATHER || srcs[i].gidx, "gather source without index");
-            DI2P_CHECK_ARG(srcs[i].mode != DI2P_SRC_GROUP || srcs[i].group >= 1, "group source without group");
-            DI2P_CHECK_ARG((long long)srcs[i].channels * srcs[i].row_stride < (1ll << 31), "per-frame source extent must fit 31 bits");
-            s.ptr[i] = srcs[i].ptr; s.gidx[i] = srcs[i].gidx; s.batch_stride[i] = srcs[i].batch_stride;
-            s.row_stride[i] = srcs[i].row_stride; s.mode[i] = srcs[i].mode; s.group[i] = srcs[i].group > 0 ? srcs[i].group : 1;
-            ctot += srcs[i].channels;
-        }
-        s.c_end[i] = ctot;
-    }
-    s.n_src = n_src;
-    alias_absent_sources(s, n_src);
-    DI2P_CHECK_ARG(ctot == K, "source channels do not sum to K");
-    EpiDev e{};
-    e.group_max = 1;
-    if (epi) {
-        e.scale = epi->scale; e.shift = epi->shift; e.batch_bias = epi->batch_bias; e.relu = epi->relu;
-        e.group_max = epi->group_max > 1 ? epi->group_max : 1;
-        for (int t = 0; t < 2; ++t) { e.g_table[t] = epi->g_table[t]; e.g_idx[t] = epi->g_idx[t]; e.g_w[t] = epi->g_w[t]; e.g_nodes[t] = epi->g_nodes[t]; }
-        e.transpose_out = epi->transpose_out;
-        e.gmax_out = epi->group_max > 1 ? epi->group_max_out : nullptr;
-        e.gmax_dst = e.gmax_out ? e.gmax_out : Y;
-        for (int t = 0; t < 2; ++t) {
-            e.g_k[t] = e.g_table[t] ? epi->g_k[t] : 0;
-            DI2P_CHECK_ARG(e.g_k[t] >= 0 && e.g_k[t] <= DI2P_MAX_GK, "g_k must be in [0, DI2P_MAX_GK]");
-            DI2P_CHECK_ARG(!e.g_table[t] || (e.g_idx[t] && e.g_k[t] >= 1 && e.g_nodes[t] >= 1), "gathered table without index / k / nodes");
-        }
-        DI2P_CHECK_ARG(!(e.g_table[0] || e.g_table[1]) || (M % 4 == 0 && M >= 4), "gathered tables need M % 4 == 0");
-        DI2P_CHECK_ARG(!e.transpose_out || (M % 4 == 0 && e.group_max == 1), "transpose_out needs M % 4 == 0 and no group_max");
-        DI2P_CHECK_ARG(!epi->planes_out, "planes_out: only the bf16x3 entry points write split planes");
-    }
-    if (e.group_max > 1) {
-        const int g = e.group_max;
-        DI2P_CHECK_ARG((g & (g - 1)) == 0 && g <= 32 && N % g == 0, "group_max must be a power of two <= 32 dividing N");
-    }
+    SrcDev s;
+    bool dense;
+    EpiDev e;
+    if (pw_sources(__func__, srcs, n_src, K, "K", s, dense) || pw_epilogue(__func__, epi, Y, M, N, false, e)) return -1;
     hipStream_t st = (hipStream_t)stream;
     // 4-column staged path (weights 16-byte addressable, whole 4-column groups); sources that are all dense and 16-byte
     // addressable get one 16-byte load per row, gathered / group sources four dword loads
     // (narrow layers, M <= 64, are HBM/latency-bound and measured 25-35 % faster on the scalar stager below, whose K-step 16
     //  skips the rows k >= K instead of re-reading clamped ones)
     const bool vec = M > 64 && N % 4 == 0 && N >= 4 && M % 4 == 0 && aligned16(Wt) && !di2p_opt(DI2P_OPT_PW_NOVEC);
-    bool dense = true;
-    for (int i = 0; i < n_src; ++i)
-        dense = dense && srcs[i].mode == DI2P_SRC_DENSE && srcs[i].row_stride % 4 == 0 && srcs[i].batch_stride % 4 == 0 && aligned16(srcs[i].ptr);
     if (vec) {
         // 64 x 64 tiles for every layer.  Alone, the big point layers are a few per cent faster on 128 x 128 tiles, but in the 8-stream
         // pipeline the small tile (32 KB of LDS and 100 registers per workgroup instead of 64 KB and 200) packs better beside the pose
@@ -1452,38 +1421,6 @@ extern "C" int di2p_bf16x3_pack_conv3x3(const float* W, int Cout, int Cin, int d
     DI2P_RETURN_LAUNCH();
 }
 
-// the epilogue of the two bf16x3 entry points (host struct -> device struct, argument checks)
-static int x3_epilogue(const char* who, const di2p_epilogue_t* epi, float* Y, int M, int N, EpiDev& e) {
-#define X3_EPI_CHECK(cond, msg) do { if (!(cond)) { di2p_set_error("%s: %s", who, msg); return -1; } } while (0)
-    e = EpiDev{};
-    e.group_max = 1;
-    if (epi) {
-        e.scale = epi->scale; e.shift = epi->shift; e.batch_bias = epi->batch_bias; e.relu = epi->relu;
-        e.group_max = epi->group_max > 1 ? epi->group_max : 1;
-        for (int t = 0; t < 2; ++t) { e.g_table[t] = epi->g_table[t]; e.g_idx[t] = epi->g_idx[t]; e.g_w[t] = epi->g_w[t]; e.g_nodes[t] = epi->g_nodes[t]; }
-        e.transpose_out = epi->transpose_out;
-        e.planes = (u32x2_t*)epi->planes_out;
-        // the full-size output goes to Y, or to the planes; the group maxima to group_max_out when given, else to Y (which then holds nothing else)
-        e.gmax_out = epi->group_max > 1 ? epi->group_max_out : nullptr;
-        e.gmax_dst = e.gmax_out ? e.gmax_out : Y;
-        for (int t = 0; t < 2; ++t) {
-            e.g_k[t] = e.g_table[t] ? epi->g_k[t] : 0;
-            X3_EPI_CHECK(e.g_k[t] >= 0 && e.g_k[t] <= DI2P_MAX_GK, "g_k must be in [0, DI2P_MAX_GK]");
-            X3_EPI_CHECK(!e.g_table[t] || (e.g_idx[t] && e.g_k[t] >= 1 && e.g_nodes[t] >= 1), "gathered table without index / k / nodes");
-        }
-        X3_EPI_CHECK(!e.transpose_out || e.group_max == 1, "transpose_out excludes group_max");
-        X3_EPI_CHECK(!e.planes || (!e.transpose_out && ((uintptr_t)e.planes & 15) == 0), "planes_out excludes transpose_out and must be 16-byte aligned");
-        X3_EPI_CHECK(!e.planes || (long long)3 * M * N * 2 < (1ll << 31), "planes_out: a frame's planes must fit 31 bits");
-    }
-    X3_EPI_CHECK(Y || (e.planes && (e.group_max == 1 || e.gmax_out)), "Y may be NULL only when planes_out takes the full-size output");
-    if (e.group_max > 1) {
-        const int g = e.group_max;
-        X3_EPI_CHECK((g & (g - 1)) == 0 && g <= 32 && N % g == 0, "group_max must be a power of two <= 32 dividing N");
-    }
-    return 0;
-#undef X3_EPI_CHECK
-}
-
 // Same contract as di2p_pointwise_gemm with the weights given as di2p_bf16x3_pack's output (of the SAME [K][M] matrix).  Needs N % 4 == 0;
 // every epilogue of the fp32 entry point is available, and planes_out.
 extern "C" int di2p_pointwise_gemm_x3(const di2p_src_t* srcs, int n_src, const void* Wp, float* Y, int B, int M, int K, int N,
@@ -1492,28 +1429,10 @@ extern "C" int di2p_pointwise_gemm_x3(const di2p_src_t* srcs, int n_src, const v
     DI2P_CHECK_ARG(Wp && aligned16(Wp), "null / misaligned pointer");
     DI2P_CHECK_ARG(B >= 0 && M >= 4 && M % 4 == 0 && K >= 1 && N >= 4 && N % 4 == 0, "needs M % 4 == 0 and N % 4 == 0");
     if (B == 0) return 0;
-    SrcDev s{};
-    int ctot = 0;
-    for (int i = 0; i < DI2P_MAX_SRC; ++i) {
-        if (i < n_src) {
-            DI2P_CHECK_ARG(srcs[i].ptr && srcs[i].channels > 0, "bad source");
-            DI2P_CHECK_ARG(srcs[i].mode != DI2P_SRC_GATHER || srcs[i].gidx, "gather source without index");
-            DI2P_CHECK_ARG(srcs[i].mode != DI2P_SRC_GROUP || srcs[i].group >= 1, "group source without group");
-            DI2P_CHECK_ARG((long long)srcs[i].channels * srcs[i].row_stride < (1ll << 31), "per-frame source extent must fit 31 bits");
-            s.ptr[i] = srcs[i].ptr; s.gidx[i] = srcs[i].gidx; s.batch_stride[i] = srcs[i].batch_stride;
-            s.row_stride[i] = srcs[i].row_stride; s.mode[i] = srcs[i].mode; s.group[i] = srcs[i].group > 0 ? srcs[i].group : 1;
-            ctot += srcs[i].channels;
-        }
-        s.c_end[i] = ctot;
-    }
-    s.n_src = n_src;
-    alias_absent_sources(s, n_src);
-    DI2P_CHECK_ARG(ctot == K, "source channels do not sum to K");
+    SrcDev s;
+    bool dense;
     EpiDev e;
-    if (x3_epilogue(__func__, epi, Y, M, N, e)) return -1;
-    bool dense = true;
-    for (int i = 0; i < n_src; ++i)
-        dense = dense && srcs[i].mode == DI2P_SRC_DENSE && srcs[i].row_stride % 4 == 0 && srcs[i].batch_stride % 4 == 0 && aligned16(srcs[i].ptr);
+    if (pw_sources(__func__, srcs, n_src, K, "K", s, dense) || pw_epilogue(__func__, epi, Y, M, N, true, e)) return -1;
     const int Mp = di2p_cdiv(M, X3_BM) * X3_BM;
     const dim3 grid(di2p_cdiv(N, X3_BN), di2p_cdiv(M, X3_BM), B);
     const hipStream_t st = (hipStream_t)stream;
@@ -1540,13 +1459,13 @@ extern "C" int di2p_pointwise_gemm_x3p(const void* planes, const void* Wp, float
     DI2P_CHECK_ARG((long long)3 * K * N * 2 < (1ll << 31), "a frame's planes must fit 31 bits");
     if (B == 0) return 0;
     EpiDev e;
-    if (x3_epilogue(__func__, epi, Y, M, N, e)) return -1;
+    if (pw_epilogue(__func__, epi, Y, M, N, true, e)) return -1;
     const int Mp = di2p_cdiv(M, X3_BM) * X3_BM;
     const hipStream_t st = (hipStream_t)stream;
     if (M % 256 == 0 && di2p_opt(DI2P_OPT_PW_X3_PLANES) != 2) {          // 256-row tiles, both operands through LDS (knob value 2: the 128-row kernel)
         const dim3 grid(N / X3_BN, M / 256, B);
         auto k = e.planes ? pointwise_gemm_x3p8_kernel<true> : pointwise_gemm_x3p8_kernel<false>;
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, X3P8_LDS_BYTES);
+        if (di2p_allow_dynamic_lds((const void*)k, X3P8_LDS_BYTES, __func__)) return -1;
         hipLaunchKernelGGL(k, grid, dim3(512), X3P8_LDS_BYTES, st, (const u32x4_t*)planes, (const u32x4_t*)Wp, Y, M, K, N, Mp, e);
         DI2P_RETURN_LAUNCH();
     }
@@ -1565,31 +1484,14 @@ extern "C" int di2p_point_head(const di2p_src_t* srcs, int n_src, const float* W
     DI2P_CHECK_ARG(B >= 0 && N >= 4 && N % 4 == 0 && K0 >= 1, "bad size");
     DI2P_CHECK_ARG(epi0->group_max <= 1 && !epi0->transpose_out && !epi0->planes_out, "fused head: layer 0 takes scale/shift/relu/bias/gathered only");
     if (B == 0) return 0;
-    SrcDev s{};
-    int ctot = 0;
-    for (int i = 0; i < DI2P_MAX_SRC; ++i) {
-        if (i < n_src) {
-            DI2P_CHECK_ARG(srcs[i].ptr && srcs[i].channels > 0 && srcs[i].mode == DI2P_SRC_DENSE, "fused head: dense sources only");
-            DI2P_CHECK_ARG(srcs[i].row_stride % 4 == 0 && srcs[i].batch_stride % 4 == 0 && aligned16(srcs[i].ptr), "sources must be 16-byte addressable");
-            DI2P_CHECK_ARG((long long)srcs[i].channels * srcs[i].row_stride < (1ll << 31), "per-frame source extent must fit 31 bits");
-            s.ptr[i] = srcs[i].ptr; s.batch_stride[i] = srcs[i].batch_stride; s.row_stride[i] = srcs[i].row_stride; s.mode[i] = DI2P_SRC_DENSE; s.group[i] = 1;
-            ctot += srcs[i].channels;
-        }
-        s.c_end[i] = ctot;
-    }
-    s.n_src = n_src;
-    alias_absent_sources(s, n_src);
-    DI2P_CHECK_ARG(ctot == K0, "source channels do not sum to K0");
+    for (int i = 0; i < n_src; ++i) DI2P_CHECK_ARG(srcs[i].ptr && srcs[i].channels > 0 && srcs[i].mode == DI2P_SRC_DENSE, "fused head: dense sources only");
+    SrcDev s;
+    bool dense;
+    if (pw_sources(__func__, srcs, n_src, K0, "K0", s, dense)) return -1;
+    DI2P_CHECK_ARG(dense, "sources must be 16-byte addressable");
     DI2P_CHECK_ARG(aligned16(W0t) && aligned16(W1t), "weights must be 16-byte aligned");
-    EpiDev e{};
-    e.group_max = 1;
-    e.scale = epi0->scale; e.shift = epi0->shift; e.batch_bias = epi0->batch_bias; e.relu = epi0->relu;
-    for (int t = 0; t < 2; ++t) { e.g_table[t] = epi0->g_table[t]; e.g_idx[t] = epi0->g_idx[t]; e.g_w[t] = epi0->g_w[t]; e.g_nodes[t] = epi0->g_nodes[t]; }
-    for (int t = 0; t < 2; ++t) {
-        e.g_k[t] = e.g_table[t] ? epi0->g_k[t] : 0;
-        DI2P_CHECK_ARG(e.g_k[t] >= 0 && e.g_k[t] <= DI2P_MAX_GK, "g_k must be in [0, DI2P_MAX_GK]");
-        DI2P_CHECK_ARG(!e.g_table[t] || (e.g_idx[t] && e.g_k[t] >= 1 && e.g_nodes[t] >= 1), "gathered table without index / k / nodes");
-    }
+    EpiDev e;
+    if (pw_epilogue(__func__, epi0, nullptr, M, N, false, e)) return -1;
     HeadTail tl{W1t, scale1, shift1, W2t, scale2, shift2, relu1, relu2, P};
     bool reg_ok = K0 <= 96 && n_src <= 2 && di2p_opt(DI2P_OPT_HEAD_REG) != 0;
     if (n_src == 2) reg_ok = reg_ok && srcs[0].channels % 2 == 0;            // both half-waves of a K-step read the same source
@@ -1603,10 +1505,10 @@ extern "C" int di2p_point_head(const di2p_src_t* srcs, int n_src, const float* W
         const int wgs = (int)std::min<long long>(di2p_cu_count(), (total + 7) / 8);
         const size_t lds_reg = (size_t)(2 * KS0 * HEAD_M + HEAD_M * HEAD_M + HEAD_M * 4 + 4 * HEAD_M) * sizeof(float);
         if (e.g_table[0] && e.g_table[1] && e.g_k[0] == 3 && e.g_k[1] == 3) {
-            (void)hipFuncSetAttribute((const void*)point_head_reg_kernel<true, KS0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_reg);
+            if (di2p_allow_dynamic_lds((const void*)point_head_reg_kernel<true, KS0>, lds_reg, __func__)) return -1;
             hipLaunchKernelGGL((point_head_reg_kernel<true, KS0>), dim3(wgs), dim3(512), lds_reg, (hipStream_t)stream, s, W0t, K0, e, tl, out, N, nblk, (int)total);
         } else {
-            (void)hipFuncSetAttribute((const void*)point_head_reg_kernel<false, KS0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_reg);
+            if (di2p_allow_dynamic_lds((const void*)point_head_reg_kernel<false, KS0>, lds_reg, __func__)) return -1;
             hipLaunchKernelGGL((point_head_reg_kernel<false, KS0>), dim3(wgs), dim3(512), lds_reg, (hipStream_t)stream, s, W0t, K0, e, tl, out, N, nblk, (int)total);
         }
         DI2P_RETURN_LAUNCH();
@@ -1614,10 +1516,10 @@ extern "C" int di2p_point_head(const di2p_src_t* srcs, int n_src, const float* W
     const size_t lds = (HeadCfg::LDS_FLOATS + HEAD_M * HEAD_BN) * sizeof(float);
     // > 64 KB of dynamic LDS needs the opt-in (per device; the call is cheap, so it is simply made every time)
     if (e.g_table[0] && e.g_table[1] && e.g_k[0] == 3 && e.g_k[1] == 3) {      // the reference's configuration (k_interp_point_a = k_interp_point_b = 3)
-        (void)hipFuncSetAttribute((const void*)point_head_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (di2p_allow_dynamic_lds((const void*)point_head_kernel<true>, lds, __func__)) return -1;
         hipLaunchKernelGGL(point_head_kernel<true>, dim3(di2p_cdiv(N, HEAD_BN), B), dim3(HeadCfg::THREADS), lds, (hipStream_t)stream, s, W0t, K0, e, tl, out, N);
     } else {
-        (void)hipFuncSetAttribute((const void*)point_head_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (di2p_allow_dynamic_lds((const void*)point_head_kernel<false>, lds, __func__)) return -1;
         hipLaunchKernelGGL(point_head_kernel<false>, dim3(di2p_cdiv(N, HEAD_BN), B), dim3(HeadCfg::THREADS), lds, (hipStream_t)stream, s, W0t, K0, e, tl, out, N);
     }
     DI2P_RETURN_LAUNCH();
@@ -1634,15 +1536,8 @@ extern "C" int di2p_point_chain(const di2p_src_t* srcs, int n_src, const float* 
     if (B == 0) return 0;          // an empty batch has no output buffer to check
     DI2P_CHECK_ARG(Y && srcs[0].ptr && srcs[0].channels == K0 && srcs[0].mode == DI2P_SRC_DENSE, "fused chain: one dense source of K0 channels");
     DI2P_CHECK_ARG((long long)srcs[0].channels * srcs[0].row_stride < (1ll << 31), "per-frame source extent must fit 31 bits");
-    EpiDev e{};
-    e.group_max = 1;
-    e.scale = epi0->scale; e.shift = epi0->shift; e.batch_bias = epi0->batch_bias; e.relu = epi0->relu;
-    for (int t = 0; t < 2; ++t) { e.g_table[t] = epi0->g_table[t]; e.g_idx[t] = epi0->g_idx[t]; e.g_w[t] = epi0->g_w[t]; e.g_nodes[t] = epi0->g_nodes[t]; }
-    for (int t = 0; t < 2; ++t) {
-        e.g_k[t] = e.g_table[t] ? epi0->g_k[t] : 0;
-        DI2P_CHECK_ARG(e.g_k[t] >= 0 && e.g_k[t] <= DI2P_MAX_GK, "g_k must be in [0, DI2P_MAX_GK]");
-        DI2P_CHECK_ARG(!e.g_table[t] || (e.g_idx[t] && e.g_k[t] >= 1 && e.g_nodes[t] >= 1), "gathered table without index / k / nodes");
-    }
+    EpiDev e;
+    if (pw_epilogue(__func__, epi0, nullptr, M, N, false, e)) return -1;
     ChainTail tl{W1t, scale1, shift1, W2t, scale2, shift2, relu1, relu2};
     const float* X = srcs[0].ptr;
     const long long x_bs = srcs[0].batch_stride;

@@ -279,10 +279,10 @@ extern "C" int di2p_point_head_labels_x3(const di2p_head_labels_x3_t* hd, int B,
     const int grid = a.total < di2p_cu_count() ? a.total : di2p_cu_count();      // one 104 KB workgroup per compute unit, persistent
     hipStream_t st = (hipStream_t)stream;
     if (a.ptiles <= 4) {
-        (void)hipFuncSetAttribute((const void*)point_head_labels_x3_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HL_LDS);
+        if (di2p_allow_dynamic_lds((const void*)point_head_labels_x3_kernel<1>, HL_LDS, __func__)) return -1;
         hipLaunchKernelGGL(point_head_labels_x3_kernel<1>, dim3(grid), dim3(HL_NW * 64), HL_LDS, st, a);
     } else {
-        (void)hipFuncSetAttribute((const void*)point_head_labels_x3_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HL_LDS);
+        if (di2p_allow_dynamic_lds((const void*)point_head_labels_x3_kernel<2>, HL_LDS, __func__)) return -1;
         hipLaunchKernelGGL(point_head_labels_x3_kernel<2>, dim3(grid), dim3(HL_NW * 64), HL_LDS, st, a);
     }
     DI2P_RETURN_LAUNCH();

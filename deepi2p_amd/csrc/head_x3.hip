@@ -397,10 +397,10 @@ extern "C" int di2p_point_head_x3(const di2p_head_x3_t* hd, float* out, int B, i
         // instructions -- 242 us alone against 339 for four waves with 512 registers (knob value 2; the eight-wave form with the deeper request
         // rings spilled 368 bytes per lane and took 385-430 us).  In the 8-stream pipeline the two are within 0.5 % of each other.
         if (opt == 2) {
-            (void)hipFuncSetAttribute((const void*)point_head_x3_kernel<true, 6, 4, 1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_tab);
+            if (di2p_allow_dynamic_lds((const void*)point_head_x3_kernel<true, 6, 4, 1, false, true>, lds_tab, __func__)) return -1;
             hipLaunchKernelGGL((point_head_x3_kernel<true, 6, 4, 1, false, true>), dim3(B * parts), dim3(256), lds_tab, st, a);
         } else {
-            (void)hipFuncSetAttribute((const void*)point_head_x3_kernel<true, 6, 8, 2, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_tab);
+            if (di2p_allow_dynamic_lds((const void*)point_head_x3_kernel<true, 6, 8, 2, false, false, true>, lds_tab, __func__)) return -1;
             hipLaunchKernelGGL((point_head_x3_kernel<true, 6, 8, 2, false, false, true>), dim3(B * parts), dim3(512), lds_tab, st, a);
         }
     } else {

@@ -148,7 +148,7 @@ extern "C" int di2p_conv7x7s2_stem(const float* x, const float* Wp, const float*
     const long long total = (long long)B * n_rt * n_ct;
     DI2P_CHECK_ARG(total < (1ll << 31), "too many work items");
     const long long grid = total < 512 ? total : 512;            // two persistent workgroups per CU
-    (void)hipFuncSetAttribute((const void*)stem_conv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(ST_LDS_FLOATS * sizeof(float)));
+    if (di2p_allow_dynamic_lds((const void*)stem_conv_kernel, ST_LDS_FLOATS * sizeof(float), __func__)) return -1;
     hipLaunchKernelGGL(stem_conv_kernel, dim3((unsigned)grid), dim3(256), ST_LDS_FLOATS * sizeof(float), (hipStream_t)stream, x, Wp, scale, shift, y, H, W, OH,
                        OW, n_ct, n_rt, (int)total, relu);
     DI2P_RETURN_LAUNCH();

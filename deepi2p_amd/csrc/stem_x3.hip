@@ -333,7 +333,7 @@ extern "C" int di2p_stem_x3(const float* x, const void* Wp, const float* scale, 
     a.tiles = di2p_cdiv(a.PH, a.prw);
     a.LW = W + 8; a.LDT = a.OW + 4;
     const size_t lds = (size_t)SX_RING * 9 * a.LW * 2 + (size_t)SX_CO * a.LDT * 4 + 16;
-    (void)hipFuncSetAttribute((const void*)stem_x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (di2p_allow_dynamic_lds((const void*)stem_x3_kernel, lds, __func__)) return -1;
     hipLaunchKernelGGL(stem_x3_kernel, dim3(B * a.tiles), dim3(256), lds, (hipStream_t)stream, a);
     DI2P_RETURN_LAUNCH();
 }

@@ -367,7 +367,7 @@ int rc_launch(const char* who, LA la, LB lb, int Z, int rows, int cols, int R, f
     const size_t lds = RC_LDS_FLOATS * sizeof(float);
     if constexpr (std::is_same<LA, RcStrided>::value && std::is_same<LB, RcStrided>::value) {
         if (big) {
-            (void)hipFuncSetAttribute((const void*)rc_gemm128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(RC2_LDS_FLOATS * sizeof(float)));
+            if (di2p_allow_dynamic_lds((const void*)rc_gemm128_kernel, RC2_LDS_FLOATS * sizeof(float), who)) return -1;
             hipLaunchKernelGGL(rc_gemm128_kernel, grid, dim3(256), RC2_LDS_FLOATS * sizeof(float), st, la, lb, R, pl.rch, pl.chunks, (float*)ws, rows, cols);
         } else if (a_vec && b_vec) hipLaunchKernelGGL((rc_gemm_kernel<true, true, LA, LB>), grid, dim3(256), lds, st, la, lb, R, pl.rch, pl.chunks, (float*)ws, rows, cols);
         else hipLaunchKernelGGL((rc_gemm_kernel<false, false, LA, LB>), grid, dim3(256), lds, st, la, lb, R, pl.rch, pl.chunks, (float*)ws, rows, cols);

@@ -482,7 +482,7 @@ extern "C" int di2p_conv3x3_winograd(const float* x, const float* U, const float
         const int by_co = n_cb % 8 == 0 && (map_opt ? map_opt == 2 : (long long)16 * Cin * Cout * 4 > (2ll << 20));                           \
         const int grid = by_co ? n_cb * n_tb : di2p_cdiv(n_tb, 8) * 8 * n_cb;                                                                \
         const size_t lds = WinoLds<COBV, DBV, KCV>::TOTAL * sizeof(float);                                                                        \
-        (void)hipFuncSetAttribute((const void*)wino_conv_kernel<COBV, DBV, KCV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);           \
+        if (di2p_allow_dynamic_lds((const void*)wino_conv_kernel<COBV, DBV, KCV>, lds, __func__)) return -1;                                      \
         hipLaunchKernelGGL((wino_conv_kernel<COBV, DBV, KCV>), dim3(grid), dim3(256), lds, st, x, U, scale, shift, residual, y, Cin, H, W, Cout, \
                            TH, TW, (int)total, n_tb, n_cb, relu, by_co);                                                                     \
     } while (0)

@@ -340,6 +340,11 @@ def pointwise_gemm(srcs, Wt, M, N, scale=None, shift=None, batch_bias=None, relu
         x3 = True
     if planes_out and (transpose_out or not X3Planes.ok(M, N)):
         raise RuntimeError("planes_out needs M % 32 == 0, N % 128 == 0 and no transpose_out")
+    if x3 is not False and any(t is not None and t.data_ptr() % 16 for t in (scale, shift, batch_bias)):
+        # the bf16x3 kernels read the per-row operands 16 bytes at a time (a bias that is a view at an odd offset of a flat parameter buffer)
+        if x3 is not None and x3 != "step":
+            raise RuntimeError("bf16x3 needs 16-byte aligned scale, shift and batch_bias")
+        x3 = False
     Wp = _x3_operand(Wt, B, M, N, x3)
     if planes_out and Wp is None:
         raise RuntimeError("planes_out: only the bf16x3 kernels write split planes")

@@ -137,6 +137,8 @@ typedef struct {
                                   transpose_out.  Y then only receives the group maxima (group_max > 1 and group_max_out == NULL) and
                                   may be NULL otherwise. */
 } di2p_epilogue_t;
+/* Alignment: every g_table must be 16-byte aligned (all kernels read gathered rows 16 bytes at a time); the bf16x3 entry points
+ * (di2p_pointwise_gemm_x3 / _x3p) also need scale, shift and batch_bias 16-byte aligned, with M % 4 == 0 for the batch_bias rows. */
 
 int di2p_pointwise_gemm(const di2p_src_t* srcs_host, int n_src, const float* Wt, float* Y,
                         int B, int M, int K, int N, const di2p_epilogue_t* epi_host, void* stream);

@@ -45,6 +45,104 @@ def test_argument_errors_are_reported_not_crashed():
     _lib.call("di2p_index_max_forward", None, None, None, 0, 4, 10, 8, None, None)
 
 
+def test_pointwise_entry_points_share_their_argument_checks():
+    # in a thread of its own: di2p_last_error is per thread, and the export test above expects "ok" on the main thread
+    import concurrent.futures
+    with concurrent.futures.ThreadPoolExecutor(1) as ex:
+        ex.submit(_pointwise_argument_checks).result()
+
+
+def _pointwise_argument_checks():
+    """The five pointwise entry points marshal their sources and their epilogue through one function each (gemm.hip: pw_sources,
+    pw_epilogue): every argument error carries the entry point's own name, and comes before any device call -- the addresses below are
+    made up and never dereferenced."""
+    from deepi2p_amd import _lib
+    E, SrcT, EpilogueT = _lib.DeepI2PHipError, _lib.SrcT, _lib.EpilogueT
+    fake = 4096                                  # 16-byte aligned; fake + 4: addr % 16 == 4
+    B, N = 2, 256
+
+    def srcs(*specs):                            # (channels, mode, gidx, group)
+        arr = (SrcT * 4)()                       # room for the n_src = 4 case
+        for i, (c, mode, gidx, group) in enumerate(specs):
+            arr[i].ptr, arr[i].gidx, arr[i].batch_stride, arr[i].row_stride = fake, gidx, c * N, N
+            arr[i].channels, arr[i].mode, arr[i].group = c, mode, group
+        return arr
+
+    dense = lambda c: (c, _lib.SRC_DENSE, None, 0)
+
+    def epi(**kw):
+        e = EpilogueT()
+        e.group_max = 1
+        for k, v in kw.items():
+            if isinstance(v, tuple):
+                for t, x in enumerate(v):
+                    getattr(e, k)[t] = x
+            else:
+                setattr(e, k, v)
+        return e
+
+    # every entry point as f(sources, n_src, epilogue, B) on a shape it accepts: M = 128 (chain: 64), K = 64, N = 256
+    def gemm(s, n, e, B=B):
+        _lib.call("di2p_pointwise_gemm", s, n, fake, fake, B, 128, 64, N, ctypes.byref(e), None)
+
+    def gemm_x3(s, n, e, B=B):
+        _lib.call("di2p_pointwise_gemm_x3", s, n, fake, fake, B, 128, 64, N, ctypes.byref(e), None)
+
+    def gemm_x3p(s, n, e, B=B):
+        _lib.call("di2p_pointwise_gemm_x3p", fake, fake, fake, B, 128, 64, N, ctypes.byref(e), None)
+
+    def head(s, n, e, B=B):
+        _lib.call("di2p_point_head", ctypes.cast(s, ctypes.c_void_p), n, fake, 64, ctypes.cast(ctypes.pointer(e), ctypes.c_void_p), fake, None, None, 1,
+                  fake, None, None, 0, fake, B, 128, 2, N, None)
+
+    def chain(s, n, e, B=B):
+        _lib.call("di2p_point_chain", ctypes.cast(s, ctypes.c_void_p), n, fake, 64, ctypes.cast(ctypes.pointer(e), ctypes.c_void_p), fake, None, None, 1,
+                  None, None, None, 0, fake, B, 64, N, None)
+
+    entries = {"di2p_pointwise_gemm": gemm, "di2p_pointwise_gemm_x3": gemm_x3, "di2p_pointwise_gemm_x3p": gemm_x3p, "di2p_point_head": head,
+               "di2p_point_chain": chain}
+
+    def fails(name, text, s, n, e):
+        with pytest.raises(E, match=re.escape(": %s: %s" % (name, text))):
+            entries[name](s, n, e)
+
+    one = srcs(dense(64))
+    # ---- sources
+    for name in ("di2p_pointwise_gemm", "di2p_pointwise_gemm_x3"):
+        fails(name, "source channels do not sum to K", srcs(dense(32), dense(16)), 2, epi())
+        fails(name, "gather source without index", srcs((64, _lib.SRC_GATHER, None, 0)), 1, epi())
+        fails(name, "group source without group", srcs((64, _lib.SRC_GROUP, None, 0)), 1, epi())
+        fails(name, "1..3 sources", one, 0, epi())
+        fails(name, "1..3 sources", srcs(dense(16), dense(16), dense(16), dense(16)), 4, epi())
+    fails("di2p_point_head", "source channels do not sum to K0", srcs(dense(32), dense(16)), 2, epi())
+    fails("di2p_point_head", "fused head: dense sources only", srcs((64, _lib.SRC_GATHER, None, 0)), 1, epi())
+    fails("di2p_point_head", "fused head: dense sources only", srcs((64, _lib.SRC_GROUP, None, 0)), 1, epi())
+    fails("di2p_point_head", "null pointer", one, 0, epi())
+    fails("di2p_point_head", "null pointer", srcs(dense(16), dense(16), dense(16), dense(16)), 4, epi())
+    odd = srcs(dense(64))
+    odd[0].ptr = fake + 4
+    fails("di2p_point_head", "sources must be 16-byte addressable", odd, 1, epi())
+    fails("di2p_point_chain", "fused chain: one dense source", one, 0, epi())
+    fails("di2p_point_chain", "fused chain: one dense source of K0 channels", srcs((64, _lib.SRC_GATHER, None, 0)), 1, epi())
+    # ---- epilogue
+    for name in entries:
+        fails(name, "g_k must be in [0, DI2P_MAX_GK]", one, 1, epi(g_table=(fake,), g_idx=(fake,), g_nodes=(8,), g_k=(17,)))
+        fails(name, "gathered table without index / k / nodes", one, 1, epi(g_table=(fake,), g_nodes=(8,), g_k=(3,)))
+        fails(name, "gathered tables must be 16-byte aligned", one, 1, epi(g_table=(fake + 4,), g_idx=(fake,), g_nodes=(8,), g_k=(3,)))
+        entries[name](one, 1, epi(), B=0)                                    # an empty batch stays a valid no-op
+    for name in ("di2p_pointwise_gemm", "di2p_pointwise_gemm_x3", "di2p_pointwise_gemm_x3p"):
+        for g in (3, 64):
+            fails(name, "group_max must be a power of two <= 32 dividing N", one, 1, epi(group_max=g))
+    for name, what in (("di2p_point_head", "fused head"), ("di2p_point_chain", "fused chain")):
+        for kw in (dict(group_max=16), dict(transpose_out=1), dict(planes_out=fake)):
+            fails(name, what + ": layer 0 takes scale/shift/relu/bias/gathered only", one, 1, epi(**kw))
+    fails("di2p_pointwise_gemm", "planes_out: only the bf16x3 entry points write split planes", one, 1, epi(planes_out=fake))
+    # the bf16x3 kernels read the per-row operands 16 bytes at a time
+    for name in ("di2p_pointwise_gemm_x3", "di2p_pointwise_gemm_x3p"):
+        for field in ("scale", "shift", "batch_bias"):
+            fails(name, "scale, shift and batch_bias must be 16-byte aligned", one, 1, epi(**{field: fake + 4}))
+
+
 def test_host_side_shape_queries_of_the_bf16x3_entry_points_with_cfg():
     """Pure host logic behind the C ABI (no device needed): which shapes the round-5 kernels take, and the sizes of their packed operands.
     ABI 8: di2p_conv3x3_x3_supported takes the tile configuration (-1: the knob conv_x3_cfg, by default the cost model's choice)."""

@@ -431,3 +431,14 @@ def test_bf16x3_split_planes_argument_checks(dev):
     with pytest.raises(_lib.DeepI2PHipError):                        # Y == NULL without planes_out
         _lib.call("di2p_pointwise_gemm_x3p", pl.t.data_ptr(), Wp.data_ptr(), None, 1, 256, 256, 256, None, _lib.stream())
     assert _lib.load().di2p_bf16x3_planes_bytes(2, 256, 2048) == 2 * 3 * 256 * 2048 * 2
+    # the bf16x3 kernels read scale / shift / batch_bias 16 bytes at a time: a shift that is a view at a one-float offset of a larger buffer
+    # sends a layer the automatic rule would run on bf16x3 to the fp32 kernel (same bits as forcing it); forcing bf16x3 raises
+    x2 = torch.randn(1, 256, 512, generator=g).to(dev)
+    shift = torch.randn(257, generator=g).to(dev)[1:]
+    assert shift.data_ptr() % 16 == 4 and ops._x3_auto(W, 256, 512)
+    y_auto = ops.pointwise_gemm([ops.Src(x2)], W, 256, 512, shift=shift, relu=True)
+    y_fp32 = ops.pointwise_gemm([ops.Src(x2)], W, 256, 512, shift=shift, relu=True, x3=False)
+    assert torch.equal(y_auto, y_fp32)
+    assert torch.equal(ops.pointwise_gemm([ops.Src(x2)], W, 256, 512, shift=shift, relu=True, x3="step"), y_fp32)
+    with pytest.raises(RuntimeError):
+        ops.pointwise_gemm([ops.Src(x2)], W, 256, 512, shift=shift, relu=True, x3=True)
