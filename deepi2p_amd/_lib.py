@@ -46,6 +46,11 @@ class HeadLabelsX3T(ctypes.Structure):      # di2p_head_labels_x3_t
                 ("scores", c_void_p), ("coarse", c_void_p), ("fine", c_void_p)]
 
 
+class SampleOptT(ctypes.Structure):      # di2p_sample_opt_t
+    _fields_ = [("mode", c_int), ("crop_top", c_int), ("img_scale", c_double), ("img_H", c_int), ("img_W", c_int), ("Hs", c_int), ("Ws", c_int),
+                ("amplitude", c_double * 6), ("color_range", c_double * 8)]
+
+
 SRC_DENSE, SRC_GATHER, SRC_GROUP = 0, 1, 2
 
 # name -> argtypes (all return int)
@@ -131,6 +136,13 @@ _SIGS = {
     "di2p_group_max_backward": [c_void_p, c_void_p, c_void_p, c_ll, c_int, c_void_p],
     "di2p_dropout_mask": [ctypes.c_ulonglong, c_int, c_float, c_ll, c_void_p, c_void_p],
     "di2p_apply_mask": [c_void_p, c_void_p, c_float, c_void_p, c_ll, c_void_p],
+    "di2p_sample_draws": [ctypes.c_ulonglong, c_void_p, c_int, c_int, ctypes.POINTER(SampleOptT)] + [c_void_p] * 10,
+    "di2p_image_prepare": [c_void_p, c_int, c_int, c_int, ctypes.POINTER(SampleOptT), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                           c_void_p],
+    "di2p_transform_segments": [c_void_p] * 4 + [c_int, c_int] + [c_void_p] * 3,
+    "di2p_gather_ragged_aug": [c_void_p] * 6 + [c_int, c_int, ctypes.c_ulonglong, c_void_p, c_int, c_double, c_double] + [c_void_p] * 4,
+    "di2p_random_choice_dseed": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "di2p_random_choice_ragged_dseed": [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
 }
 _WS_SIGS = {        # <name>_workspace_bytes helpers returning long long
     "di2p_channel_reduce_workspace_bytes": [c_int] * 3,
@@ -144,6 +156,7 @@ _WS_SIGS = {        # <name>_workspace_bytes helpers returning long long
     "di2p_stem_x3_packed_bytes": [],
     "di2p_scan_prep_workspace_bytes": [c_int, c_int],
     "di2p_random_choice_ragged_workspace_bytes": [c_int, c_int],
+    "di2p_image_prepare_workspace_bytes": [c_int],
 }
 EXPORTS = sorted(list(_SIGS) + ["di2p_last_error", "di2p_version", "di2p_solve_workspace_bytes", "di2p_solver_set_profile_buffer", "di2p_pnp_workspace_bytes",
                  "di2p_conv2d_workspace_bytes", "di2p_set_option", "di2p_get_option", "di2p_random_choice_workspace_bytes", "di2p_classifier_loss_workspace_bytes"] + list(_WS_SIGS))

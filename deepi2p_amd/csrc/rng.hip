@@ -9,28 +9,9 @@
 // The reference's generators are host Mersenne Twisters with process-global state; no stream of theirs can be reproduced,
 // only the distributions: normal(0, sigma), uniform(-amp, amp), uniform subsets in uniform random order.
 #include "common.h"
+#include "philox.h"
 
 namespace {
-
-struct U4 { unsigned x, y, z, w; };
-
-__device__ __forceinline__ U4 philox4x32_10(U4 ctr, unsigned k0, unsigned k1) {
-    constexpr unsigned M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = (unsigned long long)M0 * ctr.x, p1 = (unsigned long long)M1 * ctr.z;
-        const U4 n{(unsigned)(p1 >> 32) ^ ctr.y ^ k0, (unsigned)p1, (unsigned)(p0 >> 32) ^ ctr.w ^ k1, (unsigned)p0};
-        ctr = n;
-        k0 += W0; k1 += W1;
-    }
-    return ctr;
-}
-
-// 53-bit uniform in (0, 1]: never 0, so log() is finite
-__device__ __forceinline__ double u53(unsigned hi, unsigned lo) {
-    const unsigned long long m = ((unsigned long long)(hi >> 5) << 26) | (unsigned long long)(lo >> 6);
-    return ((double)m + 1.0) * (1.0 / 9007199254740992.0);
-}
 
 // stream 0: the restart list.  counter = (hypothesis index low, high, stream, 0)
 __global__ __launch_bounds__(256) void draw_restarts_kernel(unsigned long long seed, long long n, double sigma, double amp,
@@ -53,8 +34,10 @@ __global__ __launch_bounds__(256) void draw_restarts_kernel(unsigned long long s
 // every index floor(n_out / n_src) times, then the first n_out mod n_src keys (prep.downsample's rule); an empty frame gives -1.
 __global__ __launch_bounds__(1024) void random_choice_kernel(unsigned long long seed, int stream_id, int n_src, int P, int n_out,
                                                              unsigned long long* __restrict__ keys_all, int* __restrict__ out,
-                                                             const int* __restrict__ offsets) {
+                                                             const int* __restrict__ offsets,
+                                                             const unsigned long long* __restrict__ seed_dev) {
     constexpr int CH = 8192;
+    if (seed_dev) seed = *seed_dev;      // a captured graph keeps the pointer, not the value: a replay draws from the slot's current seed
     __shared__ unsigned long long chunk[CH];
     const int b = blockIdx.x, tid = threadIdx.x;
     if (offsets) {
@@ -159,7 +142,7 @@ extern "C" int di2p_random_choice(unsigned long long seed, int stream_id, int B,
     DI2P_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "workspace must be 8-byte aligned");
     if (B == 0 || n_out == 0) return 0;
     hipLaunchKernelGGL(random_choice_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, seed, stream_id, n_src, pow2_at_least(n_src),
-                       n_out, (unsigned long long*)workspace, idx_out, (const int*)nullptr);
+                       n_out, (unsigned long long*)workspace, idx_out, (const int*)nullptr, (const unsigned long long*)nullptr);
     DI2P_RETURN_LAUNCH();
 }
 
@@ -172,7 +155,29 @@ extern "C" int di2p_random_choice_ragged(unsigned long long seed, int stream_id,
     DI2P_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "workspace must be 8-byte aligned");
     if (B == 0 || n_out == 0) return 0;
     hipLaunchKernelGGL(random_choice_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, seed, stream_id, max_src, pow2_at_least(max_src),
-                       n_out, (unsigned long long*)workspace, idx_out, (const int*)offsets);
+                       n_out, (unsigned long long*)workspace, idx_out, (const int*)offsets, (const unsigned long long*)nullptr);
+    DI2P_RETURN_LAUNCH();
+}
+
+// the two choices above with the seed read from device memory at run time (seed_dev: one 64-bit word)
+extern "C" int di2p_random_choice_dseed(const unsigned long long* seed_dev, int stream_id, int B, int n_src, int n_out, int32_t* idx_out,
+                                        void* workspace, void* stream) {
+    DI2P_CHECK_ARG(B >= 0 && n_src >= 1 && n_out >= 0 && n_out <= n_src && idx_out && workspace && seed_dev, "bad args (n_out <= n_src)");
+    DI2P_CHECK_ARG(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)seed_dev & 7) == 0, "workspace and seed_dev must be 8-byte aligned");
+    if (B == 0 || n_out == 0) return 0;
+    hipLaunchKernelGGL(random_choice_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, 0ull, stream_id, n_src, pow2_at_least(n_src),
+                       n_out, (unsigned long long*)workspace, idx_out, (const int*)nullptr, seed_dev);
+    DI2P_RETURN_LAUNCH();
+}
+
+extern "C" int di2p_random_choice_ragged_dseed(const unsigned long long* seed_dev, int stream_id, int B, const int32_t* offsets, int max_src,
+                                               int n_out, int32_t* idx_out, void* workspace, void* stream) {
+    DI2P_CHECK_ARG(B >= 0 && max_src >= 1 && max_src <= (1 << 20) && n_out >= 0, "bad args (1 <= max_src <= 2^20, n_out >= 0)");
+    DI2P_CHECK_ARG(B == 0 || (offsets && idx_out && workspace && seed_dev), "null pointer");
+    DI2P_CHECK_ARG(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)seed_dev & 7) == 0, "workspace and seed_dev must be 8-byte aligned");
+    if (B == 0 || n_out == 0) return 0;
+    hipLaunchKernelGGL(random_choice_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, 0ull, stream_id, max_src, pow2_at_least(max_src),
+                       n_out, (unsigned long long*)workspace, idx_out, (const int*)offsets, seed_dev);
     DI2P_RETURN_LAUNCH();
 }
 

@@ -13,6 +13,7 @@
 // Sorting: rocPRIM's stable device radix sort, temporary storage from the workspace.  Stability makes the summation order (ascending
 // input index inside a voxel) and therefore the bits reproducible.
 #include "common.h"
+#include "philox.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -489,10 +490,22 @@ __global__ __launch_bounds__(256) void nearest_raw_kernel(const float* __restric
     }
 }
 
-// ---------------------------------------------------------------- stage 4: ragged gather (+ rigid transform)
+// ---------------------------------------------------------------- stage 4: ragged gather (+ jitter) (+ rigid transform)
+// Jitter (sigma > 0): clip(sigma * N(0,1), +-clip) rounded to float32, a pure function of (seed, stream_id, frame, output index, component):
+// Philox counter (n, frame, stream_id * 8 + component, 5), component 0..2 the point, 4..6 the normal; Box-Muller on two 53-bit uniforms.
+struct Jitter { unsigned long long seed; const unsigned long long* seed_dev; int stream_id; double sigma, clip; };
+
+__device__ __forceinline__ float jitter_noise(unsigned long long seed, const Jitter& j, int b, int n, int comp) {
+    const U4 r = philox4x32_10(U4{(unsigned)n, (unsigned)b, (unsigned)(j.stream_id * 8 + comp), 5u}, (unsigned)seed, (unsigned)(seed >> 32));
+    const double z = sqrt(-2.0 * log(u53(r.x, r.y))) * cos(6.283185307179586476925 * u53(r.z, r.w));
+    const double v = j.sigma * z;
+    return (float)(v < -j.clip ? -j.clip : v > j.clip ? j.clip : v);
+}
+
 __global__ __launch_bounds__(256) void gather_ragged_kernel(const float* __restrict__ pts, const float* __restrict__ inten, const float* __restrict__ nrm,
                                                             const int* __restrict__ off, const int* __restrict__ idx, const double* __restrict__ T,
-                                                            int n_out, float* __restrict__ pc, float* __restrict__ out_int, float* __restrict__ sn) {
+                                                            int n_out, float* __restrict__ pc, float* __restrict__ out_int, float* __restrict__ sn,
+                                                            Jitter jit) {
     const int b = blockIdx.y, n = blockIdx.x * 256 + threadIdx.x;
     if (n >= n_out) return;
     const int i = idx[(long long)b * n_out + n];
@@ -504,6 +517,13 @@ __global__ __launch_bounds__(256) void gather_ragged_kernel(const float* __restr
         for (int c = 0; c < 3; ++c) p[c] = (double)pts[3 * g + c];
         if (nrm) for (int c = 0; c < 3; ++c) s[c] = (double)nrm[3 * g + c];
         if (inten) it = inten[g];
+        if (jit.sigma > 0.0) {      // augmentation.jitter_point_cloud: float32 noise + float32 value, before the transform, normals not re-normalised
+            const unsigned long long seed = jit.seed_dev ? *jit.seed_dev : jit.seed;
+            for (int c = 0; c < 3; ++c) {
+                p[c] = (double)__fadd_rn(jitter_noise(seed, jit, b, n, c), (float)p[c]);
+                if (nrm) s[c] = (double)__fadd_rn(jitter_noise(seed, jit, b, n, 4 + c), (float)s[c]);
+            }
+        }
     }
     const long long o3 = (long long)b * 3 * n_out + n;
     if (T && ok) {
@@ -525,25 +545,42 @@ int frame_bits(int B) { int bits = 1; while ((1ll << bits) <= B) ++bits; return 
 
 // Stable sort of `cap` elements by (frame, 63-bit key): a stable radix sort on the key, then a stable one on the frame of each element
 // (LSD order).  idx_out = original positions, key_out = their keys, fr_out = their frames.
-hipError_t sort_by_frame_key(void* ws, const Layout& L, int B, int cap, const unsigned long long* key_in, const unsigned* elem_frame,
-                             int* idx_out, unsigned long long* key_out, unsigned* fr_out, hipStream_t st) {
+// Above 2^20 elements rocPRIM's radix sort switches from its merge-sort path to onesweep (decoupled look-back: a memset of the look-back
+// states and of an atomic workgroup counter before every digit place).  Memset nodes of a captured graph are not reliably ordered before
+// the kernel node behind them when the graph is replayed here: replayed with 1.92 M elements that path ended in an
+// illegal memory access (eager launches of the same sort are fine, and so are replays of the merge-sort path, which clears nothing), so
+// while the stream is capturing the sorts stay on the merge-sort path at every size.  Both paths are stable sorts: the same output, bit for bit.
+using SortMergeOnly = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, rocprim::default_config, (size_t)1 << 40>;
+
+template <class Cfg>
+hipError_t sort_by_frame_key_cfg(void* ws, const Layout& L, int B, int cap, const unsigned long long* key_in, const unsigned* elem_frame,
+                                 int* idx_out, unsigned long long* key_out, unsigned* fr_out, hipStream_t st) {
     void* tmp = at<void>(ws, L.tmp);
     size_t need1 = 0, need2 = 0;
     hipError_t e;
-    e = rocprim::radix_sort_pairs(nullptr, need1, key_in, at<unsigned long long>(ws, L.k1), at<int>(ws, L.iota), at<int>(ws, L.i1), cap, 0, 63, st);
+    e = rocprim::radix_sort_pairs<Cfg>(nullptr, need1, key_in, at<unsigned long long>(ws, L.k1), at<int>(ws, L.iota), at<int>(ws, L.i1), cap, 0, 63, st);
     if (e != hipSuccess) return e;
-    e = rocprim::radix_sort_pairs(nullptr, need2, at<unsigned>(ws, L.f1), fr_out, at<int>(ws, L.i1), idx_out, cap, 0, frame_bits(B), st);
+    e = rocprim::radix_sort_pairs<Cfg>(nullptr, need2, at<unsigned>(ws, L.f1), fr_out, at<int>(ws, L.i1), idx_out, cap, 0, frame_bits(B), st);
     if (e != hipSuccess) return e;
     if (need1 > L.tmp_bytes || need2 > L.tmp_bytes) return hipErrorInvalidValue;
     size_t sz = L.tmp_bytes;
-    e = rocprim::radix_sort_pairs(tmp, sz, key_in, at<unsigned long long>(ws, L.k1), at<int>(ws, L.iota), at<int>(ws, L.i1), cap, 0, 63, st);
+    e = rocprim::radix_sort_pairs<Cfg>(tmp, sz, key_in, at<unsigned long long>(ws, L.k1), at<int>(ws, L.iota), at<int>(ws, L.i1), cap, 0, 63, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(gather_frames_kernel, dim3(di2p_cdiv(cap, 256)), dim3(256), 0, st, elem_frame, at<int>(ws, L.i1), at<unsigned>(ws, L.f1), cap);
     sz = L.tmp_bytes;
-    e = rocprim::radix_sort_pairs(tmp, sz, at<unsigned>(ws, L.f1), fr_out, at<int>(ws, L.i1), idx_out, cap, 0, frame_bits(B), st);
+    e = rocprim::radix_sort_pairs<Cfg>(tmp, sz, at<unsigned>(ws, L.f1), fr_out, at<int>(ws, L.i1), idx_out, cap, 0, frame_bits(B), st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(gather_keys_kernel, dim3(di2p_cdiv(cap, 256)), dim3(256), 0, st, key_in, idx_out, key_out, cap);
     return hipGetLastError();
+}
+
+hipError_t sort_by_frame_key(void* ws, const Layout& L, int B, int cap, const unsigned long long* key_in, const unsigned* elem_frame,
+                             int* idx_out, unsigned long long* key_out, unsigned* fr_out, hipStream_t st) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    const hipError_t e = hipStreamIsCapturing(st, &cs);
+    if (e != hipSuccess) return e;
+    if (cs != hipStreamCaptureStatusNone) return sort_by_frame_key_cfg<SortMergeOnly>(ws, L, B, cap, key_in, elem_frame, idx_out, key_out, fr_out, st);
+    return sort_by_frame_key_cfg<rocprim::default_config>(ws, L, B, cap, key_in, elem_frame, idx_out, key_out, fr_out, st);
 }
 
 int persistent_grid(int per_cu) { return di2p_cu_count() * per_cu; }
@@ -651,6 +688,21 @@ extern "C" int di2p_gather_ragged(const float* points, const float* intensity, c
     DI2P_CHECK_ARG(!sn || normals, "sn needs normals");
     if (B == 0 || n_out == 0) return 0;
     hipLaunchKernelGGL(gather_ragged_kernel, dim3(di2p_cdiv(n_out, 256), B), dim3(256), 0, (hipStream_t)stream, points, intensity, normals, offsets,
-                       idx, transform, n_out, pc, intensity_out, sn);
+                       idx, transform, n_out, pc, intensity_out, sn, Jitter{0ull, nullptr, 0, 0.0, 0.0});
+    DI2P_RETURN_LAUNCH();
+}
+
+extern "C" int di2p_gather_ragged_aug(const float* points, const float* intensity, const float* normals, const int32_t* offsets, const int32_t* idx,
+                                      const double* transform, int B, int n_out, unsigned long long seed, const unsigned long long* seed_dev,
+                                      int stream_id, double sigma, double clip, float* pc, float* intensity_out, float* sn, void* stream) {
+    DI2P_CHECK_ARG(B >= 0 && n_out >= 0, "bad sizes");
+    DI2P_CHECK_ARG(B == 0 || n_out == 0 || (points && offsets && idx && pc), "null pointer");
+    DI2P_CHECK_ARG(!intensity_out || intensity, "intensity_out needs intensity");
+    DI2P_CHECK_ARG(!sn || normals, "sn needs normals");
+    DI2P_CHECK_ARG(sigma >= 0.0 && sigma < 1e30 && clip > 0.0 && stream_id >= 0 && stream_id < (1 << 28), "jitter needs 0 <= sigma, clip > 0");
+    DI2P_CHECK_ARG(((uintptr_t)seed_dev & 7) == 0, "seed_dev must be 8-byte aligned");
+    if (B == 0 || n_out == 0) return 0;
+    hipLaunchKernelGGL(gather_ragged_kernel, dim3(di2p_cdiv(n_out, 256), B), dim3(256), 0, (hipStream_t)stream, points, intensity, normals, offsets,
+                       idx, transform, n_out, pc, intensity_out, sn, Jitter{seed, seed_dev, stream_id, sigma, clip});
     DI2P_RETURN_LAUNCH();
 }

@@ -159,18 +159,31 @@ class BatchPlan:
         self.fps_idx = [torch.empty((B, self.node_num), dtype=torch.int32, device=dev) for _ in range(2)]
         self.nodes = [torch.empty((B, 3, self.node_num), dtype=torch.float32, device=dev) for _ in range(2)]
 
-    def run(self, points, normals, offsets, seed, P=None):
+    def run(self, points, normals, offsets, seed, P=None, seed_dev=None, jitter=None):
         """points f32[>=total,4] (x, y, z, intensity), normals f32[>=total,3], offsets i32[B+1] (device; total <= cap, every frame
-        <= max_frame_points), P f64[B,4,4] or None -> (pc, intensity, sn, node_a, node_b), views of the plan's buffers."""
-        require_cuda(points, normals, offsets, P)
+        <= max_frame_points), P f64[B,4,4] or None -> (pc, intensity, sn, node_a, node_b), views of the plan's buffers.
+        seed_dev (i64[1] device, sample_prep.SamplePlan): every draw reads its seed from there when it runs, `seed` is ignored -- the same
+        draws as seed = seed_dev's value.  jitter (sigma, clip): Gaussian noise on points and normals before P (di2p_gather_ragged_aug)."""
+        require_cuda(points, normals, offsets, P, seed_dev)
         B, s = self.B, stream()
         call("di2p_voxel_down_sample", ptr(points), ptr(offsets), B, self.cap, self.max_src, float(self.voxel), MAX_EXTENT, 2 * self.n, ptr(normals),
              ptr(self.v_off), ptr(self.v_pts), ptr(self.v_int), ptr(self.v_nrm), None, ptr(self.status), ptr(self.ws), s)
-        call("di2p_random_choice_ragged", int(seed), 0, B, ptr(self.v_off), self.max_src, self.n, ptr(self.idx), ptr(self.choice_ws), s)
-        call("di2p_gather_ragged", ptr(self.v_pts), ptr(self.v_int), ptr(self.v_nrm), ptr(self.v_off), ptr(self.idx), ptr(P), B, self.n,
-             ptr(self.pc), ptr(self.intensity), ptr(self.sn), s)
+        if seed_dev is None:
+            call("di2p_random_choice_ragged", int(seed), 0, B, ptr(self.v_off), self.max_src, self.n, ptr(self.idx), ptr(self.choice_ws), s)
+        else:
+            call("di2p_random_choice_ragged_dseed", ptr(seed_dev), 0, B, ptr(self.v_off), self.max_src, self.n, ptr(self.idx), ptr(self.choice_ws), s)
+        if jitter is None:
+            call("di2p_gather_ragged", ptr(self.v_pts), ptr(self.v_int), ptr(self.v_nrm), ptr(self.v_off), ptr(self.idx), ptr(P), B, self.n,
+                 ptr(self.pc), ptr(self.intensity), ptr(self.sn), s)
+        else:
+            call("di2p_gather_ragged_aug", ptr(self.v_pts), ptr(self.v_int), ptr(self.v_nrm), ptr(self.v_off), ptr(self.idx), ptr(P), B, self.n,
+                 0 if seed_dev is not None else int(seed), ptr(seed_dev), 0, float(jitter[0]), float(jitter[1]), ptr(self.pc), ptr(self.intensity),
+                 ptr(self.sn), s)
         for k in range(2):          # node_a (stream 1), node_b (stream 2): prep.sample_nodes_device with preallocated buffers
-            call("di2p_random_choice", int(seed), k + 1, B, self.n, self.m, ptr(self.cand_idx[k]), ptr(self.cand_ws), s)
+            if seed_dev is None:
+                call("di2p_random_choice", int(seed), k + 1, B, self.n, self.m, ptr(self.cand_idx[k]), ptr(self.cand_ws), s)
+            else:
+                call("di2p_random_choice_dseed", ptr(seed_dev), k + 1, B, self.n, self.m, ptr(self.cand_idx[k]), ptr(self.cand_ws), s)
             call("di2p_gather_points", ptr(self.pc), ptr(self.cand_idx[k]), ptr(self.cand[k]), B, 3, self.n, self.m, s)
             call("di2p_farthest_point_sampling", ptr(self.cand[k]), None, ptr(self.fps_idx[k]), ptr(self.nodes[k]), B, self.m, self.node_num, s)
         return self.pc, self.intensity, self.sn, self.nodes[0], self.nodes[1]

@@ -295,3 +295,22 @@ def make_velodyne_scan(rng, beams=64, azimuths=1800, max_range=120.0, dropout=0.
     pts = dk * t[:, None]
     inten = np.clip(np.asarray(refl)[which] + rng.normal(0.0, 0.05, t.shape[0]), 0.0, 1.0)
     return np.concatenate([pts, inten[:, None]], axis=1).astype(np.float32)
+
+
+def make_camera_image(rng, H0=370, W0=1226):
+    """A synthetic camera frame u8[H0, W0, 3] (HWC, as np.load gives the loader's images) that reaches every branch of the colour code:
+    smooth gradients (every hue sector), per-pixel texture, saturated primaries, pure black / white, and exactly grey patches."""
+    y, x = np.mgrid[0:H0, 0:W0].astype(np.float64)
+    img = np.stack([127.5 + 127.5 * np.sin(x / 97.0 + y / 211.0), 127.5 + 127.5 * np.sin(x / 61.0 - y / 83.0 + 2.0),
+                    127.5 + 127.5 * np.cos(x / 173.0 + y / 47.0 + 4.0)], -1)
+    img += rng.normal(0.0, 12.0, img.shape)
+    img = np.clip(np.rint(img), 0, 255).astype(np.uint8)
+    ph, pw = max(H0 // 8, 1), max(W0 // 16, 1)
+    patches = [(255, 0, 0), (0, 255, 0), (0, 0, 255), (255, 255, 0), (0, 255, 255), (255, 0, 255), (0, 0, 0), (255, 255, 255), (128, 128, 128),
+               (37, 37, 37), (254, 255, 254), (1, 0, 0)]
+    for k, c in enumerate(patches):
+        r0, c0 = int(rng.integers(0, max(H0 - ph, 1))), int(rng.integers(0, max(W0 - pw, 1)))
+        img[r0:r0 + ph, c0:c0 + pw] = c
+    g = rng.integers(0, 256, (ph, pw)).astype(np.uint8)          # a textured but exactly grey patch: S = 0 pixels next to each other
+    img[H0 // 2:H0 // 2 + ph, W0 // 3:W0 // 3 + pw] = g[: img[H0 // 2:H0 // 2 + ph].shape[0], : img[:, W0 // 3:W0 // 3 + pw].shape[1], None]
+    return img

@@ -518,6 +518,56 @@ int di2p_group_max_backward(const float* dy, const int32_t* arg, float* dx, long
 int di2p_dropout_mask(unsigned long long seed, int stream_id, float p, long long n, uint8_t* mask, void* stream);
 int di2p_apply_mask(const float* x, const uint8_t* mask, float scale, float* y, long long n, void* stream);
 
+/* ---- training-sample preparation (csrc/sample_prep.hip; data/kitti_pc_img_pose_loader.py:108-156,199-232,326-384,439) -------------
+ * Everything here launches on `stream` without allocating or synchronising; B == 0 is a valid no-op.  Where a seed is taken, seed_dev
+ * (one 64-bit word in device memory, may be NULL) overrides `seed` and is read when the kernel runs, so a captured graph can be replayed
+ * with another seed.
+ * di2p_sample_draws: per frame b (a pure function of (seed, frame0 + b); Philox stream tag 4), from raw K f64[B,3,3], Pc f64[B,4,4] and
+ *   Pji f64[B,4,4] (NULL: identity):  ints i32[B,8] = {dx, dy, flip, op0, op1, op2, op3, hue shift}: the crop window (train: uniform in
+ *   [0, Ws - img_W] x [0, Hs - img_H]; else centred), the flip bit (train: probability 1/2), the order of the colour operations
+ *   (0 brightness, 1 contrast, 2 saturation, 3 hue; a uniform permutation) and uint8(hue * 255), computed from the fp64 hue factor: the
+ *   image path reads the shift from ints[7] only, factors[3] (the factor rounded to float32) is informative and may give a shift one
+ *   off at a truncation boundary;  factors f32[B,4] = brightness, contrast,
+ *   saturation, hue (uniform in color_range; 1, 1, 1, 0 outside train mode);  Pr f64[B,4,4] (train: Rz Ry Rx of uniform angles and a uniform
+ *   translation in +- amplitude, times diag(-1,1,1,1) when flipped; val_random_Ry: Ry in +- 2 pi whatever amplitude[4]; val: identity);  PrPcn = Pr . P_cam_nwu
+ *   f64[B,4,4] (the transform of the point kernels);  P = Pji . Pc . P_nwu_cam . Pr^-1 f32[B,3,4] (fp64, closed-form rigid inverse, rounded
+ *   once);  K_out f32[B,3,3] = K after crop-top, scale, crop-window (the flip does not touch K).
+ * di2p_image_prepare: images u8[B,H0,W0,3] -> out f32[B,3,img_H,img_W] (integral values 0..255) from the draw tables: top-row crop, the
+ *   rounded 2x2 mean (img_scale 0.5, even cropped source dimensions) or no resize (1.0), the crop window, the colour chain in the frame's
+ *   order with PIL's arithmetic, the flip.  geometry = 0: the source already is img_H x img_W, no crop / resize / flip; color = 0: no colour
+ *   chain.  reduce_blocks: workgroups per frame of the grey-sum launch (0: default; the sum is an integer, so any value gives the same bits).
+ *   workspace: di2p_image_prepare_workspace_bytes(B); afterwards its first B uint32 hold the grey sums the contrast operation used.
+ * di2p_transform_segments: points f32[total,4] (x, y, z, intensity) / normals f32[total,3] (may be NULL): segment s (rows seg_offsets[s] ..
+ *   seg_offsets[s+1]) by transforms f64[S,4,4] (points [R|t], normals R; fp64, rounded once), in place or into a second buffer.
+ * di2p_gather_ragged_aug: di2p_gather_ragged with clip(sigma * N(0,1), +-clip), rounded to float32, added to every gathered coordinate
+ *   and normal component before the transform; normals take the ROTATION of the transform only (the reference's homogeneous transform
+ *   would add a non-zero translation of Pr to them) (Philox stream tag 5; a function of (seed, stream_id, frame, output index, component)).
+ * di2p_random_choice_dseed / _ragged_dseed: di2p_random_choice / _ragged with the seed read from device memory. */
+typedef struct {
+    int mode;               /* 0 train, 1 val, 2 val_random_Ry */
+    int crop_top;           /* crop_original_top_rows */
+    double img_scale;       /* 0.5 or 1.0 */
+    int img_H, img_W;       /* the crop window */
+    int Hs, Ws;             /* the scaled image: (H0 - crop_top) * img_scale, W0 * img_scale */
+    double amplitude[6];    /* P_tx, P_ty, P_tz, P_Rx, P_Ry, P_Rz */
+    double color_range[8];  /* brightness, contrast, saturation, hue: lo, hi */
+} di2p_sample_opt_t;
+int di2p_sample_draws(unsigned long long seed, const unsigned long long* seed_dev, int B, int frame0, const di2p_sample_opt_t* opt,
+                      const double* K, const double* Pc, const double* Pji, int32_t* ints, float* factors, double* Pr, double* PrPcn,
+                      float* P, float* K_out, void* stream);
+long long di2p_image_prepare_workspace_bytes(int B);
+int di2p_image_prepare(const uint8_t* images, int B, int H0, int W0, const di2p_sample_opt_t* opt, const int32_t* ints,
+                       const float* factors, int geometry, int color, int reduce_blocks, float* out, void* workspace, void* stream);
+int di2p_transform_segments(const float* points, const float* normals, const int32_t* seg_offsets, const double* transforms, int S,
+                            int total, float* points_out, float* normals_out, void* stream);
+int di2p_gather_ragged_aug(const float* points, const float* intensity, const float* normals, const int32_t* offsets, const int32_t* idx,
+                           const double* transform, int B, int n_out, unsigned long long seed, const unsigned long long* seed_dev,
+                           int stream_id, double sigma, double clip, float* pc, float* intensity_out, float* sn, void* stream);
+int di2p_random_choice_dseed(const unsigned long long* seed_dev, int stream_id, int B, int n_src, int n_out, int32_t* idx_out,
+                             void* workspace, void* stream);
+int di2p_random_choice_ragged_dseed(const unsigned long long* seed_dev, int stream_id, int B, const int32_t* offsets, int max_src,
+                                    int n_out, int32_t* idx_out, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
