@@ -591,7 +591,7 @@ int conv_splits(int Cin, int Cout, int KH, int KW, int OW, long long opix, int t
     // number of 64x64 workgroups one frame contributes below which a 32-frame batch leaves CUs idle.
     const long long per_frame = di2p_cdiv(opix, 64) * (long long)di2p_cdiv(Cout, 64);
     const int T = Cin * KH * KW / 32;
-    const long long limit = di2p_opt(DI2P_OPT_CONV_SPLIT_BLOCKS);   // tuning knob (per-frame workgroups), default 32
+    constexpr long long limit = 32;   // per-frame workgroups
     if (per_frame >= limit || T < 24) return 1;
     return per_frame * 2 >= limit * 3 / 2 ? 2 : 3;
 }
@@ -612,8 +612,7 @@ int conv2d_impl(const float* x, const float* Wt, const float* scale, const float
     hipStream_t st = (hipStream_t)stream;
 #define DI2P_CONV(CFG) launch_conv<CFG>(x, Wt, scale, shift, residual, y, Cin, H, W, Cout, OH, OW, KH, KW, stride, pad, Ntot, relu, tap_major, st)
     // tile choice: K-step 32 when a tap holds whole 32-channel groups (halves barriers, doubles the prefetch
-    // distance); the largest tile that still yields >= ~2 workgroups per CU.  DI2P_CONV_CFG overrides (experiments).
-    const int force = (int)di2p_opt(DI2P_OPT_CONV_CFG);
+    // distance); the largest tile that still yields >= ~2 workgroups per CU.
     const bool k32 = tap_major && Cin % 32 == 0;
     const long long nb64x128 = (long long)di2p_cdiv(Ntot, 128) * di2p_cdiv(Cout, 64);
     const long long nb128x128 = (long long)di2p_cdiv(Ntot, 128) * di2p_cdiv(Cout, 128);
@@ -623,11 +622,8 @@ int conv2d_impl(const float* x, const float* Wt, const float* scale, const float
     else if (nb64x128 >= 512) choice = 1;
     else if (Cout >= 128 && nb128x64 >= 512) choice = 2;
     else choice = 0;
-    if (force >= 0) { choice = force % 10; if (choice >= 2 && Cout < 128) choice = 1; }
-    const bool use32 = k32 && (force < 0 || force >= 10);
     // the 7x7/2 stem (weights in their own order): row-decoding vector stager
-    if (!tap_major && KH == 7 && KW == 7 && stride == 2 && OW % 4 == 0 && Cout % 4 == 0 && ((uintptr_t)Wt & 15) == 0 &&
-        !di2p_opt(DI2P_OPT_CONV_NOVEC)) {
+    if (!tap_major && KH == 7 && KW == 7 && stride == 2 && OW % 4 == 0 && Cout % 4 == 0 && ((uintptr_t)Wt & 15) == 0) {
         using CfgS = TileCfg<2, 2, 1, 2, 32>;      // 64 x 128, B_PASSES = 4 (one mask per pass)
         const dim3 grid(di2p_cdiv(Ntot, CfgS::BN), di2p_cdiv(Cout, CfgS::BM));
         hipLaunchKernelGGL(conv2d_stem_kernel<CfgS>, grid, dim3(CfgS::THREADS), CfgS::LDS_FLOATS * sizeof(float), st, x, Wt, scale, shift,
@@ -635,19 +631,17 @@ int conv2d_impl(const float* x, const float* Wt, const float* scale, const float
         DI2P_RETURN_LAUNCH();
     }
     // vector stager: tap-major weights, 32-channel taps, whole 4-pixel groups per output row, 16-byte aligned weights
-    const bool novec = di2p_opt(DI2P_OPT_CONV_NOVEC) != 0;
-    const bool vec = !novec && use32 && OW % 4 == 0 && Cout % 4 == 0 && ((uintptr_t)Wt & 15) == 0 &&
+    const bool vec = k32 && OW % 4 == 0 && Cout % 4 == 0 && ((uintptr_t)Wt & 15) == 0 &&
                      ((stride == 1 && pad <= 1 && KW <= 2 * pad + 1 && W >= 4) || stride == 2);
-    if (vec && force < 0) choice = Cout <= 64 ? 1 : 0;   // measured: 64x64 tiles (more, smaller workgroups) win for Cout >= 128
+    if (vec) choice = Cout <= 64 ? 1 : 0;   // measured: 64x64 tiles (more, smaller workgroups) win for Cout >= 128
     int splits = vec ? conv_splits(Cin, Cout, KH, KW, OW, (long long)OH * OW, tap_major) : 1;
     if (splits > 1 && (!workspace || workspace_bytes < (long long)splits * Cout * Ntot * (long long)sizeof(float) || ((uintptr_t)workspace & 15))) splits = 1;
     if (splits > 1) choice = 0;
     float* part = (float*)workspace;
 #define DI2P_CONVV(CFG) launch_conv_vec<CFG>(x, Wt, scale, shift, residual, y, Cin, H, W, Cout, OH, OW, KH, KW, stride, pad, Ntot, relu, part, splits, st)
     if (vec) {
-        switch (choice) { case 3: DI2P_CONVV(CfgC128x128k32); break; case 2: DI2P_CONVV(CfgC128x64k32); break;
-                          case 1: DI2P_CONVV(CfgC64x128k32); break; default: DI2P_CONVV(CfgC64x64k32); }
-    } else if (use32) {
+        if (choice == 1) DI2P_CONVV(CfgC64x128k32); else DI2P_CONVV(CfgC64x64k32);
+    } else if (k32) {
         switch (choice) { case 3: DI2P_CONV(CfgC128x128k32); break; case 2: DI2P_CONV(CfgC128x64k32); break;
                           case 1: DI2P_CONV(CfgC64x128k32); break; default: DI2P_CONV(CfgC64x64k32); }
     } else {

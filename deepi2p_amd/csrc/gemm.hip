@@ -1370,14 +1370,8 @@ extern "C" int di2p_pointwise_gemm(const di2p_src_t* srcs, int n_src, const floa
         // 64 x 64 tiles for every layer.  Alone, the big point layers are a few per cent faster on 128 x 128 tiles, but in the 8-stream
         // pipeline the small tile (32 KB of LDS and 100 registers per workgroup instead of 64 KB and 200) packs better beside the pose
         // solver's workgroups and the family's own serial time drops too (2.05 -> 1.95 ms): +1.5-2 % frames/s (tools/sweep_packing.sh).
-        // DI2P_PW_CFG: 2 = 64x128, 3 = 128x128 tiles everywhere, 4 = 64x64 with K-step 16 (level with K-step 32); >= 16: 128x128 / 64x128 from that many workgroups on (the old rule: 1024)
-        const long long wg128 = (long long)B * di2p_cdiv(N, 128) * di2p_cdiv(M, 128);
-        const long long wg64x128 = (long long)B * di2p_cdiv(N, 128) * di2p_cdiv(M, 64);
-        const long long opt = di2p_opt(DI2P_OPT_PW_CFG);
-        const long long force = opt < 16 ? opt : 0, thr = opt >= 16 ? opt : (1ll << 62);
-        if (force == 4 && N % 64 == 0) launch_pw_vec<TileCfg<2, 2, 1, 1, 16>>(dense, s, Wt, Y, B, M, K, N, e, st);
-        else if (force == 3 || (!force && wg128 >= thr)) launch_pw_vec<TileCfg<2, 2, 2, 2, 32>>(dense, s, Wt, Y, B, M, K, N, e, st);
-        else if (force == 2 || (!force && wg64x128 >= thr) || N % 64 != 0) launch_pw_vec<TileCfg<2, 2, 1, 2, 32>>(dense, s, Wt, Y, B, M, K, N, e, st);
+        // (64 x 128 where N is no multiple of 64.)
+        if (N % 64 != 0) launch_pw_vec<TileCfg<2, 2, 1, 2, 32>>(dense, s, Wt, Y, B, M, K, N, e, st);
         else launch_pw_vec<TileCfg<2, 2, 1, 1, 32>>(dense, s, Wt, Y, B, M, K, N, e, st);
         DI2P_RETURN_LAUNCH();
     }

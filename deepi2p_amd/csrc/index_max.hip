@@ -134,11 +134,12 @@ int launch(const float* data, const int* index, int* max_idx, float* max_val, co
     if (B == 0 || C == 0 || K == 0) return 0;
     const size_t lds = (size_t)K * sizeof(unsigned long long);
     if (lds > 64 * 1024) { di2p_set_error("index_max: K=%d too large (max 8192)", K); return -1; }
-    // split N (u64 atomic merge + init / decode launches) only while the grid has fewer than ~1024 blocks (4 per CU) and every block
+    // split N (u64 atomic merge + init / decode launches) only while the grid has fewer than SPLIT_MAX_ROWS blocks (4 per CU) and every block
     // still streams >= 8 KiB: at B*C = 1024 rows one launch is faster than the split (cold: 20.9 vs 25.9 us at C = 32, B = 32)
     int S = 1;
     const long long rows = (long long)B * C;
-    while (rows * S < (long long)di2p_opt(DI2P_OPT_INDEX_MAX_ROWS) && (N / (S * 2)) >= 2048) S *= 2;
+    constexpr long long SPLIT_MAX_ROWS = 1024;
+    while (rows * S < SPLIT_MAX_ROWS && (N / (S * 2)) >= 2048) S *= 2;
     if (S > 1 && workspace == nullptr) S = 1;
     if (S == 1) {
         hipLaunchKernelGGL(index_max_kernel<false>, dim3(C, B, 1), dim3(256), lds, st, data, index, max_idx, max_val,

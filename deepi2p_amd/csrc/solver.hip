@@ -2618,9 +2618,7 @@ int launch_solve(const PT* points, const int* labels, const double* K, const dou
         hipLaunchKernelGGL(prepare_kernel<PT>, dim3(F), dim3(1024), 0, st, points, labels, N, ws.P, ws.NCMAX, keys, packed, boxes, counts, 0, K, H, W,
                            camf, (const int*)pw.flag);
     }
-    // DI2P_SOLVER_CFG=<waves per hypothesis><min waves/SIMD>, e.g. 43 (default); DI2P_SOLVER_NOCULL=1 classifies every
-    // cluster per point (the sums are bit-identical by construction: tests compare the two)
-    const int cfg = (int)di2p_opt(DI2P_OPT_SOLVER_CFG);
+    // DI2P_SOLVER_NOCULL=1 classifies every cluster per point (the sums are bit-identical by construction: tests compare the two)
     const int nocull = (di2p_opt(DI2P_OPT_SOLVER_NOCULL) ? 1 : 0) | (di2p_opt(DI2P_OPT_SOLVER_NOPREFILTER) ? 2 : 0) |
                        (di2p_opt(DI2P_OPT_SOLVER_NOCACHE) ? 4 : 0);   // bit 0: no cluster test, bit 1: no fp32 pre-filter, bit 2: no classification cache
     const dim3 grid(R * F);
@@ -2638,46 +2636,27 @@ int launch_solve(const PT* points, const int* labels, const double* K, const dou
     ka.cache = (CacheEnt*)(base + ws.off_cache);
     ka.camf = camf;
     ka.H = H; ka.W = W; ka.bnd = b; ka.NCMAX = ws.NCMAX; ka.nocull = nocull; ka.max_iter = max_iter; ka.F = F; ka.R = R; ka.N = N;
-    // the diagnostics (phase clocks, cluster / evaluation counters) are a separate instantiation: the production kernel carries none of it
-#define DI2P_LAUNCH_SOLVE_P(NPV, MW, WP, PEND, BUDGET, RESUME)                                                                   \
+    // the diagnostics (phase clocks, cluster / evaluation counters) are a separate instantiation: the production kernel carries none of it.
+    // It exists for the first tier only and runs at <= 3 waves per SIMD: at 128 registers its timers push it into scratch and distort the phases
+#define DI2P_LAUNCH_SOLVE(NPV, MW, WP, PROFILE, PEND, BUDGET, RESUME)                                                            \
     do {                                                                                                                         \
         ka.pending = PEND; ka.budget = BUDGET; ka.resume = RESUME;                                                               \
-        /* the instrumented build runs at <= 3 waves per SIMD: at 128 registers its timers push it into scratch and distort the phases */ \
-        if (g_prof) hipLaunchKernelGGL((solve_kernel<NPV, PT, (MW > 3 ? 3 : MW), WP, true>), grid, dim3(WP * 64), 0, st, ka);    \
-        else hipLaunchKernelGGL((solve_kernel<NPV, PT, MW, WP, false>), grid, dim3(WP * 64), lds_pad, st, ka);                   \
+        hipLaunchKernelGGL((solve_kernel<NPV, PT, MW, WP, PROFILE>), grid, dim3(WP * 64), 0, st, ka);                            \
     } while (0)
-#define DI2P_LAUNCH_SOLVE(NPV, MW, WP, PEND, BUDGET, RESUME)                                                                     \
-    do {                                                                                                                         \
-        ka.pending = PEND; ka.budget = BUDGET; ka.resume = RESUME;                                                               \
-        hipLaunchKernelGGL((solve_kernel<NPV, PT, MW, WP, false>), grid, dim3(WP * 64), lds_pad, st, ka);                        \
-    } while (0)
-    // unused dynamic LDS: caps the solver's workgroups per CU (160 KB / (static + pad)) so that registers and LDS stay free for
-    // the MFMA kernels of the other streams -- the solver needs VALU issue slots, they need the matrix pipe
-    const size_t lds_pad = (size_t)di2p_opt(DI2P_OPT_SOLVER_LDS_PAD);
+    // waves per hypothesis x minimum waves per SIMD of the 2-D first tier: compile-time (tools/build_solver_variant.py builds others; DESIGN.md
+    // section 4 lists what each one measured)
+    constexpr int MINW = DI2P_SOLVER_DEFAULT_MINW, WPH = DI2P_SOLVER_DEFAULT_WPH;
     int* pend1 = tier > 0 ? pending : nullptr;
     if (is_2d) {
-        switch (cfg) {
-#ifndef DI2P_SOLVER_MIN_INSTANCES
-            // variants kept for measurements (DESIGN.md section 4 lists what each one measured); the diagnostics build exists for the default only
-            case 42: DI2P_LAUNCH_SOLVE(4, 2, 4, pend1, tier, 0); break;
-            case 43: DI2P_LAUNCH_SOLVE(4, 3, 4, pend1, tier, 0); break;
-            case 23: DI2P_LAUNCH_SOLVE(4, 3, 2, pend1, tier, 0); break;
-            case 24: DI2P_LAUNCH_SOLVE(4, 4, 2, pend1, tier, 0); break;
-            case 14: DI2P_LAUNCH_SOLVE(4, 4, 1, pend1, tier, 0); break;
-            case 83: DI2P_LAUNCH_SOLVE(4, 3, 8, pend1, tier, 0); break;
-            case 84: DI2P_LAUNCH_SOLVE(4, 4, 8, pend1, tier, 0); break;
-#endif
-            default: DI2P_LAUNCH_SOLVE_P(4, DI2P_SOLVER_DEFAULT_MINW, DI2P_SOLVER_DEFAULT_WPH, pend1, tier, 0); break;
-        }
-#ifndef DI2P_SOLVER_MIN_INSTANCES
-        if (tier > 0) DI2P_LAUNCH_SOLVE(4, 3, 12, pending, 0, 1);
+        if (g_prof) DI2P_LAUNCH_SOLVE(4, (MINW > 3 ? 3 : MINW), WPH, true, pend1, tier, 0);
+        else DI2P_LAUNCH_SOLVE(4, MINW, WPH, false, pend1, tier, 0);
+        if (tier > 0) DI2P_LAUNCH_SOLVE(4, 3, 12, false, pending, 0, 1);
     } else {
-        DI2P_LAUNCH_SOLVE_P(6, 2, 4, pend1, tier, 0);
-        if (tier > 0) DI2P_LAUNCH_SOLVE(6, 2, 8, pending, 0, 1);
-#endif
+        if (g_prof) DI2P_LAUNCH_SOLVE(6, 2, 4, true, pend1, tier, 0);
+        else DI2P_LAUNCH_SOLVE(6, 2, 4, false, pend1, tier, 0);
+        if (tier > 0) DI2P_LAUNCH_SOLVE(6, 2, 8, false, pending, 0, 1);
     }
 #undef DI2P_LAUNCH_SOLVE
-#undef DI2P_LAUNCH_SOLVE_P
     return 0;
 }
 

@@ -26,11 +26,11 @@ namespace {
 constexpr int WG_TILES = 32;
 typedef float f32x4 __attribute__((ext_vector_type(4)));      // a plain vector type: its loads / stores stay register values (no memcpy)
 
-template <int COB, bool DB, int KC>
+template <int COB, int KC>
 struct WinoLds {
     static constexpr int U_FLOATS = 16 * KC * COB, V_FLOATS = 16 * KC * WG_TILES;
     static constexpr int STAGE = U_FLOATS + V_FLOATS;
-    static constexpr int TOTAL = (DB ? 2 : 1) * STAGE;
+    static constexpr int TOTAL = 2 * STAGE;      // double buffered
 };
 
 // U[xi][ci][co] = (G g G^T)[xi] of weight[co][ci][3][3];  G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]]
@@ -63,14 +63,13 @@ __global__ __launch_bounds__(256) void wino_weight_kernel(const float* __restric
     }
 }
 
-// DB: operand panels double buffered (one barrier per K-step, 64 KB at COB 32: two workgroups per CU) or single buffered (two
-// barriers per K-step, 32 KB: four workgroups per CU cover each other's barriers and the grid quantises finer)
+// The operand panels are double buffered: one barrier per K-step (single buffered, two barriers per K-step at half the LDS, measured slower).
 // KC: input channels per K-step (8: every thread transforms one tile-channel per step; 4: half the panel bytes, waves 0-1 transform)
-template <int COB, bool DB, int KC>
+template <int COB, int KC>
 __global__ __launch_bounds__(256) void wino_conv_kernel(const float* __restrict__ x, const float* __restrict__ U, const float* __restrict__ scale,
                                                         const float* __restrict__ shift, const float* __restrict__ residual, float* __restrict__ y,
                                                         int Cin, int H, int W, int Cout, int TH, int TW, int total_tiles, int n_tb, int n_cb, int relu, int by_co) {
-    using L = WinoLds<COB, DB, KC>;
+    using L = WinoLds<COB, KC>;
     constexpr int UP = (16 * KC * COB / 4 + 255) / 256;      // 16-byte U loads per thread and K-step
     constexpr int MT = COB / 32;                 // MFMA row tiles per xi
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -178,7 +177,7 @@ __global__ __launch_bounds__(256) void wino_conv_kernel(const float* __restrict_
     lstore(0);
     __syncthreads();
     for (int t = 0; t < T; ++t) {
-        const int buf = DB ? (t & 1) : 0;
+        const int buf = t & 1;
         if (t + 1 < T) gload(t + 1);
         const float* Us = lds + buf * L::STAGE;
         const float* Vs = Us + L::U_FLOATS;
@@ -199,13 +198,8 @@ __global__ __launch_bounds__(256) void wino_conv_kernel(const float* __restrict_
                 for (int h = 0; h < MT; ++h) acc[j][h] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kk][h], bv[kk], acc[j][h], 0, 0, 0);
         }
         DI2P_MFMA_END();
-        if (DB) {
-            if (t + 1 < T) lstore(buf ^ 1);
-            __syncthreads();
-        } else {
-            __syncthreads();
-            if (t + 1 < T) { lstore(0); __syncthreads(); }
-        }
+        if (t + 1 < T) lstore(buf ^ 1);
+        __syncthreads();
     }
 
     // ---- epilogue: per pass q the 8 output channels {8q .. 8q+7} of every 32-row MFMA tile (accumulator registers 4q .. 4q+3)
@@ -473,25 +467,24 @@ extern "C" int di2p_conv3x3_winograd(const float* x, const float* U, const float
     const long long opt = di2p_opt(DI2P_OPT_WINO_COB);
     const bool cob64 = opt ? (opt == 64 && Cout % 64 == 0) : (Cout % 64 == 0 && (long long)n_tb * (Cout / 64) >= 768);
     hipStream_t st = (hipStream_t)stream;
-    const bool db = di2p_opt(DI2P_OPT_WINO_DB) != 0;
-    const int map_opt = (int)di2p_opt(DI2P_OPT_WINO_MAP);      // 0: automatic, 1: tile blocks over the XCDs, 2: co-blocks over the XCDs
-#define DI2P_WINO_LAUNCH(COBV, DBV, KCV)                                                                                                     \
+#define DI2P_WINO_LAUNCH(COBV, KCV)                                                                                                          \
     do {                                                                                                                                     \
         const int n_cb = Cout / COBV;                                                                                                        \
-        /* the co-block mapping needs n_cb % 8 == 0 (the kernel divides by n_cb / 8): the knob cannot force it elsewhere */                 \
-        const int by_co = n_cb % 8 == 0 && (map_opt ? map_opt == 2 : (long long)16 * Cin * Cout * 4 > (2ll << 20));                           \
+        /* co-blocks over the XCDs where U is larger than 2 MB (else tile blocks); needs n_cb % 8 == 0 (the kernel divides by n_cb / 8) */  \
+        const int by_co = n_cb % 8 == 0 && (long long)16 * Cin * Cout * 4 > (2ll << 20);                                                     \
         const int grid = by_co ? n_cb * n_tb : di2p_cdiv(n_tb, 8) * 8 * n_cb;                                                                \
-        const size_t lds = WinoLds<COBV, DBV, KCV>::TOTAL * sizeof(float);                                                                        \
-        if (di2p_allow_dynamic_lds((const void*)wino_conv_kernel<COBV, DBV, KCV>, lds, __func__)) return -1;                                      \
-        hipLaunchKernelGGL((wino_conv_kernel<COBV, DBV, KCV>), dim3(grid), dim3(256), lds, st, x, U, scale, shift, residual, y, Cin, H, W, Cout, \
+        const size_t lds = WinoLds<COBV, KCV>::TOTAL * sizeof(float);                                                                        \
+        if (di2p_allow_dynamic_lds((const void*)wino_conv_kernel<COBV, KCV>, lds, __func__)) return -1;                                      \
+        hipLaunchKernelGGL((wino_conv_kernel<COBV, KCV>), dim3(grid), dim3(256), lds, st, x, U, scale, shift, residual, y, Cin, H, W, Cout, \
                            TH, TW, (int)total, n_tb, n_cb, relu, by_co);                                                                     \
     } while (0)
     const long long reg_opt = di2p_opt(DI2P_OPT_WINO_REG);      // 0: automatic, 1: LDS-panel kernel, 2: register-resident, 4 waves, 3: 2 waves
-    // automatic: the register-resident kernel wherever its 64-tile workgroups number at least 256 (ResNet stages 1-3).  Alone, the LDS-panel
+    // automatic: the register-resident kernel wherever its 64-tile workgroups number at least REG_MIN_WGS (ResNet stages 1-3).  Alone, the LDS-panel
     // kernel is level or ahead from stage 2 on (stage 3: 85 vs 93 us), but in the 8-stream pipeline the register-resident kernel's
     // 16 KB of LDS per workgroup (against 32-64 KB) lets it share a CU with the pose solver's workgroups: +2.8 % frames/s with the
-    // threshold at 300 instead of 1024 (tools/sweep_wino_reg_min.sh); at the 512-channel stage (192 workgroups) the LDS-panel kernel stays
-    const bool reg_auto = reg_opt == 0 && (long long)di2p_cdiv(total, 64) * (Cout / 32) >= di2p_opt(DI2P_OPT_WINO_REG_MIN);
+    // threshold at 300 instead of 1024 (round 3); at the 512-channel stage (192 workgroups) the LDS-panel kernel stays
+    constexpr long long REG_MIN_WGS = 256;      // all but the 512-channel stage
+    const bool reg_auto = reg_opt == 0 && (long long)di2p_cdiv(total, 64) * (Cout / 32) >= REG_MIN_WGS;
     if ((reg_opt >= 2 || reg_auto) && Cin % 4 == 0) {
         const int nw = reg_opt == 3 ? 2 : 4;
         const int n_tb_r = di2p_cdiv(total, nw * 16), n_cb = Cout / 32;
@@ -503,9 +496,9 @@ extern "C" int di2p_conv3x3_winograd(const float* x, const float* U, const float
     const long long kc_opt = di2p_opt(DI2P_OPT_WINO_KC);
     const bool kc4 = kc_opt ? kc_opt == 4 : Cin <= 256;      // measured in the pipeline: K-step 4 wins up to 256 input channels, 8 at 512
     if (cob64) {
-        if (!db) DI2P_WINO_LAUNCH(64, false, 8); else if (kc4) DI2P_WINO_LAUNCH(64, true, 4); else DI2P_WINO_LAUNCH(64, true, 8);
+        if (kc4) DI2P_WINO_LAUNCH(64, 4); else DI2P_WINO_LAUNCH(64, 8);
     } else {
-        if (!db) DI2P_WINO_LAUNCH(32, false, 8); else if (kc4) DI2P_WINO_LAUNCH(32, true, 4); else DI2P_WINO_LAUNCH(32, true, 8);
+        if (kc4) DI2P_WINO_LAUNCH(32, 4); else DI2P_WINO_LAUNCH(32, 8);
     }
 #undef DI2P_WINO_LAUNCH
     DI2P_RETURN_LAUNCH();

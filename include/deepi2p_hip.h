@@ -23,8 +23,12 @@ extern "C" {
 
 const char* di2p_last_error(void);
 int di2p_version(void);
-/* Tuning / test knobs, cached in the library (initialised once from the environment variable DI2P_<NAME>): "conv_nosplit",
- * "conv_split_blocks", "conv_novec", "conv_cfg", "conv_depth1", "conv_x3", "conv_x3_cfg", "head_x3", "head_x3_tab", "stem_x3", "pw_x3", "pw_novec", "solver_cfg", "solver_nocull", "solver_noprefilter", "solver_tier_sweeps".
+/* Tuning / test knobs, cached in the library (initialised once from the environment variable DI2P_<NAME>; what each one does is written
+ * on its entry of the one table that defines them, DI2P_OPTIONS in deepi2p_amd/csrc/common.h):
+ *   "conv_nosplit", "conv_depth1", "pw_novec", "solver_nocull", "solver_noprefilter", "solver_tier_sweeps", "wino_cob", "conv_nowinograd",
+ *   "wino_kc", "conv_nostem", "wino_reg", "solver_nocache", "solver_prep_single", "solver_prep_bitonic", "pw_x3", "pw_nochain", "head_reg",
+ *   "conv_s2scalar", "conv_x3", "conv_x3_cfg", "head_x3", "head_x3_tab", "stem_x3", "bn_unfused", "pw_x3_planes", "conv_dgrad_dense",
+ *   "rc_tile64".
  * set: 0, or -1 for an unknown name; get: the value, or -1 for an unknown name. */
 int di2p_set_option(const char* name, long long value);
 long long di2p_get_option(const char* name);

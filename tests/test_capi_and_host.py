@@ -33,6 +33,34 @@ def test_library_exports_every_declared_symbol():
     assert l.di2p_solve_workspace_bytes(32, 60, 20480) >= 32 * 20480 * 32
 
 
+def test_documented_knobs_are_the_knob_table():
+    """csrc/common.h's DI2P_OPTIONS is the one definition of the knobs; the lists in include/deepi2p_hip.h and INTEGRATION.md name exactly
+    its entries, and the library knows each of them under that name."""
+    table = re.findall(r'\bX\((\w+), "(\w+)", "(\w+)", (-?\d+)\)', open(os.path.join(ROOT, "deepi2p_amd", "csrc", "common.h")).read())
+    names = [name for _, name, _, _ in table]
+    assert len(names) >= 20 and len(set(names)) == len(names)
+    for ident, name, env, _ in table:
+        assert name == ident.lower() and env == "DI2P_" + ident
+    header = open(os.path.join(ROOT, "include", "deepi2p_hip.h")).read()
+    comment = header[header.index("/* Tuning / test knobs"):header.index("int di2p_set_option(")]
+    assert sorted(re.findall(r'"(\w+)"', comment)) == sorted(names)
+    guide = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    listed = guide[guide.index("The knobs ("):]
+    listed = listed[listed.index("\n") + 1:listed.index(".\n")]
+    assert sorted(re.findall(r"`(\w+)`", listed)) == sorted(names)
+    # in a thread of its own: the unknown name below sets di2p_last_error, which is per thread
+    import concurrent.futures
+    from deepi2p_amd import _lib
+
+    def known():
+        for name in names:
+            _lib.set_option(name, _lib.get_option(name))
+        with pytest.raises(_lib.DeepI2PHipError, match="unknown option"):
+            _lib.set_option("no_such_knob", 1)
+    with concurrent.futures.ThreadPoolExecutor(1) as ex:
+        ex.submit(known).result()
+
+
 def test_argument_errors_are_reported_not_crashed():
     from deepi2p_amd import _lib
     l = _lib.load()

@@ -6,10 +6,10 @@ import threading
 import pytest
 
 
-def test_head_labels_packed_bytes_and_abi_version_8():
+def test_head_labels_packed_bytes_and_abi_version():
     from deepi2p_amd import _lib
     lib = _lib.load()
-    assert lib.di2p_version() == 8
+    assert lib.di2p_version() == 9
     # [ceil(P / 32) row tiles][K / 16 K-steps][3 planes][64 lanes] x 16 B
     assert lib.di2p_head_labels_x3_packed_bytes(256, 256) == 8 * 16 * 3 * 1024
     assert lib.di2p_head_labels_x3_packed_bytes(256, 82) == 3 * 16 * 3 * 1024

@@ -110,7 +110,7 @@ if sc:
 wino_counters_txt = ("* `%s_winograd_counters.txt` -- `tools/prof_winograd.sh`: SQ / TA / TCP / TCC counters of `wino_conv_kernel` on the stage-3 shape.\n" % TAG
                      if os.path.exists(P + TAG + "_winograd_counters.txt") else "")
 extra_txt = ""
-if os.path.exists(P + TAG + "_EXTRA.md"):        # the round's A/B calls (tools/oneoff/<tag>_call*.sh), described by hand
+if os.path.exists(P + TAG + "_EXTRA.md"):        # the round's A/B calls, described by hand
     extra_txt = open(P + TAG + "_EXTRA.md").read().rstrip() + "\n"
 txt = f"""# Round-{RN} profiles (1x MI355X, ROCm 7.2)
 
