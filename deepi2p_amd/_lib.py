@@ -49,6 +49,8 @@ class HeadLabelsX3T(ctypes.Structure):      # di2p_head_labels_x3_t
 class SampleOptT(ctypes.Structure):      # di2p_sample_opt_t
     _fields_ = [("mode", c_int), ("crop_top", c_int), ("img_scale", c_double), ("img_H", c_int), ("img_W", c_int), ("Hs", c_int), ("Ws", c_int),
                 ("amplitude", c_double * 6), ("color_range", c_double * 8)]
+    # Python-side companions of the block for the _ds entry points (not part of the C struct): sample_prep.option_block sets them
+    dataset, crop_bottom, resize_k, max_range = 0, 0, 0, 0.0
 
 
 SRC_DENSE, SRC_GATHER, SRC_GROUP = 0, 1, 2
@@ -143,6 +145,11 @@ _SIGS = {
     "di2p_gather_ragged_aug": [c_void_p] * 6 + [c_int, c_int, ctypes.c_ulonglong, c_void_p, c_int, c_double, c_double] + [c_void_p] * 4,
     "di2p_random_choice_dseed": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "di2p_random_choice_ragged_dseed": [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "di2p_range_shuffle": [c_void_p, c_void_p, c_int, c_int, c_int, c_double, ctypes.c_ulonglong] + [c_void_p] * 6,
+    "di2p_gather_ragged_aug_intensity": [c_void_p] * 5 + [c_int, c_int, ctypes.c_ulonglong, c_void_p, c_int, c_double, c_double] + [c_void_p] * 3,
+    "di2p_sample_draws_ds": [ctypes.c_ulonglong, c_void_p, c_int, c_int, ctypes.POINTER(SampleOptT), c_int] + [c_void_p] * 10,
+    "di2p_image_prepare_ds": [c_void_p, c_int, c_int, c_int, ctypes.POINTER(SampleOptT), c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                              c_void_p, c_void_p, c_void_p],
 }
 _WS_SIGS = {        # <name>_workspace_bytes helpers returning long long
     "di2p_channel_reduce_workspace_bytes": [c_int] * 3,

@@ -12,6 +12,12 @@
 // Colour arithmetic is PIL's, value for value (tests pin it against PIL): Image.blend in float32 with a separately rounded multiply and
 // add (this file is built with FMA contraction off, and the blend spells the roundings out), clip, truncate; RGB <-> HSV as Convert.c does.
 // The resize is the rounded 2x2 mean, which is what OpenCV's INTER_LINEAR gives at an exact factor of two (restated, not pinned).
+//
+// Oxford / nuScenes loaders (data/oxford_pc_img_pose_loader.py:220-380, data/nuscenes_pc_img_pose_loader.py:273-408; the _ds entry points):
+// the same kernels with a bottom-row crop, the centre-pick resize 1/k for odd k (with an explicit dsize OpenCV's scale is src / dst = k exactly,
+// the sample coordinate (d + 0.5) k - 0.5 is the integer k d + (k - 1) / 2, the bilinear weights are exactly (1, 0) and the fixed-point path
+// returns the pixel itself -- derived, not checked against OpenCV), a per-frame colour enable (one further uniform, block 7), no flip,
+// Pr applied in the frame the cloud is stored in, P = P_cam_pc . Pr^-1, and val_random_Ry about the data set's axis.
 #include "common.h"
 #include "philox.h"
 
@@ -19,6 +25,7 @@ namespace {
 
 enum { OP_BRIGHTNESS = 0, OP_CONTRAST = 1, OP_SATURATION = 2, OP_HUE = 3 };
 enum { I_DX = 0, I_DY = 1, I_FLIP = 2, I_OP0 = 3, I_HUE_SHIFT = 7, INTS = 8 };
+enum { DS_KITTI = 0, DS_OXFORD = 1, DS_NUSCENES = 2 };
 
 __constant__ unsigned char kPerms[24][4] = {{0, 1, 2, 3}, {0, 1, 3, 2}, {0, 2, 1, 3}, {0, 2, 3, 1}, {0, 3, 1, 2}, {0, 3, 2, 1}, {1, 0, 2, 3}, {1, 0, 3, 2},
                                             {1, 2, 0, 3}, {1, 2, 3, 0}, {1, 3, 0, 2}, {1, 3, 2, 0}, {2, 0, 1, 3}, {2, 0, 3, 1}, {2, 1, 0, 3}, {2, 1, 3, 0},
@@ -38,12 +45,15 @@ __global__ __launch_bounds__(64) void sample_draws_kernel(unsigned long long see
                                                           di2p_sample_opt_t o, const double* __restrict__ K, const double* __restrict__ Pc,
                                                           const double* __restrict__ Pji, int* __restrict__ ints, float* __restrict__ factors,
                                                           double* __restrict__ Pr_out, double* __restrict__ PrPcn_out, float* __restrict__ P_out,
-                                                          float* __restrict__ K_out) {
+                                                          float* __restrict__ K_out, int dataset, int* __restrict__ enable,
+                                                          float* __restrict__ t_ij) {
+    // dataset DS_KITTI: di2p_sample_draws.  DS_OXFORD / DS_NUSCENES (di2p_sample_draws_ds): the same uniforms for the same items, no flip, the
+    // colour enable from u[14] (block 7, which KITTI frames never draw), Pc is P_cam_pc and the cloud stays in the frame it is stored in
     const int j = blockIdx.x * 64 + threadIdx.x;
     if (j >= B) return;
     if (seed_dev) seed = *seed_dev;
-    double u[14];
-    for (int k = 0; k < 7; ++k) {
+    double u[16];
+    for (int k = 0; k < (dataset == DS_KITTI ? 7 : 8); ++k) {
         const U4 r = philox4x32_10(U4{(unsigned)(frame0 + j), (unsigned)k, 0u, 4u}, (unsigned)seed, (unsigned)(seed >> 32));
         u[2 * k] = u53(r.x, r.y);
         u[2 * k + 1] = u53(r.z, r.w);
@@ -54,7 +64,7 @@ __global__ __launch_bounds__(64) void sample_draws_kernel(unsigned long long see
         const int nx = o.Ws - o.img_W + 1, ny = o.Hs - o.img_H + 1;
         dx = min((int)(u[0] * nx), nx - 1);
         dy = min((int)(u[1] * ny), ny - 1);
-        flip = u[2] > 0.5 ? 1 : 0;
+        flip = dataset == DS_KITTI && u[2] > 0.5 ? 1 : 0;
         perm = min((int)(u[3] * 24), 23);
         for (int k = 0; k < 4; ++k) f[k] = o.color_range[2 * k] + (o.color_range[2 * k + 1] - o.color_range[2 * k]) * u[4 + k];
         for (int k = 0; k < 3; ++k) t[k] = o.amplitude[k] * (2.0 * u[8 + k] - 1.0);
@@ -64,13 +74,16 @@ __global__ __launch_bounds__(64) void sample_draws_kernel(unsigned long long see
         dy = (o.Hs - o.img_H) / 2;
         // val_random_Ry: generate_random_transform(0, 0, 0, 0, 2 pi, 0) -- the amplitude is fixed, P_Ry_amplitude is not read (:367-368);
         // the angle comes from u[12], the uniform that is the Ry draw in train mode too
-        if (o.mode == 2) ang[1] = (2.0 * 3.141592653589793) * (2.0 * u[12] - 1.0);
+        // (:302-304 Oxford: about y as KITTI; nuScenes :339-341: about z, from u[13], the Rz draw of train mode)
+        const int axis = dataset == DS_NUSCENES ? 2 : 1;
+        if (o.mode == 2) ang[axis] = (2.0 * 3.141592653589793) * (2.0 * u[11 + axis] - 1.0);
     }
     int* I = ints + INTS * (long long)j;
     I[I_DX] = dx; I[I_DY] = dy; I[I_FLIP] = flip;
     for (int k = 0; k < 4; ++k) I[I_OP0 + k] = kPerms[perm][k];
     I[I_HUE_SHIFT] = (int)(f[3] * 255.0) & 255;          // np.uint8(hue_factor * 255): truncation, then wrap-around
     for (int k = 0; k < 4; ++k) factors[4 * (long long)j + k] = (float)f[k];
+    if (enable) enable[j] = o.mode == 0 && u[14] > 0.5 ? 1 : 0;          // if random.random() > 0.5: augment_img
 
     // Pr = [Rz Ry Rx | t] (augmentation.angles2rotation_matrix), times diag(-1, 1, 1, 1) when flipped
     const double cx = cos(ang[0]), sx = sin(ang[0]), cy = cos(ang[1]), sy = sin(ang[1]), cz = cos(ang[2]), sz = sin(ang[2]);
@@ -89,17 +102,25 @@ __global__ __launch_bounds__(64) void sample_draws_kernel(unsigned long long see
         for (int c = 0; c < 3; ++c) Pinv[4 * r + c] = Pr[4 * c + r];
         Pinv[4 * r + 3] = -((Pr[r] * t[0] + Pr[4 + r] * t[1]) + Pr[8 + r] * t[2]);
     }
-    matmul4(Pr, Pcn, A);
-    for (int k = 0; k < 16; ++k) {
-        Pr_out[16 * (long long)j + k] = Pr[k];
-        PrPcn_out[16 * (long long)j + k] = A[k];
+    if (dataset == DS_KITTI) {
+        matmul4(Pr, Pcn, A);
+        for (int k = 0; k < 16; ++k) {
+            Pr_out[16 * (long long)j + k] = Pr[k];
+            PrPcn_out[16 * (long long)j + k] = A[k];
+        }
+        matmul4(Pnc, Pinv, A);
+        matmul4(Pc + 16 * (long long)j, A, Bm);
+        if (Pji) matmul4(Pji + 16 * (long long)j, Bm, C);
+        for (int k = 0; k < 12; ++k) P_out[12 * (long long)j + k] = (float)(Pji ? C[k] : Bm[k]);
+    } else {          // the point kernels' transform is Pr itself; P = P_cam_pc . Pr^-1, t_ij = P_cam_pc[:3, 3]
+        for (int k = 0; k < 16; ++k) Pr_out[16 * (long long)j + k] = Pr[k];
+        matmul4(Pc + 16 * (long long)j, Pinv, Bm);
+        for (int k = 0; k < 12; ++k) P_out[12 * (long long)j + k] = (float)Bm[k];
+        if (t_ij) for (int r = 0; r < 3; ++r) t_ij[3 * (long long)j + r] = (float)Pc[16 * (long long)j + 4 * r + 3];
     }
-    matmul4(Pnc, Pinv, A);
-    matmul4(Pc + 16 * (long long)j, A, Bm);
-    if (Pji) matmul4(Pji + 16 * (long long)j, Bm, C);
-    for (int k = 0; k < 12; ++k) P_out[12 * (long long)j + k] = (float)(Pji ? C[k] : Bm[k]);
 
-    // K': crop the top rows, scale (K[2][2] back to 1), crop the window.  The flip does not touch K (neither does the reference).
+    // K': crop the top rows, scale (K[2][2] back to 1), crop the window.  The flip does not touch K (neither does the reference), and
+    // neither does Oxford's bottom-row crop (its crop_top is 0: K - 0.0 is K).
     double Kc[9];
     for (int k = 0; k < 9; ++k) Kc[k] = K[9 * (long long)j + k];
     Kc[5] -= (double)o.crop_top;
@@ -111,25 +132,28 @@ __global__ __launch_bounds__(64) void sample_draws_kernel(unsigned long long see
 }
 
 // ---------------------------------------------------------------- b. image path
-struct ImgGeom { int H0, W0, top, half, H, W, max_dx, max_dy; };
+struct ImgGeom { int H0, W0, top, half, H, W, max_dx, max_dy, k, noflip; };          // k: centre pick of k x k (1: the pixel itself)
 
-struct FrameDraw { int dx, dy, flip, op[4], shift; float f[3]; };
+struct FrameDraw { int dx, dy, flip, op[4], shift; float f[3]; int color; };
 
-__device__ __forceinline__ FrameDraw load_draw(const int* __restrict__ ints, const float* __restrict__ factors, int b, const ImgGeom& g, int geometry) {
-    FrameDraw d{0, 0, 0, {0, 1, 2, 3}, 0, {1.0f, 1.0f, 1.0f}};
+__device__ __forceinline__ FrameDraw load_draw(const int* __restrict__ ints, const float* __restrict__ factors, const int* __restrict__ enable, int b,
+                                               const ImgGeom& g, int geometry) {
+    FrameDraw d{0, 0, 0, {0, 1, 2, 3}, 0, {1.0f, 1.0f, 1.0f}, 1};
     if (!ints || !factors) return d;      // neither geometry nor colour: plain uint8 HWC -> float32 CHW
     const int* I = ints + INTS * (long long)b;
     // clamped: a caller-supplied table can never move the window outside the image
     d.dx = geometry ? min(max(I[I_DX], 0), g.max_dx) : 0;
     d.dy = geometry ? min(max(I[I_DY], 0), g.max_dy) : 0;
-    d.flip = geometry ? (I[I_FLIP] & 1) : 0;
+    d.flip = geometry && !g.noflip ? (I[I_FLIP] & 1) : 0;
+    d.color = enable ? (enable[b] != 0) : 1;
     for (int k = 0; k < 4; ++k) d.op[k] = I[I_OP0 + k] & 3;
     d.shift = I[I_HUE_SHIFT] & 255;
     for (int k = 0; k < 3; ++k) d.f[k] = factors[4 * (long long)b + k];
     return d;
 }
 
-// pixel (y, x) of the crop window before the flip: the rounded 2x2 mean of the source (scale 0.5) or the source pixel (scale 1)
+// pixel (y, x) of the crop window before the flip: the rounded 2x2 mean of the source (scale 0.5), the source pixel (scale 1) or the centre
+// pixel of the k x k block (scale 1 / k, k odd)
 __device__ __forceinline__ void fetch(const unsigned char* __restrict__ img, const ImgGeom& g, const FrameDraw& d, int y, int x, int c[3]) {
     const int sy = d.dy + y, sx = d.dx + x;
     if (g.half) {
@@ -137,7 +161,8 @@ __device__ __forceinline__ void fetch(const unsigned char* __restrict__ img, con
         const unsigned char* r1 = r0 + (long long)g.W0 * 3;
         for (int k = 0; k < 3; ++k) c[k] = ((int)r0[k] + (int)r0[3 + k] + (int)r1[k] + (int)r1[3 + k] + 2) >> 2;
     } else {
-        const unsigned char* r0 = img + ((long long)(g.top + sy) * g.W0 + sx) * 3;
+        const int h = (g.k - 1) >> 1;
+        const unsigned char* r0 = img + ((long long)(g.top + g.k * sy + h) * g.W0 + g.k * sx + h) * 3;
         for (int k = 0; k < 3; ++k) c[k] = r0[k];
     }
 }
@@ -211,10 +236,12 @@ __global__ __launch_bounds__(256) void zero_sums_kernel(unsigned* __restrict__ s
 // launch 1: sums[b] = sum over the window of the grey level after the operations that precede the contrast operation in this frame's order.
 // An integer sum (160 * 512 * 255 < 2^32), so it does not depend on the grid.
 __global__ __launch_bounds__(256) void grey_sum_kernel(const unsigned char* __restrict__ images, ImgGeom g, const int* __restrict__ ints,
-                                                       const float* __restrict__ factors, int geometry, unsigned* __restrict__ sums) {
+                                                       const float* __restrict__ factors, const int* __restrict__ enable, int geometry,
+                                                       unsigned* __restrict__ sums) {
     __shared__ unsigned part[4];
     const int b = blockIdx.y;
-    const FrameDraw d = load_draw(ints, factors, b, g, geometry);
+    const FrameDraw d = load_draw(ints, factors, enable, b, g, geometry);
+    if (!d.color) return;          // uniform over the workgroup: a frame without colour needs no sum
     const unsigned char* img = images + (long long)b * g.H0 * g.W0 * 3;
     unsigned acc = 0;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < g.H * g.W; i += gridDim.x * 256) {
@@ -231,15 +258,15 @@ __global__ __launch_bounds__(256) void grey_sum_kernel(const unsigned char* __re
 
 // launch 2: 2x2 box -> colour chain in this frame's order -> flip -> three coalesced float32 plane stores
 __global__ __launch_bounds__(256) void image_apply_kernel(const unsigned char* __restrict__ images, ImgGeom g, const int* __restrict__ ints,
-                                                          const float* __restrict__ factors, int geometry, int color,
-                                                          const unsigned* __restrict__ sums, float* __restrict__ out) {
+                                                          const float* __restrict__ factors, const int* __restrict__ enable, int geometry,
+                                                          int color, const unsigned* __restrict__ sums, float* __restrict__ out) {
     const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
     if (i >= g.H * g.W) return;
-    const FrameDraw d = load_draw(ints, factors, b, g, geometry);
+    const FrameDraw d = load_draw(ints, factors, enable, b, g, geometry);
     const int y = i / g.W, x = i % g.W;
     int c[3];
     fetch(images + (long long)b * g.H0 * g.W0 * 3, g, d, y, d.flip ? g.W - 1 - x : x, c);
-    if (color) {
+    if (color && d.color) {
         const unsigned long long n = (unsigned long long)g.H * g.W;
         const int mean = (int)((2ull * sums[b] + n) / (2ull * n));          // int(sum / count + 0.5), exactly
         for (int k = 0; k < 4; ++k) color_op(d.op[k], c, d, mean);
@@ -268,10 +295,10 @@ __global__ __launch_bounds__(256) void transform_segments_kernel(const float* pt
     }
 }
 
-const char* check_opt(const di2p_sample_opt_t* o) {
+const char* check_opt(const di2p_sample_opt_t* o, bool any_scale = false) {
     if (!o) return "null option block";
     if (o->mode < 0 || o->mode > 2) return "bad mode (0 train, 1 val, 2 val_random_Ry)";
-    if (o->img_scale != 0.5 && o->img_scale != 1.0) return "unsupported img_scale (0.5 or 1.0)";
+    if (any_scale ? !(o->img_scale > 0.0 && o->img_scale <= 1.0) : (o->img_scale != 0.5 && o->img_scale != 1.0)) return "unsupported img_scale (0.5 or 1.0)";
     if (o->crop_top < 0 || o->img_H < 1 || o->img_W < 1 || o->Hs < 1 || o->Ws < 1) return "bad sizes";
     if (o->img_H > o->Hs || o->img_W > o->Ws) return "crop window larger than the scaled image";
     if ((long long)o->img_H * o->img_W > (1ll << 24)) return "crop window above 2^24 pixels";
@@ -290,26 +317,49 @@ extern "C" int di2p_sample_draws(unsigned long long seed, const unsigned long lo
     DI2P_CHECK_ARG(((uintptr_t)seed_dev & 7) == 0, "seed_dev must be 8-byte aligned");
     if (B == 0) return 0;
     hipLaunchKernelGGL(sample_draws_kernel, dim3(di2p_cdiv(B, 64)), dim3(64), 0, (hipStream_t)stream, seed, seed_dev, B, frame0, *opt, K, Pc, Pji, ints,
-                       factors, Pr, PrPcn, P, K_out);
+                       factors, Pr, PrPcn, P, K_out, (int)DS_KITTI, (int*)nullptr, (float*)nullptr);
+    DI2P_RETURN_LAUNCH();
+}
+
+extern "C" int di2p_sample_draws_ds(unsigned long long seed, const unsigned long long* seed_dev, int B, int frame0, const di2p_sample_opt_t* opt,
+                                    int dataset, const double* K, const double* P_cam_pc, int32_t* ints, float* factors, int32_t* color_enable,
+                                    double* Pr, float* P, float* K_out, float* t_ij, void* stream) {
+    const char* bad = check_opt(opt, true);
+    DI2P_CHECK_ARG(!bad, bad);
+    DI2P_CHECK_ARG(dataset == DS_OXFORD || dataset == DS_NUSCENES, "bad data set (1 Oxford, 2 nuScenes; KITTI frames go through di2p_sample_draws)");
+    DI2P_CHECK_ARG(B >= 0 && frame0 >= 0, "bad sizes");
+    DI2P_CHECK_ARG(B == 0 || (K && P_cam_pc && ints && factors && color_enable && Pr && P && K_out), "null pointer");
+    DI2P_CHECK_ARG(((uintptr_t)seed_dev & 7) == 0, "seed_dev must be 8-byte aligned");
+    if (B == 0) return 0;
+    hipLaunchKernelGGL(sample_draws_kernel, dim3(di2p_cdiv(B, 64)), dim3(64), 0, (hipStream_t)stream, seed, seed_dev, B, frame0, *opt, K, P_cam_pc,
+                       (const double*)nullptr, ints, factors, Pr, (double*)nullptr, P, K_out, dataset, color_enable, t_ij);
     DI2P_RETURN_LAUNCH();
 }
 
 extern "C" long long di2p_image_prepare_workspace_bytes(int B) { return B < 0 ? 0 : ((long long)B * 4 + 255) / 256 * 256 + 256; }
 
-extern "C" int di2p_image_prepare(const uint8_t* images, int B, int H0, int W0, const di2p_sample_opt_t* opt, const int32_t* ints,
-                                  const float* factors, int geometry, int color, int reduce_blocks, float* out, void* workspace, void* stream) {
-    const char* bad = check_opt(opt);
+namespace {
+
+// resize_k: 0 the scale of the option block (0.5: rounded 2x2 mean, 1.0: none), odd k >= 3: the centre pixel of every k x k block
+int image_prepare(const uint8_t* images, int B, int H0, int W0, const di2p_sample_opt_t* opt, int crop_bottom, int resize_k, const int32_t* ints,
+                  const float* factors, const int32_t* enable, int noflip, int geometry, int color, int reduce_blocks, float* out, void* workspace,
+                  void* stream) {
+    const char* bad = check_opt(opt, resize_k != 0);
     DI2P_CHECK_ARG(!bad, bad);
+    DI2P_CHECK_ARG(crop_bottom >= 0 && (resize_k == 0 || (resize_k >= 3 && resize_k % 2 == 1)), "bad crop_bottom / resize_k (0, or odd >= 3)");
+    DI2P_CHECK_ARG(geometry || (crop_bottom == 0 && resize_k == 0), "crop_bottom and resize_k need geometry");
     DI2P_CHECK_ARG(B >= 0 && H0 >= 1 && W0 >= 1 && reduce_blocks >= 0 && reduce_blocks <= 65535 && B <= 65535, "bad sizes");
     DI2P_CHECK_ARG((long long)H0 * W0 * 3 < (1ll << 31), "image above 2^31 bytes");
-    ImgGeom g{H0, W0, 0, 0, opt->img_H, opt->img_W, 0, 0};
+    ImgGeom g{H0, W0, 0, 0, opt->img_H, opt->img_W, 0, 0, 1, noflip};
     if (geometry) {
-        const bool half = opt->img_scale == 0.5;
-        DI2P_CHECK_ARG(opt->crop_top < H0, "crop_original_top_rows leaves no image");
-        DI2P_CHECK_ARG(!half || ((H0 - opt->crop_top) % 2 == 0 && W0 % 2 == 0), "odd scaled size: img_scale 0.5 needs even cropped source dimensions");
-        DI2P_CHECK_ARG(opt->Hs == (half ? (H0 - opt->crop_top) / 2 : H0 - opt->crop_top) && opt->Ws == (half ? W0 / 2 : W0),
-                       "scaled size does not match the source image");
-        g.top = opt->crop_top; g.half = half ? 1 : 0; g.max_dx = opt->Ws - opt->img_W; g.max_dy = opt->Hs - opt->img_H;
+        const bool half = resize_k == 0 && opt->img_scale == 0.5;
+        const int div = resize_k ? resize_k : half ? 2 : 1;
+        DI2P_CHECK_ARG(opt->crop_top < H0 - crop_bottom, "crop_original_top_rows / crop_original_bottom_rows leave no image");
+        const int Hc = H0 - opt->crop_top - crop_bottom;
+        DI2P_CHECK_ARG(!half || (Hc % 2 == 0 && W0 % 2 == 0), "odd scaled size: img_scale 0.5 needs even cropped source dimensions");
+        DI2P_CHECK_ARG(Hc % div == 0 && W0 % div == 0, "resize_k must divide both cropped source dimensions");
+        DI2P_CHECK_ARG(opt->Hs == Hc / div && opt->Ws == W0 / div, "scaled size does not match the source image");
+        g.top = opt->crop_top; g.half = half ? 1 : 0; g.k = resize_k ? resize_k : 1; g.max_dx = opt->Ws - opt->img_W; g.max_dy = opt->Hs - opt->img_H;
     } else {
         DI2P_CHECK_ARG(H0 == opt->img_H && W0 == opt->img_W, "without geometry the source must already be img_H x img_W");
     }
@@ -325,10 +375,24 @@ extern "C" int di2p_image_prepare(const uint8_t* images, int B, int H0, int W0, 
         // reduction (second replay of a 20-frame plan: stale sums, a wrong contrast mean); kernel nodes keep their order
         hipLaunchKernelGGL(zero_sums_kernel, dim3(di2p_cdiv(B, 256)), dim3(256), 0, st, sums, B);
         const int rb = reduce_blocks > 0 ? reduce_blocks : min(di2p_cdiv(npix, 1024), 128);
-        hipLaunchKernelGGL(grey_sum_kernel, dim3(rb, B), dim3(256), 0, st, images, g, ints, factors, geometry, sums);
+        hipLaunchKernelGGL(grey_sum_kernel, dim3(rb, B), dim3(256), 0, st, images, g, ints, factors, enable, geometry, sums);
     }
-    hipLaunchKernelGGL(image_apply_kernel, dim3(di2p_cdiv(npix, 256), B), dim3(256), 0, st, images, g, ints, factors, geometry, color, sums, out);
+    hipLaunchKernelGGL(image_apply_kernel, dim3(di2p_cdiv(npix, 256), B), dim3(256), 0, st, images, g, ints, factors, enable, geometry, color, sums,
+                       out);
     DI2P_RETURN_LAUNCH();
+}
+
+}  // namespace
+
+extern "C" int di2p_image_prepare(const uint8_t* images, int B, int H0, int W0, const di2p_sample_opt_t* opt, const int32_t* ints,
+                                  const float* factors, int geometry, int color, int reduce_blocks, float* out, void* workspace, void* stream) {
+    return image_prepare(images, B, H0, W0, opt, 0, 0, ints, factors, nullptr, 0, geometry, color, reduce_blocks, out, workspace, stream);
+}
+
+extern "C" int di2p_image_prepare_ds(const uint8_t* images, int B, int H0, int W0, const di2p_sample_opt_t* opt, int crop_bottom, int resize_k,
+                                     const int32_t* ints, const float* factors, const int32_t* color_enable, int color, int reduce_blocks,
+                                     float* out, void* workspace, void* stream) {
+    return image_prepare(images, B, H0, W0, opt, crop_bottom, resize_k, ints, factors, color_enable, 1, 1, color, reduce_blocks, out, workspace, stream);
 }
 
 extern "C" int di2p_transform_segments(const float* points, const float* normals, const int32_t* seg_offsets, const double* transforms, int S,

@@ -492,8 +492,9 @@ __global__ __launch_bounds__(256) void nearest_raw_kernel(const float* __restric
 
 // ---------------------------------------------------------------- stage 4: ragged gather (+ jitter) (+ rigid transform)
 // Jitter (sigma > 0): clip(sigma * N(0,1), +-clip) rounded to float32, a pure function of (seed, stream_id, frame, output index, component):
-// Philox counter (n, frame, stream_id * 8 + component, 5), component 0..2 the point, 4..6 the normal; Box-Muller on two 53-bit uniforms.
-struct Jitter { unsigned long long seed; const unsigned long long* seed_dev; int stream_id; double sigma, clip; };
+// Philox counter (n, frame, stream_id * 8 + component, 5), component 0..2 the point, 3 the intensity (di2p_gather_ragged_aug_intensity only),
+// 4..6 the normal; Box-Muller on two 53-bit uniforms.
+struct Jitter { unsigned long long seed; const unsigned long long* seed_dev; int stream_id; double sigma, clip; int intensity; };
 
 __device__ __forceinline__ float jitter_noise(unsigned long long seed, const Jitter& j, int b, int n, int comp) {
     const U4 r = philox4x32_10(U4{(unsigned)n, (unsigned)b, (unsigned)(j.stream_id * 8 + comp), 5u}, (unsigned)seed, (unsigned)(seed >> 32));
@@ -523,6 +524,7 @@ __global__ __launch_bounds__(256) void gather_ragged_kernel(const float* __restr
                 p[c] = (double)__fadd_rn(jitter_noise(seed, jit, b, n, c), (float)p[c]);
                 if (nrm) s[c] = (double)__fadd_rn(jitter_noise(seed, jit, b, n, 4 + c), (float)s[c]);
             }
+            if (jit.intensity && inten) it = __fadd_rn(jitter_noise(seed, jit, b, n, DI2P_JITTER_SLOT_INTENSITY), it);
         }
     }
     const long long o3 = (long long)b * 3 * n_out + n;
@@ -539,6 +541,52 @@ __global__ __launch_bounds__(256) void gather_ragged_kernel(const float* __restr
         }
     }
     if (out_int) out_int[(long long)b * n_out + n] = it;
+}
+
+// ---------------------------------------------------------------- stage 0 (Oxford loader): range filter + shuffle + compaction
+// data/oxford_pc_img_pose_loader.py:269-279.  Point i of frame b is kept iff fl32(fl32(x x) + fl32(z z)) < fl32(r r) (r <= 0: every point);
+// the kept points of a frame come out in ascending order of key(seed, b, i) = the upper 63 bits of the first two words of Philox counter
+// (i, b, 0, 6), ties to the lower i (the sort is stable).  Dropped points, the rows past the batch and every point of a rejected frame go
+// to the sentinel frame B and are never written.
+__global__ __launch_bounds__(256) void shuffle_keys_kernel(const float* __restrict__ pts, const int* __restrict__ off, int B, int cap,
+                                                           int max_frame_points, float r2, unsigned long long seed,
+                                                           const unsigned long long* __restrict__ seed_dev, unsigned* __restrict__ pfr,
+                                                           unsigned long long* __restrict__ key, int* __restrict__ iota, int* __restrict__ status) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const bool head_ok = off[0] == 0;
+    if (i < B && status) {
+        const int s0 = off[i], s1 = off[i + 1];
+        const bool ok = head_ok && s0 >= 0 && s1 >= s0 && s1 <= cap;
+        status[i] = !ok ? ST_OFFSETS : (s1 - s0 > max_frame_points ? ST_TOO_MANY : ST_OK);
+    }
+    if (i >= cap) return;
+    iota[i] = (int)i;
+    pfr[i] = (unsigned)B;
+    key[i] = PAD_KEY;
+    const int total = min(max(off[B], 0), cap);
+    if (i >= total) return;
+    const int b = frame_of(off, B, i);
+    const int s0 = off[b], s1 = off[b + 1];
+    if (!(head_ok && s0 >= 0 && s1 >= s0 && s1 <= cap && s1 - s0 <= max_frame_points && i >= s0 && i < s1)) return;
+    const float4 p = *(const float4*)(pts + 4 * i);
+    if (r2 > 0.0f && !(__fadd_rn(__fmul_rn(p.x, p.x), __fmul_rn(p.z, p.z)) < r2)) return;
+    if (seed_dev) seed = *seed_dev;
+    const U4 r = philox4x32_10(U4{(unsigned)(i - s0), (unsigned)b, 0u, 6u}, (unsigned)seed, (unsigned)(seed >> 32));
+    pfr[i] = (unsigned)b;
+    key[i] = (((unsigned long long)r.x << 32) | (unsigned long long)r.y) >> 1;
+}
+
+// out_off[j] = the first sorted position whose frame is >= j (j = 0 .. B); sorted position p of a kept point is its output row
+__global__ __launch_bounds__(256) void shuffle_compact_kernel(const float* __restrict__ pts, const unsigned* __restrict__ sfr,
+                                                              const int* __restrict__ sidx, int B, int cap, float* __restrict__ out,
+                                                              int* __restrict__ out_off) {
+    const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (j <= B) {
+        int lo = 0, hi = cap;
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (sfr[mid] < (unsigned)j) lo = mid + 1; else hi = mid; }
+        out_off[j] = lo;
+    }
+    if (j < cap && sfr[j] < (unsigned)B) *(float4*)(out + 4 * j) = *(const float4*)(pts + 4 * (long long)sidx[j]);
 }
 
 int frame_bits(int B) { int bits = 1; while ((1ll << bits) <= B) ++bits; return bits; }
@@ -688,7 +736,7 @@ extern "C" int di2p_gather_ragged(const float* points, const float* intensity, c
     DI2P_CHECK_ARG(!sn || normals, "sn needs normals");
     if (B == 0 || n_out == 0) return 0;
     hipLaunchKernelGGL(gather_ragged_kernel, dim3(di2p_cdiv(n_out, 256), B), dim3(256), 0, (hipStream_t)stream, points, intensity, normals, offsets,
-                       idx, transform, n_out, pc, intensity_out, sn, Jitter{0ull, nullptr, 0, 0.0, 0.0});
+                       idx, transform, n_out, pc, intensity_out, sn, Jitter{0ull, nullptr, 0, 0.0, 0.0, 0});
     DI2P_RETURN_LAUNCH();
 }
 
@@ -703,6 +751,49 @@ extern "C" int di2p_gather_ragged_aug(const float* points, const float* intensit
     DI2P_CHECK_ARG(((uintptr_t)seed_dev & 7) == 0, "seed_dev must be 8-byte aligned");
     if (B == 0 || n_out == 0) return 0;
     hipLaunchKernelGGL(gather_ragged_kernel, dim3(di2p_cdiv(n_out, 256), B), dim3(256), 0, (hipStream_t)stream, points, intensity, normals, offsets,
-                       idx, transform, n_out, pc, intensity_out, sn, Jitter{seed, seed_dev, stream_id, sigma, clip});
+                       idx, transform, n_out, pc, intensity_out, sn, Jitter{seed, seed_dev, stream_id, sigma, clip, 0});
+    DI2P_RETURN_LAUNCH();
+}
+
+extern "C" int di2p_gather_ragged_aug_intensity(const float* points, const float* intensity, const int32_t* offsets, const int32_t* idx,
+                                                const double* transform, int B, int n_out, unsigned long long seed,
+                                                const unsigned long long* seed_dev, int stream_id, double sigma, double clip, float* pc,
+                                                float* intensity_out, void* stream) {
+    DI2P_CHECK_ARG(B >= 0 && n_out >= 0, "bad sizes");
+    DI2P_CHECK_ARG(B == 0 || n_out == 0 || (points && intensity && offsets && idx && pc && intensity_out), "null pointer");
+    DI2P_CHECK_ARG(sigma >= 0.0 && sigma < 1e30 && clip > 0.0 && stream_id >= 0 && stream_id < (1 << 28), "jitter needs 0 <= sigma, clip > 0");
+    DI2P_CHECK_ARG(((uintptr_t)seed_dev & 7) == 0, "seed_dev must be 8-byte aligned");
+    if (B == 0 || n_out == 0) return 0;
+    hipLaunchKernelGGL(gather_ragged_kernel, dim3(di2p_cdiv(n_out, 256), B), dim3(256), 0, (hipStream_t)stream, points, intensity,
+                       (const float*)nullptr, offsets, idx, transform, n_out, pc, intensity_out, (float*)nullptr,
+                       Jitter{seed, seed_dev, stream_id, sigma, clip, 1});
+    DI2P_RETURN_LAUNCH();
+}
+
+extern "C" int di2p_range_shuffle(const float* points, const int32_t* offsets, int B, int cap, int max_frame_points, double max_range,
+                                  unsigned long long seed, const unsigned long long* seed_dev, float* out_points, int32_t* out_offsets,
+                                  int32_t* status, void* workspace, void* stream) {
+    DI2P_CHECK_ARG(B >= 0 && cap >= 0, "bad sizes (B >= 0, cap >= 0)");
+    DI2P_CHECK_ARG(max_frame_points >= 0 && max_frame_points <= MAX_FRAME_POINTS, "max_frame_points above 2^20 points per frame");
+    DI2P_CHECK_ARG(max_range == max_range && max_range < 1e18, "max_range must be finite (<= 0: no range filter)");
+    DI2P_CHECK_ARG(B == 0 || (points && offsets && out_points && out_offsets && workspace), "null pointer");
+    DI2P_CHECK_ARG(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)seed_dev & 7) == 0 && ((uintptr_t)points & 15) == 0 &&
+                       ((uintptr_t)out_points & 15) == 0, "workspace must be 256-byte, points 16-byte, seed_dev 8-byte aligned");
+    if (B == 0) return 0;
+    const Layout L = layout(B, cap);
+    hipStream_t st = (hipStream_t)stream;
+    void* ws = workspace;
+    const float r = (float)max_range;
+    const float r2 = max_range > 0.0 ? r * r : 0.0f;
+    const int n = cap > B + 1 ? cap : B + 1;
+    hipLaunchKernelGGL(shuffle_keys_kernel, dim3(di2p_cdiv(n, 256)), dim3(256), 0, st, points, offsets, B, cap, max_frame_points, r2, seed, seed_dev,
+                       at<unsigned>(ws, L.pfr), at<unsigned long long>(ws, L.key), at<int>(ws, L.iota), status);
+    if (cap > 0) {
+        const hipError_t e = sort_by_frame_key(ws, L, B, cap, at<unsigned long long>(ws, L.key), at<unsigned>(ws, L.pfr), at<int>(ws, L.i2),
+                                               at<unsigned long long>(ws, L.k2), at<unsigned>(ws, L.f2), st);
+        if (e != hipSuccess) { di2p_set_error("di2p_range_shuffle: sort failed: %s", hipGetErrorString(e)); return (int)e; }
+    }
+    hipLaunchKernelGGL(shuffle_compact_kernel, dim3(di2p_cdiv(n, 256)), dim3(256), 0, st, points, at<unsigned>(ws, L.f2), at<int>(ws, L.i2), B, cap,
+                       out_points, out_offsets);
     DI2P_RETURN_LAUNCH();
 }

@@ -96,6 +96,23 @@ def nearest_raw(state, points, offsets):
     return idx, inten, d2
 
 
+def range_shuffle(points, offsets, max_range, seed=0, seed_dev=None, max_frame_points=MAX_FRAME_POINTS, cap=None, out=None, ws=None):
+    """di2p_range_shuffle (the Oxford loader's shuffle and horizontal range filter): points f32[>=total,4], offsets i32[B+1] (device) ->
+    (points f32[cap,4], offsets i32[B+1], status i32[B]): per frame the points with x^2 + z^2 < max_range^2 (float32; max_range <= 0: all) in
+    the order of their Philox keys.  out = (points, offsets, status) preallocated, ws the scan_prep workspace of (B, cap).  No synchronisation."""
+    require_cuda(points, offsets, seed_dev)
+    B = offsets.shape[0] - 1
+    cap = int(points.shape[0]) if cap is None else int(cap)
+    dev = points.device
+    if out is None:
+        out = (torch.zeros((max(cap, 1), 4), dtype=torch.float32, device=dev), torch.zeros((B + 1,), dtype=torch.int32, device=dev),
+               torch.zeros((max(B, 1),), dtype=torch.int32, device=dev))
+    ws = workspace(B, cap, dev) if ws is None else ws
+    call("di2p_range_shuffle", ptr(points), ptr(offsets), B, cap, int(max_frame_points), float(max_range), 0 if seed_dev is not None else int(seed),
+         ptr(seed_dev), ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(ws), stream())
+    return out
+
+
 def random_choice_ragged(seed, offsets, max_src, n_out, stream_id=0, out=None, ws=None):
     """-> i32[B, n_out] frame-local indices: prep.downsample's draw per frame with that frame's own count (device offsets)."""
     B = offsets.shape[0] - 1
@@ -137,7 +154,8 @@ class BatchPlan:
     """Fixed-capacity, preallocated form of prepare_batch: run() launches every stage on the current stream with no host
     synchronisation and no allocation, so it can be captured in a hipGraph (torch.cuda.graph).  status (i32[B]) stays on the device."""
 
-    def __init__(self, B, cap, max_frame_points, input_pt_num=20480, node_num=128, voxel=0.3, device=None):
+    def __init__(self, B, cap, max_frame_points, input_pt_num=20480, node_num=128, voxel=0.3, device=None, normals=True):
+        """normals=False (the Oxford / nuScenes records have none): no normal buffers, run() takes normals=None and returns sn = None"""
         dev = device or _dev()
         self.B, self.cap, self.max_src, self.n, self.node_num, self.voxel = B, int(cap), int(max_frame_points), int(input_pt_num), int(node_num), voxel
         self.ws = workspace(B, self.cap, dev)
@@ -145,13 +163,13 @@ class BatchPlan:
         self.v_off = torch.zeros((B + 1,), dtype=torch.int32, device=dev)
         self.v_pts = torch.empty((c, 3), dtype=torch.float32, device=dev)
         self.v_int = torch.empty((c,), dtype=torch.float32, device=dev)
-        self.v_nrm = torch.empty((c, 3), dtype=torch.float32, device=dev)
+        self.v_nrm = torch.empty((c, 3), dtype=torch.float32, device=dev) if normals else None
         self.status = torch.zeros((max(B, 1),), dtype=torch.int32, device=dev)
         self.idx = torch.empty((B, self.n), dtype=torch.int32, device=dev)
         self.choice_ws = torch.empty((_lib.load().di2p_random_choice_ragged_workspace_bytes(B, max(1, self.max_src)),), dtype=torch.uint8, device=dev)
         self.pc = torch.empty((B, 3, self.n), dtype=torch.float32, device=dev)
         self.intensity = torch.empty((B, 1, self.n), dtype=torch.float32, device=dev)
-        self.sn = torch.empty((B, 3, self.n), dtype=torch.float32, device=dev)
+        self.sn = torch.empty((B, 3, self.n), dtype=torch.float32, device=dev) if normals else None
         self.m = min(self.n, self.node_num * 8)
         self.cand_ws = torch.empty((_lib.load().di2p_random_choice_workspace_bytes(B, self.n),), dtype=torch.uint8, device=dev)
         self.cand_idx = [torch.empty((B, self.m), dtype=torch.int32, device=dev) for _ in range(2)]
@@ -159,12 +177,17 @@ class BatchPlan:
         self.fps_idx = [torch.empty((B, self.node_num), dtype=torch.int32, device=dev) for _ in range(2)]
         self.nodes = [torch.empty((B, 3, self.node_num), dtype=torch.float32, device=dev) for _ in range(2)]
 
-    def run(self, points, normals, offsets, seed, P=None, seed_dev=None, jitter=None):
+    def run(self, points, normals, offsets, seed, P=None, seed_dev=None, jitter=None, jitter_intensity=False):
         """points f32[>=total,4] (x, y, z, intensity), normals f32[>=total,3], offsets i32[B+1] (device; total <= cap, every frame
         <= max_frame_points), P f64[B,4,4] or None -> (pc, intensity, sn, node_a, node_b), views of the plan's buffers.
         seed_dev (i64[1] device, sample_prep.SamplePlan): every draw reads its seed from there when it runs, `seed` is ignored -- the same
-        draws as seed = seed_dev's value.  jitter (sigma, clip): Gaussian noise on points and normals before P (di2p_gather_ragged_aug)."""
+        draws as seed = seed_dev's value.  jitter (sigma, clip): Gaussian noise on points and normals before P (di2p_gather_ragged_aug);
+        jitter_intensity (a plan without normals only): the noise on the intensity too (di2p_gather_ragged_aug_intensity)."""
         require_cuda(points, normals, offsets, P, seed_dev)
+        if (normals is None) != (self.v_nrm is None):
+            raise ValueError("scan_prep: normals must be given to a plan with normals and be None for a plan without (BatchPlan(normals=...))")
+        if jitter_intensity and (jitter is None or normals is not None):
+            raise ValueError("scan_prep: jitter_intensity needs jitter and a plan without normals")
         B, s = self.B, stream()
         call("di2p_voxel_down_sample", ptr(points), ptr(offsets), B, self.cap, self.max_src, float(self.voxel), MAX_EXTENT, 2 * self.n, ptr(normals),
              ptr(self.v_off), ptr(self.v_pts), ptr(self.v_int), ptr(self.v_nrm), None, ptr(self.status), ptr(self.ws), s)
@@ -172,7 +195,10 @@ class BatchPlan:
             call("di2p_random_choice_ragged", int(seed), 0, B, ptr(self.v_off), self.max_src, self.n, ptr(self.idx), ptr(self.choice_ws), s)
         else:
             call("di2p_random_choice_ragged_dseed", ptr(seed_dev), 0, B, ptr(self.v_off), self.max_src, self.n, ptr(self.idx), ptr(self.choice_ws), s)
-        if jitter is None:
+        if jitter_intensity:
+            call("di2p_gather_ragged_aug_intensity", ptr(self.v_pts), ptr(self.v_int), ptr(self.v_off), ptr(self.idx), ptr(P), B, self.n,
+                 0 if seed_dev is not None else int(seed), ptr(seed_dev), 0, float(jitter[0]), float(jitter[1]), ptr(self.pc), ptr(self.intensity), s)
+        elif jitter is None:
             call("di2p_gather_ragged", ptr(self.v_pts), ptr(self.v_int), ptr(self.v_nrm), ptr(self.v_off), ptr(self.idx), ptr(P), B, self.n,
                  ptr(self.pc), ptr(self.intensity), ptr(self.sn), s)
         else:

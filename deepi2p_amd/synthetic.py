@@ -297,6 +297,25 @@ def make_velodyne_scan(rng, beams=64, azimuths=1800, max_range=120.0, dropout=0.
     return np.concatenate([pts, inten[:, None]], axis=1).astype(np.float32)
 
 
+def make_oxford_submap(rng, n, length=100.0, half_width=8.0, far_share=0.2, max_range=50.0):
+    """A push-broom sub-map as the Oxford loader stores it: f32[4, n] rows (x, y, z, intensity) in the CAMERA frame (x right, y down, z
+    forward), built from a 2-D LMS-like scanner swept along z, so it is much longer (`length`, along z) than wide (+- half_width in x) and
+    its points are stored in SCAN ORDER: profile after profile, ascending z -- which is why the loader shuffles before it down-samples.
+    About `far_share` of the points lie beyond `max_range` in the x-z plane (the loader's horizontal range filter removes them)."""
+    per = 64                                                    # points per scanner profile
+    profiles = -(-n // per)
+    zmax = max_range + far_share * length                        # uniform in z: the share beyond max_range is about far_share
+    z0 = np.sort(rng.uniform(zmax - length, zmax, profiles))
+    ang = np.linspace(-1.2, 1.2, per)
+    zz = np.repeat(z0, per)[:n] + rng.normal(0.0, 0.01, n)
+    a = np.tile(ang, profiles)[:n]
+    road = np.abs(a) < 0.9                                       # road surface below the camera, walls at the sides
+    x = np.where(road, 1.6 * np.tan(a), np.sign(a) * half_width) + rng.normal(0.0, 0.02, n)
+    y = np.where(road, 1.6, 1.6 - (np.abs(a) - 0.9) * 20.0) + rng.normal(0.0, 0.02, n)
+    inten = np.clip(np.where(road, 0.3, 0.6) + rng.normal(0.0, 0.05, n), 0.0, 1.0)
+    return np.stack([x, y, zz, inten]).astype(np.float32)
+
+
 def make_camera_image(rng, H0=370, W0=1226):
     """A synthetic camera frame u8[H0, W0, 3] (HWC, as np.load gives the loader's images) that reaches every branch of the colour code:
     smooth gradients (every hue sector), per-pixel texture, saturated primaries, pure black / white, and exactly grey patches."""

@@ -550,7 +550,7 @@ int di2p_apply_mask(const float* x, const uint8_t* mask, float scale, float* y, 
 typedef struct {
     int mode;               /* 0 train, 1 val, 2 val_random_Ry */
     int crop_top;           /* crop_original_top_rows */
-    double img_scale;       /* 0.5 or 1.0 */
+    double img_scale;       /* 0.5 or 1.0 (the _ds entry points: any value in (0, 1], it scales K) */
     int img_H, img_W;       /* the crop window */
     int Hs, Ws;             /* the scaled image: (H0 - crop_top) * img_scale, W0 * img_scale */
     double amplitude[6];    /* P_tx, P_ty, P_tz, P_Rx, P_Ry, P_Rz */
@@ -571,6 +571,41 @@ int di2p_random_choice_dseed(const unsigned long long* seed_dev, int stream_id, 
                              void* workspace, void* stream);
 int di2p_random_choice_ragged_dseed(const unsigned long long* seed_dev, int stream_id, int B, const int32_t* offsets, int max_src,
                                     int n_out, int32_t* idx_out, void* workspace, void* stream);
+
+/* ---- (additive, ABI 9; detect by symbol) sample preparation of the Oxford and nuScenes loaders (data/oxford_pc_img_pose_loader.py:220-380,
+ *      data/nuscenes_pc_img_pose_loader.py:213-267,273-408).  Same conventions as above: asynchronous, capturable, seed or *seed_dev. ----
+ * di2p_range_shuffle (csrc/scan_prep.hip): ragged range filter + shuffle + compaction of the Oxford loader (:269-279), one call per batch.
+ *   Point i of frame b is kept iff fl32(fl32(x x) + fl32(z z)) < fl32(r r) with r = (float)max_range (strict; max_range <= 0 keeps all).  The kept
+ *   points of a frame come out in ascending order of key(seed, b, i) = (w0 << 32 | w1) >> 1 of Philox counter (i, b, 0, 6) -- stream tag 6, used
+ *   by nothing else -- ties to the lower i.  out_points f32[cap,4], out_offsets i32[B+1]; a frame may keep nothing.  status i32[B] (may be
+ *   NULL): 0 ok, 1 more than max_frame_points (<= 2^20) points, 3 bad offsets; such a frame has no output rows and nothing is written for
+ *   it.  workspace: di2p_scan_prep_workspace_bytes(B, cap), 256-byte aligned; it may be the one di2p_voxel_down_sample uses afterwards.
+ * di2p_gather_ragged_aug_intensity: di2p_gather_ragged_aug without normals, and with the same clipped noise additionally added to the
+ *   intensity (float32 + float32) from Philox component slot DI2P_JITTER_SLOT_INTENSITY, which di2p_gather_ragged_aug leaves unused
+ *   (0..2 the coordinates, 4..6 the normal).  The coordinate noise is di2p_gather_ragged_aug's, bit for bit.
+ * di2p_sample_draws_ds: di2p_sample_draws for dataset 1 (Oxford) / 2 (nuScenes).  The uniforms of the frame keep their meaning (window,
+ *   order, factors, translations, angles); no flip is drawn (ints[2] = 0); color_enable i32[B] = (u > 0.5) of one further uniform of the
+ *   frame (Philox block 7; 0 outside train mode);  Pr f64[B,4,4] = [Rz Ry Rx | t] from all six amplitudes, applied by the point kernels to the
+ *   cloud in the frame it is stored in;  val_random_Ry: +- 2 pi about y (Oxford) / about z (nuScenes);  P = P_cam_pc . Pr^-1 f32[B,3,4]
+ *   (fp64, closed-form rigid inverse, rounded once);  K_out = K after crop-top (0 for Oxford: the bottom crop does not move K), scale,
+ *   crop-window;  t_ij f32[B,3] = P_cam_pc[:3,3] (may be NULL).  opt->img_scale may be any value in (0, 1] here.
+ * di2p_image_prepare_ds: di2p_image_prepare with crop_bottom rows removed below, resize_k (0: opt->img_scale 0.5 / 1.0 as above; odd k >= 3
+ *   dividing both cropped source dimensions: output pixel (y, x) is the source pixel (k y + (k-1)/2, k x + (k-1)/2), which is INTER_LINEAR at
+ *   scale 1/k with an explicit dsize -- derived from OpenCV's coordinate rule, not checked against OpenCV), color_enable i32[B] (NULL: every
+ *   frame) gating the colour chain per frame, and no flip whatever ints[2] holds.  opt->Hs / Ws: the cropped source size over k. */
+#define DI2P_JITTER_SLOT_INTENSITY 3
+int di2p_range_shuffle(const float* points, const int32_t* offsets, int B, int cap, int max_frame_points, double max_range,
+                       unsigned long long seed, const unsigned long long* seed_dev, float* out_points, int32_t* out_offsets, int32_t* status,
+                       void* workspace, void* stream);
+int di2p_gather_ragged_aug_intensity(const float* points, const float* intensity, const int32_t* offsets, const int32_t* idx,
+                                     const double* transform, int B, int n_out, unsigned long long seed, const unsigned long long* seed_dev,
+                                     int stream_id, double sigma, double clip, float* pc, float* intensity_out, void* stream);
+int di2p_sample_draws_ds(unsigned long long seed, const unsigned long long* seed_dev, int B, int frame0, const di2p_sample_opt_t* opt,
+                         int dataset, const double* K, const double* P_cam_pc, int32_t* ints, float* factors, int32_t* color_enable,
+                         double* Pr, float* P, float* K_out, float* t_ij, void* stream);
+int di2p_image_prepare_ds(const uint8_t* images, int B, int H0, int W0, const di2p_sample_opt_t* opt, int crop_bottom, int resize_k,
+                          const int32_t* ints, const float* factors, const int32_t* color_enable, int color, int reduce_blocks, float* out,
+                          void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

@@ -3,6 +3,8 @@
 path) for a batch of records and 370 x 1226 camera frames, as one captured graph (total) and eagerly with per-launch events (stages);
 the algorithmic bytes over the total as a fraction of 8 TB/s; and, for context, the numpy oracle's image path per sample on one host thread.
     python tools/bench_sample_prep.py [--B 8] [--reps 10] [--warmup 3] [--cpu-frames 2]
+--dataset oxford / nuscenes: the same plan at that loader's own shapes (Oxford 960 x 1280 -> 384 x 640 with the range filter and shuffle,
+nuScenes 900 x 1600 -> 160 x 320; 0.2 m voxel pass, intensity jitter), e.g. --dataset oxford --B 32 --points 60000.
 """
 import argparse
 import json
@@ -24,6 +26,9 @@ from deepi2p_amd import _lib, sample_prep, scan_prep, synthetic  # noqa: E402
 STAGES = {"draws": ["di2p_sample_draws"], "voxel 0.3": ["di2p_voxel_down_sample"],
           "down-sample + jitter": ["di2p_random_choice_ragged_dseed", "di2p_gather_ragged_aug"],
           "nodes": ["di2p_random_choice_dseed", "di2p_gather_points", "di2p_farthest_point_sampling"], "image": ["di2p_image_prepare"]}
+STAGES_DS = {"draws": ["di2p_sample_draws_ds"], "filter + shuffle": ["di2p_range_shuffle"], "voxel 0.2": ["di2p_voxel_down_sample"],
+             "down-sample + jitter": ["di2p_random_choice_ragged_dseed", "di2p_gather_ragged_aug_intensity"], "nodes": STAGES["nodes"],
+             "image": ["di2p_image_prepare_ds"]}
 K_RAW = np.array([[718.856, 0.0, 607.1928], [0.0, 718.856, 185.2157], [0.0, 0.0, 1.0]])
 PC = np.array([[0, -1, 0, 0], [0, 0, -1, -0.05], [1, 0, 0, -0.3], [0, 0, 0, 1]], dtype=np.float64)
 
@@ -35,20 +40,30 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--cpu-frames", type=int, default=2)
     ap.add_argument("--points", type=int, default=60000, help="points per record (above 2 * 20480: the voxel pass runs)")
+    ap.add_argument("--dataset", choices=sorted(sample_prep.DATASETS), default="kitti")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     B, rng = a.B, np.random.default_rng(0)
+    stages = STAGES if a.dataset == "kitti" else STAGES_DS
     recs = []
     for i in range(B):
+        if a.dataset == "oxford":
+            recs.append(synthetic.make_oxford_submap(np.random.default_rng(100 + i), a.points).T)
+            continue
         s = synthetic.make_velodyne_scan(np.random.default_rng(100 + i))[:a.points]
         sn = rng.standard_normal((s.shape[0], 3)).astype(np.float32)
-        recs.append(np.concatenate([s.T, sn.T], 0))
-    raw = np.stack([synthetic.make_camera_image(np.random.default_rng(200 + i)) for i in range(B)])
-    points, normals, offsets, host = scan_prep.pack_records(recs, dev)
+        recs.append(np.concatenate([s.T, sn.T], 0) if a.dataset == "kitti" else s)
+    H0, W0 = sample_prep.RAW_HW[a.dataset]
+    one = [synthetic.make_camera_image(np.random.default_rng(200 + i), H0, W0) for i in range(min(B, 4))]
+    raw = np.stack([one[i % len(one)] for i in range(B)])
+    if a.dataset == "kitti":
+        points, normals, offsets, host = scan_prep.pack_records(recs, dev)
+    else:
+        (points, offsets, host), normals = scan_prep.pack(recs, dev), None
     images = torch.from_numpy(raw).to(dev)
     K, Pc = [torch.from_numpy(np.tile(m, (B, 1, 1))).to(dev) for m in (K_RAW, PC)]
     opt = SimpleNamespace()
-    plan = sample_prep.SamplePlan(opt, B, points.shape[0], int(np.diff(host).max()), raw.shape[1:3], "train", dev)
+    plan = sample_prep.SamplePlan(opt, B, points.shape[0], int(np.diff(host).max()), raw.shape[1:3], "train", dev, dataset=a.dataset)
     args = (points, normals, offsets, images, K, Pc, None)
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
@@ -69,13 +84,13 @@ def main():
         torch.cuda.synchronize()
         if i >= a.warmup:
             totals.append(e0.elapsed_time(e1))
-    names = sorted({n for v in STAGES.values() for n in v})
-    per_stage = {k: [] for k in STAGES}
+    names = sorted({n for v in stages.values() for n in v})
+    per_stage = {k: [] for k in stages}
     for i in range(a.reps):
         _lib.TIMED = {n: [] for n in names}
         plan.run(*args, seed=i)
         torch.cuda.synchronize()
-        for stage, keys in STAGES.items():
+        for stage, keys in stages.items():
             per_stage[stage].append(sum(s.elapsed_time(e) for k in keys for s, e, _ in _lib.TIMED[k]))
         _lib.TIMED = None
     scan_prep.check_status(plan.status[:B])
@@ -87,11 +102,11 @@ def main():
     from tests import sample_prep_oracle as spo
     ints, fac = plan.table.ints.cpu().numpy(), plan.table.factors.cpu().numpy()
     cpu = []
-    for b in range(min(a.cpu_frames, B)):
+    for b in range(min(a.cpu_frames, B) if a.dataset == "kitti" else 0):
         t = time.perf_counter()
         spo.prepare_image(raw[b], 50, 0.5, H, W, ints[b], fac[b])
         cpu.append((time.perf_counter() - t) * 1e3)
-    print("batch %d: %d x %d images, %.0f points per record" % (B, raw.shape[1], raw.shape[2], float(np.mean(np.diff(host)))))
+    print("%s, batch %d: %d x %d images, %.0f points per record" % (a.dataset, B, raw.shape[1], raw.shape[2], float(np.mean(np.diff(host)))))
     for k, v in med.items():
         print("  %-22s %8.3f ms (eager, per-launch events)" % (k, v))
     print("  %-22s %8.3f ms (graph replay; %.3f ms per sample; %.1f MB algorithmic = %.2f %% of 8 TB/s)"
@@ -99,7 +114,7 @@ def main():
     cpu_ms = float(np.mean(cpu)) if cpu else None
     if cpu:
         print("  numpy oracle, image path only, one thread: %.1f ms per sample" % cpu_ms)
-    print(json.dumps(dict(metric="sample_prep_ms", B=B, total_ms=total, per_sample_ms=total / B, stages_ms=med, algorithmic_bytes=nbytes,
+    print(json.dumps(dict(metric="sample_prep_ms", dataset=a.dataset, B=B, total_ms=total, per_sample_ms=total / B, stages_ms=med, algorithmic_bytes=nbytes,
                           fraction_of_8TBs=nbytes / (total * 1e-3) / 8e12, cpu_oracle_image_ms_per_sample=cpu_ms)))
 
 
