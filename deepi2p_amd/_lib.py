@@ -150,6 +150,8 @@ _SIGS = {
     "di2p_sample_draws_ds": [ctypes.c_ulonglong, c_void_p, c_int, c_int, ctypes.POINTER(SampleOptT), c_int] + [c_void_p] * 10,
     "di2p_image_prepare_ds": [c_void_p, c_int, c_int, c_int, ctypes.POINTER(SampleOptT), c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
                               c_void_p, c_void_p, c_void_p],
+    "di2p_estimate_normals_cells": [c_void_p, c_int, c_int, c_double, c_int, c_double] + [c_void_p] * 5,
+    "di2p_compose_poses": [c_void_p, c_void_p, c_int, c_void_p, c_void_p],
 }
 _WS_SIGS = {        # <name>_workspace_bytes helpers returning long long
     "di2p_channel_reduce_workspace_bytes": [c_int] * 3,
@@ -166,7 +168,7 @@ _WS_SIGS = {        # <name>_workspace_bytes helpers returning long long
     "di2p_image_prepare_workspace_bytes": [c_int],
 }
 EXPORTS = sorted(list(_SIGS) + ["di2p_last_error", "di2p_version", "di2p_solve_workspace_bytes", "di2p_solver_set_profile_buffer", "di2p_pnp_workspace_bytes",
-                 "di2p_conv2d_workspace_bytes", "di2p_set_option", "di2p_get_option", "di2p_random_choice_workspace_bytes", "di2p_classifier_loss_workspace_bytes"] + list(_WS_SIGS))
+                 "di2p_conv2d_workspace_bytes", "di2p_set_option", "di2p_get_option", "di2p_random_choice_workspace_bytes", "di2p_classifier_loss_workspace_bytes", "di2p_normals_cells_candidates"] + list(_WS_SIGS))
 
 
 def load():
@@ -198,6 +200,8 @@ def load():
             fn = getattr(lib, name)
             fn.argtypes = args
             fn.restype = c_ll
+        lib.di2p_normals_cells_candidates.restype = c_int
+        lib.di2p_normals_cells_candidates.argtypes = []
         lib.di2p_set_option.restype = c_int
         lib.di2p_set_option.argtypes = [ctypes.c_char_p, c_ll]
         lib.di2p_get_option.restype = c_ll

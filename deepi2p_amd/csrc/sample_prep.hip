@@ -295,6 +295,22 @@ __global__ __launch_bounds__(256) void transform_segments_kernel(const float* pt
     }
 }
 
+// ---------------------------------------------------------------- e. pose composition: one thread per frame
+__global__ __launch_bounds__(64) void compose_poses_kernel(const double* A, const double* Bm, double* out, int n) {          // no __restrict__: out may be A or Bm
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= n) return;
+    const double* a = A + 16 * (long long)b;
+    const double* m = Bm + 16 * (long long)b;
+    double r[16];
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            double acc = __dmul_rn(a[4 * i], m[j]);
+            for (int k = 1; k < 4; ++k) acc = __dadd_rn(acc, __dmul_rn(a[4 * i + k], m[4 * k + j]));
+            r[4 * i + j] = acc;
+        }
+    for (int i = 0; i < 16; ++i) out[16 * (long long)b + i] = r[i];          // out may be A or Bm
+}
+
 const char* check_opt(const di2p_sample_opt_t* o, bool any_scale = false) {
     if (!o) return "null option block";
     if (o->mode < 0 || o->mode > 2) return "bad mode (0 train, 1 val, 2 val_random_Ry)";
@@ -404,5 +420,13 @@ extern "C" int di2p_transform_segments(const float* points, const float* normals
     const int blocks = max(1, min(di2p_cdiv(di2p_cdiv(total, S), 256), 256));
     hipLaunchKernelGGL(transform_segments_kernel, dim3(blocks, S), dim3(256), 0, (hipStream_t)stream, points, normals, seg_offsets, transforms,
                        points_out, normals_out, total);
+    DI2P_RETURN_LAUNCH();
+}
+
+extern "C" int di2p_compose_poses(const double* A, const double* Bm, int n, double* out, void* stream) {
+    DI2P_CHECK_ARG(n >= 0, "bad size");
+    DI2P_CHECK_ARG(n == 0 || (A && Bm && out), "null pointer");
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(compose_poses_kernel, dim3(di2p_cdiv(n, 64)), dim3(64), 0, (hipStream_t)stream, A, Bm, out, n);
     DI2P_RETURN_LAUNCH();
 }

@@ -26,6 +26,9 @@ constexpr int MAX_FRAME_POINTS = 1 << 20;
 constexpr unsigned long long PAD_KEY = (1ull << 63) - 1;
 constexpr int NN_MAX = 64;
 constexpr int NN_CAP = 1024;          // LDS candidate buffer of one query (entries); compacted to the best max_nn when full
+constexpr int CELL_WAVES = 4;          // normals_cells_kernel: waves of a workgroup, each on a query of its own
+constexpr int CELL_CAND = 960;         // ... candidate capacity of a cell in LDS (entries: fp64 position + frame-local index, 28 B)
+constexpr int CELL_NN_CAP = 256;       // ... LDS candidate list of one wave (entries); compacted like the per-query kernel's
 constexpr int ST_OK = 0, ST_TOO_MANY = 1, ST_SPAN = 2, ST_OFFSETS = 3;
 
 __device__ __forceinline__ unsigned long long compose_key(long long ix, long long iy, long long iz) {
@@ -57,7 +60,9 @@ struct Layout {
     size_t pfr, key, iota, k1, i1, f1, f2, i2, k2;         // per raw point (cap)
     size_t head, scan, vstart, vfr, cen;                   // per voxel (cap + 1)
     size_t ck, ci2, ck2, cpos;                             // cell sort of the centroids
-    size_t tmp, tmp_bytes, total;
+    size_t tmp, tmp_bytes;
+    size_t chead, cscan, cstart, ncell;                    // cell runs of the sorted centroids (cap + 1 each; i32[1]): behind everything else
+    size_t total;
 };
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -76,6 +81,7 @@ Layout layout(int B, int cap) {
     L.ck = take(8 * n); L.ci2 = take(4 * n); L.ck2 = take(8 * n); L.cpos = take(8 * 3 * n);
     L.tmp_bytes = sort_tmp_bound(cap);
     L.tmp = take(L.tmp_bytes);
+    L.chead = take(4 * n1); L.cscan = take(4 * n1); L.cstart = take(4 * n1); L.ncell = take(4);
     L.total = o;
     return L;
 }
@@ -216,7 +222,9 @@ __global__ __launch_bounds__(256) void voxel_mean_kernel(const float* __restrict
             if (out_key) out_key[v] = (long long)key[gi];
             continue;
         }
-        const int s = vstart[v], e = vstart[v + 1];
+        // the members end where the next voxel starts, and at the frame's end: the points of a REJECTED frame that follows sit between this
+        // frame's last voxel and the next head (they start no voxel) and must not be averaged into it
+        const int s = vstart[v], e = min(vstart[v + 1], off[b + 1]);
         cnt = e - s;
         k = skey[s];
         for (int j = s; j < e; ++j) {
@@ -278,12 +286,25 @@ __device__ __forceinline__ bool nn_less(unsigned long long da, int ia, unsigned 
     return da < db || (da == db && ia < ib);
 }
 
+// Barrier between the LDS accesses of the lanes that share a candidate list: the workgroup's when it is one wave (normals_kernel), else
+// a wave-level one (normals_cells_kernel: the waves of a workgroup work on different queries and never meet inside one).  A wave's LDS
+// instructions execute in order; the fences keep the compiler from moving or merging accesses across the point.
+template <bool kWave> __device__ __forceinline__ void nn_sync() {
+    if (kWave) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    } else {
+        __syncthreads();
+    }
+}
+
 // bitonic sort of n2 (power of two >= cnt) entries of the LDS list, padding [cnt, n2) with +inf first; one wave
-__device__ void nn_sort(unsigned long long* sd, int* si, int cnt, int lane) {
+template <bool kWave> __device__ void nn_sort(unsigned long long* sd, int* si, int cnt, int lane) {
     int n2 = 64;
     while (n2 < cnt) n2 <<= 1;
     for (int i = cnt + lane; i < n2; i += 64) { sd[i] = ~0ull; si[i] = 0x7fffffff; }
-    __syncthreads();
+    nn_sync<kWave>();
     for (int k = 2; k <= n2; k <<= 1) {
         for (int j = k >> 1; j > 0; j >>= 1) {
             for (int t = lane; t < n2 / 2; t += 64) {
@@ -294,7 +315,7 @@ __device__ void nn_sort(unsigned long long* sd, int* si, int cnt, int lane) {
                 const int ia = si[i], ic = si[l];
                 if (nn_less(c, ic, a, ia) == up) { sd[i] = c; sd[l] = a; si[i] = ic; si[l] = ia; }
             }
-            __syncthreads();
+            nn_sync<kWave>();
         }
     }
 }
@@ -340,6 +361,35 @@ __device__ void smallest_eigvec(double a00, double a01, double a02, double a11, 
     nx = m == 0 ? V[0][0] : m == 1 ? V[0][1] : V[0][2];
     ny = m == 0 ? V[1][0] : m == 1 ? V[1][1] : V[1][2];
     nz = m == 0 ? V[2][0] : m == 1 ? V[2][1] : V[2][2];
+}
+
+// From the sorted candidate list of query v to its stored normal (one wave; rank t in lane t): the neighbour outputs, the mean and the
+// six covariance sums by the wave_sum butterfly, the eigenvector, the orientation rule.  Shared by both normals kernels.
+__device__ __forceinline__ void normal_from_list(const double* __restrict__ cen, const int* si, int cnt, int max_nn, int fs, int v, int lane,
+                                                 float* __restrict__ normals, int* __restrict__ nn_count, int* __restrict__ nn_idx) {
+    const int k = cnt < max_nn ? cnt : max_nn;
+    if (nn_idx)
+        for (int t = lane; t < max_nn; t += 64) nn_idx[(long long)v * max_nn + t] = t < k ? si[t] : -1;
+    if (nn_count && lane == 0) nn_count[v] = k;
+    double px = 0.0, py = 0.0, pz = 0.0;
+    if (lane < k) {
+        const long long g = (long long)fs + si[lane];
+        px = cen[3 * g + 0]; py = cen[3 * g + 1]; pz = cen[3 * g + 2];
+    }
+    const double dk = (double)k;
+    const double mx = wave_sum(px) / dk, my = wave_sum(py) / dk, mz = wave_sum(pz) / dk;
+    const double ex = lane < k ? px - mx : 0.0, ey = lane < k ? py - my : 0.0, ez = lane < k ? pz - mz : 0.0;
+    const double cxx = wave_sum(ex * ex), cxy = wave_sum(ex * ey), cxz = wave_sum(ex * ez);
+    const double cyy = wave_sum(ey * ey), cyz = wave_sum(ey * ez), czz = wave_sum(ez * ez);
+    double nx = 0.0, ny = 0.0, nz = 0.0;
+    if (k >= 3 && (cxx != 0.0 || cxy != 0.0 || cxz != 0.0 || cyy != 0.0 || cyz != 0.0 || czz != 0.0))
+        smallest_eigvec(cxx, cxy, cxz, cyy, cyz, czz, nx, ny, nz);
+    // orient_normals_to_align_with_direction([0,0,1]): a zero normal becomes the direction, n . dir < 0 flips
+    if (nx == 0.0 && ny == 0.0 && nz == 0.0) { nz = 1.0; }
+    else if (nz < 0.0) { nx = -nx; ny = -ny; nz = -nz; }
+    if (lane == 0) {
+        normals[3 * (long long)v + 0] = (float)nx; normals[3 * (long long)v + 1] = (float)ny; normals[3 * (long long)v + 2] = (float)nz;
+    }
 }
 
 // One wave (workgroup of 64) per query centroid, persistent over the batch.  The 27 neighbour cells (9 key ranges of 3 z-adjacent cells)
@@ -401,37 +451,148 @@ __global__ __launch_bounds__(64) void normals_kernel(const double* __restrict__ 
                 cnt += __popcll(m);
                 __syncthreads();
                 if (cnt > NN_CAP - 64) {
-                    nn_sort(sd, si, cnt, lane);
+                    nn_sort<false>(sd, si, cnt, lane);
                     if (cnt >= max_nn) { thr_d = sd[max_nn - 1]; thr_i = si[max_nn - 1]; cnt = max_nn; }
                     __syncthreads();
                 }
             }
         }
-        nn_sort(sd, si, cnt, lane);
-        const int k = cnt < max_nn ? cnt : max_nn;
-        if (nn_idx)
-            for (int t = lane; t < max_nn; t += 64) nn_idx[(long long)v * max_nn + t] = t < k ? si[t] : -1;
-        if (nn_count && lane == 0) nn_count[v] = k;
-        double px = 0.0, py = 0.0, pz = 0.0;
-        if (lane < k) {
-            const long long g = (long long)fs + si[lane];
-            px = cen[3 * g + 0]; py = cen[3 * g + 1]; pz = cen[3 * g + 2];
-        }
-        const double dk = (double)k;
-        const double mx = wave_sum(px) / dk, my = wave_sum(py) / dk, mz = wave_sum(pz) / dk;
-        const double ex = lane < k ? px - mx : 0.0, ey = lane < k ? py - my : 0.0, ez = lane < k ? pz - mz : 0.0;
-        const double cxx = wave_sum(ex * ex), cxy = wave_sum(ex * ey), cxz = wave_sum(ex * ez);
-        const double cyy = wave_sum(ey * ey), cyz = wave_sum(ey * ez), czz = wave_sum(ez * ez);
-        double nx = 0.0, ny = 0.0, nz = 0.0;
-        if (k >= 3 && (cxx != 0.0 || cxy != 0.0 || cxz != 0.0 || cyy != 0.0 || cyz != 0.0 || czz != 0.0))
-            smallest_eigvec(cxx, cxy, cxz, cyy, cyz, czz, nx, ny, nz);
-        // orient_normals_to_align_with_direction([0,0,1]): a zero normal becomes the direction, n . dir < 0 flips
-        if (nx == 0.0 && ny == 0.0 && nz == 0.0) { nz = 1.0; }
-        else if (nz < 0.0) { nx = -nx; ny = -ny; nz = -nz; }
-        if (lane == 0) {
-            normals[3 * (long long)v + 0] = (float)nx; normals[3 * (long long)v + 1] = (float)ny; normals[3 * (long long)v + 2] = (float)nz;
+        nn_sort<false>(sd, si, cnt, lane);
+        normal_from_list(cen, si, cnt, max_nn, fs, v, lane, normals, nn_count, nn_idx);
+        __syncthreads();
+    }
+}
+
+// ---- cell-cooperative normals
+// head[j] = 1 where sorted position j starts a cell: a run of equal (frame, cell key) among the centroids
+__global__ __launch_bounds__(256) void cell_heads_kernel(const unsigned* __restrict__ sfr, const unsigned long long* __restrict__ ck2,
+                                                         const int* __restrict__ nvox_p, int cap, int* __restrict__ head) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j > cap) return;
+    const int nvox = min(max(*nvox_p, 0), cap);
+    head[j] = j < nvox && (j == 0 || sfr[j] != sfr[j - 1] || ck2[j] != ck2[j - 1]);
+}
+
+// cstart[c] = first sorted position of cell c, cstart[ncell] = nvox
+__global__ __launch_bounds__(256) void cell_starts_kernel(const int* __restrict__ head, const int* __restrict__ scan, const int* __restrict__ nvox_p,
+                                                          int cap, int* __restrict__ cstart, int* __restrict__ ncell) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j > cap) return;
+    const int nvox = min(max(*nvox_p, 0), cap);
+    if (j < nvox && head[j]) cstart[scan[j]] = j;
+    if (j == nvox) { cstart[scan[j]] = nvox; *ncell = scan[j]; }
+}
+
+// One candidate of one wave's query: the per-query kernel's acceptance rule and list handling on the wave's own LDS list.
+__device__ __forceinline__ void nn_offer(bool in, double d2, int li, double r2, int max_nn, unsigned long long* sd, int* si, int& cnt,
+                                         unsigned long long& thr_d, int& thr_i, int lane) {
+    const unsigned long long db = (unsigned long long)__double_as_longlong(d2);
+    const bool acc = in && d2 < r2 && nn_less(db, li, thr_d, thr_i);
+    const unsigned long long m = __ballot(acc);
+    if (acc) {
+        const int pos = cnt + __popcll(m & ((1ull << lane) - 1));
+        sd[pos] = db; si[pos] = li;
+    }
+    cnt += __popcll(m);
+    if (cnt > CELL_NN_CAP - 64) {       // (> max_nn: always cut back)
+        nn_sort<true>(sd, si, cnt, lane);
+        if (cnt >= max_nn) { thr_d = sd[max_nn - 1]; thr_i = si[max_nn - 1]; cnt = max_nn; }
+        nn_sync<true>();
+    }
+}
+
+// One workgroup (CELL_WAVES waves) per occupied grid cell, persistent over the batch.  Once per cell: the 9 key ranges of the 27 neighbour
+// cells by binary search (18 threads), their members staged into LDS (fp64 position + frame-local index).  Then every wave takes
+// queries of the cell in turn and selects from the staged set exactly as normals_kernel does from global memory: the same acceptance
+// rule, an LDS list per wave cut back to the best max_nn when it fills, the same final sort and the same tail (normal_from_list), so
+// the outputs are the per-query kernel's bit for bit (the selection is exact, hence independent of the candidate order and the list size).
+// A cell whose candidate set exceeds CELL_CAND is not staged: its queries stream the ranges from global memory.
+__global__ __launch_bounds__(CELL_WAVES * 64) void normals_cells_kernel(const double* __restrict__ cen, const double* __restrict__ cpos,
+                                                                        const int* __restrict__ ci2, const unsigned long long* __restrict__ ck2,
+                                                                        const unsigned* __restrict__ sfr, const int* __restrict__ cstart,
+                                                                        const int* __restrict__ ncell_p, const int* __restrict__ out_off, int B,
+                                                                        double r2, int max_nn, float* __restrict__ normals,
+                                                                        int* __restrict__ nn_count, int* __restrict__ nn_idx) {
+    __shared__ double cx[CELL_CAND], cy[CELL_CAND], cz[CELL_CAND];
+    __shared__ int cli[CELL_CAND];
+    __shared__ unsigned long long sd_all[CELL_WAVES * CELL_NN_CAP];
+    __shared__ int si_all[CELL_WAVES * CELL_NN_CAP];
+    __shared__ int rs[9], re[9], pre[10];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    unsigned long long* sd = sd_all + w * CELL_NN_CAP;
+    int* si = si_all + w * CELL_NN_CAP;
+    const int ncell = *ncell_p;
+    for (int c = blockIdx.x; c < ncell; c += gridDim.x) {
+        const int s0 = cstart[c], s1 = cstart[c + 1];
+        const int b = min((int)sfr[s0], B - 1);
+        const int fs = out_off[b], fe = out_off[b + 1];
+        if (tid < 18) {
+            const unsigned long long key = ck2[s0];
+            const int r = tid % 9;
+            const bool upper = tid >= 9;
+            const long long kx = (long long)(key >> (2 * AXIS_BITS)) + r % 3 - 1;
+            const long long ky = (long long)((key >> AXIS_BITS) & AXIS_MAX) + r / 3 - 1;
+            const long long kz = (long long)(key & AXIS_MAX);
+            int pos = fs;
+            if (kx >= 0 && ky >= 0 && kx <= AXIS_MAX && ky <= AXIS_MAX) {
+                const unsigned long long k = upper ? compose_key(kx, ky, kz + 1 < AXIS_MAX ? kz + 1 : AXIS_MAX) : compose_key(kx, ky, kz > 0 ? kz - 1 : 0);
+                int lo = fs, hi = fe;
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (upper ? ck2[mid] <= k : ck2[mid] < k) lo = mid + 1; else hi = mid;
+                }
+                pos = lo;
+            }
+            (upper ? re : rs)[r] = pos;
         }
         __syncthreads();
+        if (tid == 0) {
+            int a = 0;
+            for (int r = 0; r < 9; ++r) { pre[r] = a; a += re[r] - rs[r]; }
+            pre[9] = a;
+        }
+        __syncthreads();
+        const int total = pre[9];
+        const bool staged = total <= CELL_CAND;
+        if (staged) {
+            for (int t = tid; t < total; t += CELL_WAVES * 64) {
+                int r = 0;
+                while (r < 8 && t >= pre[r + 1]) ++r;
+                const long long j = rs[r] + (t - pre[r]);
+                cx[t] = cpos[3 * j + 0]; cy[t] = cpos[3 * j + 1]; cz[t] = cpos[3 * j + 2];
+                cli[t] = ci2[j] - fs;
+            }
+        }
+        __syncthreads();
+        for (int q = s0 + w; q < s1; q += CELL_WAVES) {
+            const int v = ci2[q];
+            const double qx = cpos[3 * (long long)q + 0], qy = cpos[3 * (long long)q + 1], qz = cpos[3 * (long long)q + 2];   // = cen[3 v + .]
+            int cnt = 0;
+            unsigned long long thr_d = ~0ull;
+            int thr_i = 0x7fffffff;
+            if (staged) {
+                for (int base = 0; base < total; base += 64) {
+                    const int t = base + lane;
+                    const bool in = t < total;
+                    const double d2 = in ? d2_of(cx[t], cy[t], cz[t], qx, qy, qz) : 0.0;
+                    nn_offer(in, d2, in ? cli[t] : 0, r2, max_nn, sd, si, cnt, thr_d, thr_i, lane);
+                }
+            } else {
+                for (int r = 0; r < 9; ++r) {
+                    const int e = re[r];
+                    for (int base = rs[r]; base < e; base += 64) {
+                        const int j = base + lane;
+                        const bool in = j < e;
+                        const double d2 = in ? d2_of(cpos[3 * (long long)j + 0], cpos[3 * (long long)j + 1], cpos[3 * (long long)j + 2], qx, qy, qz) : 0.0;
+                        nn_offer(in, d2, in ? ci2[j] - fs : 0, r2, max_nn, sd, si, cnt, thr_d, thr_i, lane);
+                    }
+                }
+            }
+            nn_sort<true>(sd, si, cnt, lane);
+            normal_from_list(cen, si, cnt, max_nn, fs, v, lane, normals, nn_count, nn_idx);
+            nn_sync<true>();
+        }
+        __syncthreads();          // the next cell's staging overwrites what the other waves may still read
     }
 }
 
@@ -685,31 +846,78 @@ extern "C" int di2p_voxel_down_sample(const float* points, const int32_t* offset
     DI2P_RETURN_LAUNCH();
 }
 
-extern "C" int di2p_estimate_normals(const int32_t* voxel_offsets, int B, int cap, double radius, int max_nn, double max_extent, float* normals,
-                                     int32_t* nn_count, int32_t* nn_idx, void* workspace, void* stream) {
-    DI2P_CHECK_ARG(B >= 0 && cap >= 0, "bad sizes (B >= 0, cap >= 0)");
-    DI2P_CHECK_ARG(radius > 0.0 && radius < 1e30, "radius must be positive and finite");
-    DI2P_CHECK_ARG(max_nn >= 1 && max_nn <= NN_MAX, "max_nn must be in [1, 64]");
-    DI2P_CHECK_ARG(max_extent >= 0.0 && max_extent / radius < (double)AXIS_MAX - 4.0, "grid cell index span above 2^21 per axis (max_extent / radius)");
-    DI2P_CHECK_ARG(B == 0 || (voxel_offsets && normals && workspace), "null pointer");
-    DI2P_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
-    if (B == 0 || cap == 0) return 0;
-    const Layout L = layout(B, cap);
-    hipStream_t st = (hipStream_t)stream;
+namespace {
+
+// Shared front of the two normals entry points: argument checks, cell keys, the (frame, key) sort, positions in sorted order.
+// -> 0 to go on, 1 when there is nothing to do, else the error code
+int normals_front(const char* fn, const int32_t* voxel_offsets, int B, int cap, double radius, int max_nn, double max_extent, float* normals,
+                  void* workspace, hipStream_t st, Layout& L, double& cell) {
+#define FRONT_CHECK(cond, msg) do { if (!(cond)) { di2p_set_error("%s: %s", fn, msg); return -1; } } while (0)
+    FRONT_CHECK(B >= 0 && cap >= 0, "bad sizes (B >= 0, cap >= 0)");
+    FRONT_CHECK(radius > 0.0 && radius < 1e30, "radius must be positive and finite");
+    FRONT_CHECK(max_nn >= 1 && max_nn <= NN_MAX, "max_nn must be in [1, 64]");
+    FRONT_CHECK(max_extent >= 0.0 && max_extent / radius < (double)AXIS_MAX - 4.0, "grid cell index span above 2^21 per axis (max_extent / radius)");
+    FRONT_CHECK(B == 0 || (voxel_offsets && normals && workspace), "null pointer");
+    FRONT_CHECK(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
+#undef FRONT_CHECK
+    if (B == 0 || cap == 0) return 1;
+    L = layout(B, cap);
     void* ws = workspace;
-    const double cell = radius * (1.0 + 1.0 / 1048576.0);
+    cell = radius * (1.0 + 1.0 / 1048576.0);
     // cell keys into L.ck, frames into L.pfr (the raw frames are no longer needed: the raw sort result lives in i2 / k2 / f2)
     hipLaunchKernelGGL(cell_keys_kernel, dim3(di2p_cdiv(cap, 256)), dim3(256), 0, st, at<double>(ws, L.cen), voxel_offsets, B, cap, at<int>(ws, L.nvox),
                        at<double>(ws, L.minb), cell, at<unsigned>(ws, L.pfr), at<unsigned long long>(ws, L.ck), at<int>(ws, L.iota));
     // the frame-sorted output goes to f1's twin: reuse L.head (i32, cap + 1) for the sorted frames; it is not read after stage 1
     const hipError_t e = sort_by_frame_key(ws, L, B, cap, at<unsigned long long>(ws, L.ck), at<unsigned>(ws, L.pfr), at<int>(ws, L.ci2),
                                            at<unsigned long long>(ws, L.ck2), at<unsigned>(ws, L.head), st);
-    if (e != hipSuccess) { di2p_set_error("di2p_estimate_normals: sort failed: %s", hipGetErrorString(e)); return (int)e; }
+    if (e != hipSuccess) { di2p_set_error("%s: sort failed: %s", fn, hipGetErrorString(e)); return (int)e; }
     hipLaunchKernelGGL(cell_positions_kernel, dim3(di2p_cdiv(cap, 256)), dim3(256), 0, st, at<double>(ws, L.cen), at<int>(ws, L.ci2),
                        at<int>(ws, L.nvox), at<double>(ws, L.cpos));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int di2p_estimate_normals(const int32_t* voxel_offsets, int B, int cap, double radius, int max_nn, double max_extent, float* normals,
+                                     int32_t* nn_count, int32_t* nn_idx, void* workspace, void* stream) {
+    Layout L;
+    double cell;
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = normals_front("di2p_estimate_normals", voxel_offsets, B, cap, radius, max_nn, max_extent, normals, workspace, st, L, cell);
+    if (rc) return rc == 1 ? 0 : rc;
+    void* ws = workspace;
     hipLaunchKernelGGL(normals_kernel, dim3(min(cap, persistent_grid(32))), dim3(64), 0, st, at<double>(ws, L.cen), at<double>(ws, L.cpos),
                        at<int>(ws, L.ci2), at<unsigned long long>(ws, L.ck2), voxel_offsets, B, at<int>(ws, L.nvox), at<double>(ws, L.minb), cell,
                        radius * radius, max_nn, normals, nn_count, nn_idx);
+    DI2P_RETURN_LAUNCH();
+}
+
+extern "C" int di2p_normals_cells_candidates(void) { return CELL_CAND; }
+
+extern "C" int di2p_estimate_normals_cells(const int32_t* voxel_offsets, int B, int cap, double radius, int max_nn, double max_extent,
+                                           float* normals, int32_t* nn_count, int32_t* nn_idx, void* workspace, void* stream) {
+    Layout L;
+    double cell;
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = normals_front("di2p_estimate_normals_cells", voxel_offsets, B, cap, radius, max_nn, max_extent, normals, workspace, st, L, cell);
+    if (rc) return rc == 1 ? 0 : rc;
+    void* ws = workspace;
+    // the cells: runs of equal (frame, key) in the sorted order -> their start positions (flags, exclusive scan, scatter)
+    hipLaunchKernelGGL(cell_heads_kernel, dim3(di2p_cdiv(cap + 1, 256)), dim3(256), 0, st, at<unsigned>(ws, L.head), at<unsigned long long>(ws, L.ck2),
+                       at<int>(ws, L.nvox), cap, at<int>(ws, L.chead));
+    size_t need = 0;
+    hipError_t e = rocprim::exclusive_scan(nullptr, need, at<int>(ws, L.chead), at<int>(ws, L.cscan), 0, (size_t)cap + 1, rocprim::plus<int>(), st);
+    if (e == hipSuccess && need > L.tmp_bytes) e = hipErrorInvalidValue;
+    if (e == hipSuccess) {
+        need = L.tmp_bytes;
+        e = rocprim::exclusive_scan(at<void>(ws, L.tmp), need, at<int>(ws, L.chead), at<int>(ws, L.cscan), 0, (size_t)cap + 1, rocprim::plus<int>(), st);
+    }
+    if (e != hipSuccess) { di2p_set_error("di2p_estimate_normals_cells: scan failed: %s", hipGetErrorString(e)); return (int)e; }
+    hipLaunchKernelGGL(cell_starts_kernel, dim3(di2p_cdiv(cap + 1, 256)), dim3(256), 0, st, at<int>(ws, L.chead), at<int>(ws, L.cscan),
+                       at<int>(ws, L.nvox), cap, at<int>(ws, L.cstart), at<int>(ws, L.ncell));
+    hipLaunchKernelGGL(normals_cells_kernel, dim3(min(cap, persistent_grid(4))), dim3(CELL_WAVES * 64), 0, st, at<double>(ws, L.cen),
+                       at<double>(ws, L.cpos), at<int>(ws, L.ci2), at<unsigned long long>(ws, L.ck2), at<unsigned>(ws, L.head), at<int>(ws, L.cstart),
+                       at<int>(ws, L.ncell), voxel_offsets, B, radius * radius, max_nn, normals, nn_count, nn_idx);
     DI2P_RETURN_LAUNCH();
 }
 

@@ -42,6 +42,7 @@ class Slot:
         self.outputs = None
         self.busy = False
         self.host_flat, self.dev_flats = None, []         # ONE pinned staging buffer / ONE device buffer per input set: host[k] / devs[j][k] are views
+        self.copy_bytes = None                            # copy_in moves this many leading bytes of the staging buffer (None: all of it)
 
     @property
     def dev(self):
@@ -50,7 +51,11 @@ class Slot:
     def copy_in(self, j=None):
         """The step's host->device transfer of ALL inputs of the slot: one asynchronous copy of the flat staging buffer (seven tensors, one
         DMA command) on the current stream."""
-        self.dev_flats[self.cur if j is None else j].copy_(self.host_flat, non_blocking=True)
+        dst = self.dev_flats[self.cur if j is None else j]
+        if self.copy_bytes is None:
+            dst.copy_(self.host_flat, non_blocking=True)
+        else:
+            dst[:self.copy_bytes].copy_(self.host_flat[:self.copy_bytes], non_blocking=True)
 
 
 def _flat_views(flat, layout):
@@ -106,7 +111,7 @@ class RegistrationExecutor:
         self.n_streams = max(1, int(n_streams))
         self.use_graph = bool(use_graph)
         self.labels_override = labels_override
-        B = int(example_batch["pc"].shape[0])
+        B = self._batch_size(example_batch)
         self.K64 = K.to(self.device, torch.float64).contiguous()
         if self.K64.dim() == 2:
             self.K64 = self.K64.unsqueeze(0).expand(B, 3, 3).contiguous()
@@ -148,8 +153,7 @@ class RegistrationExecutor:
             s.copied = torch.cuda.Event()
             # one flat pinned buffer and one flat device buffer hold all seven inputs (256-byte aligned pieces): a step's transfer is ONE copy
             layout, off = [], 0
-            for k in INPUT_NAMES + (K_NAME,):
-                shape, dtype = ((B, 3, 3), torch.float64) if k == K_NAME else (tuple(example_batch[k].shape), example_batch[k].dtype)
+            for k, shape, dtype in self._staged_inputs(example_batch, B):
                 n = 1
                 for v in shape:
                     n *= int(v)
@@ -157,21 +161,53 @@ class RegistrationExecutor:
                 off = (off + n * torch.empty((), dtype=dtype).element_size() + 255) // 256 * 256
             s.host_flat = torch.empty((off,), dtype=torch.uint8).pin_memory()
             s.host = _flat_views(s.host_flat, layout)
-            for k in INPUT_NAMES:
-                s.host[k].copy_(example_batch[k])
-            s.host[K_NAME].copy_(self._K64_host)
+            self._stage_example(s, example_batch)
             n_sets = 2 if self.double_buffer else 1
             s.devs = []
             for _ in range(n_sets):
                 flat = s.host_flat.to(self.device, non_blocking=False)
                 s.dev_flats.append(flat)
                 s.devs.append(_flat_views(flat, layout))
+            self._slot_ready(s)
             self.slots.append(s)
         self._next = 0
         self._h2d_warm = False
         self._replayed = set()
         self._warmed = set()
         torch.cuda.synchronize(self.device)
+
+    # ------------------------------------------------------------------------------------------------------------ staged inputs
+    # What a host batch is and how it reaches a slot's pinned staging buffer; a subclass with other inputs (raw_pipeline.RawFrameExecutor)
+    # overrides these four and _slot_ready.
+    def _batch_size(self, example_batch):
+        return int(example_batch["pc"].shape[0])
+
+    def _staged_inputs(self, example_batch, B):
+        """[(name, shape, dtype)] of the pieces of a slot's flat staging buffer, in order"""
+        return [(k, tuple(example_batch[k].shape), example_batch[k].dtype) for k in INPUT_NAMES] + [(K_NAME, (B, 3, 3), torch.float64)]
+
+    def _validate(self, slot, host_batch):
+        """Raise for a host batch this executor was not built for; nothing has been enqueued or consumed yet."""
+        for k in INPUT_NAMES + ((K_NAME,) if K_NAME in host_batch else ()):
+            if tuple(host_batch[k].shape) != tuple(slot.host[k].shape):
+                raise ValueError("host batch %r has shape %s, this executor was built (and its graphs captured) for %s -- pad the batch "
+                                 "or build an executor for that shape" % (k, tuple(host_batch[k].shape), tuple(slot.host[k].shape)))
+
+    def _stage(self, slot, host_batch):
+        """Copy a (validated) host batch into the slot's pinned staging buffer."""
+        for k in INPUT_NAMES:
+            slot.host[k].copy_(host_batch[k])
+        if K_NAME in host_batch:
+            slot.host[K_NAME].copy_(host_batch[K_NAME])       # f32 -> f64 on the way into the pinned buffer
+        else:
+            slot.host[K_NAME].copy_(self._K64_host)           # no K in this batch: the constructor's, not what the slot last held
+
+    def _stage_example(self, slot, example_batch):
+        """The slot's first contents: the example's six inputs and the constructor's K."""
+        self._stage(slot, {k: example_batch[k] for k in INPUT_NAMES})
+
+    def _slot_ready(self, slot):
+        """Called once per slot when its buffers exist."""
 
     # ------------------------------------------------------------------------------------------------------------ one step
     def _step(self, slot, with_h2d):
@@ -314,10 +350,7 @@ class RegistrationExecutor:
             self.warm_up(with_h2d)                # first use: captures, first replays, first copies (synchronises the device once)
         slot = self.slots[self._next]
         if host_batch is not None:                # validate BEFORE the slot position advances: a rejected submit consumes nothing
-            for k in INPUT_NAMES + ((K_NAME,) if K_NAME in host_batch else ()):
-                if tuple(host_batch[k].shape) != tuple(slot.host[k].shape):
-                    raise ValueError("host batch %r has shape %s, this executor was built (and its graphs captured) for %s -- pad the batch "
-                                     "or build an executor for that shape" % (k, tuple(host_batch[k].shape), tuple(slot.host[k].shape)))
+            self._validate(slot, host_batch)
             if not with_h2d:
                 raise ValueError("a host batch needs with_h2d=True (its copies are part of the step)")
         self._next = (self._next + 1) % self.n_streams
@@ -326,13 +359,7 @@ class RegistrationExecutor:
             # stream; otherwise they are part of the step)
             (slot.copied if self.h2d_mode == "copy_stream" and self.double_buffer else slot.done).synchronize()
         if host_batch is not None:
-            for k in INPUT_NAMES:
-                slot.host[k].copy_(host_batch[k])
-            if K_NAME in host_batch:
-                slot.host[K_NAME].copy_(host_batch[K_NAME])       # f32 -> f64 on the way into the pinned buffer
-            else:
-                slot.host[K_NAME].copy_(self._K64_host)           # no K in this batch: the constructor's, not what the slot last held
-        names = INPUT_NAMES + (K_NAME,)
+            self._stage(slot, host_batch)
         in_step = with_h2d and self.h2d_mode == "graph"
         if with_h2d and self.h2d_mode == "copy_stream":
             if self.double_buffer:

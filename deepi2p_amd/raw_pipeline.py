@@ -1,0 +1,151 @@
+"""Raw-frame executor: "here is a scan and a camera frame, give me the pose" on the machinery of pipeline.RegistrationExecutor.
+
+One STEP = H2D copy of the raw batch -> raw_prep.RawFramePlan (voxel grid, normals, nearest-raw intensity, the loader's sample
+preparation, image path) -> classifier -> pose solve (Gauss-Newton restarts or PnP-RANSAC) -> P_scan = P . T_scan.  Streams, slots,
+pinned staging, copy streams, one captured graph per slot, weight following and submit / result tickets are the base class's; this
+class only describes other staged inputs and puts the preparation in front of the step.
+"""
+import numpy as np
+import torch
+
+from . import raw_prep
+from ._lib import call, ptr, stream
+from .pipeline import INPUT_NAMES, K_NAME, RegistrationExecutor
+
+
+def host_frames(host_batch, B, cap_raw, raw_hw):
+    """Check a raw host batch against the shapes an executor was built for and bring it to its staged form; host-only, raises ValueError
+    before anything is enqueued.  host_batch: dict with `scans` (a list of B [n_b,4] float32 arrays, or a flat [total,4] array plus
+    `offsets` [B+1]), `image` u8[B,H,W,3], `K_raw` [B,3,3], `Pc` [B,4,4] and optionally `seed`.  Scans of another dtype than float32 raise
+    in both forms (nothing is cast silently).
+    -> (points: list of f32 tensors [n,4] to lay end to end, offsets i32[B+1] tensor, image, K_raw f64, Pc f64, seed int)"""
+    for k in ("scans", "image", "K_raw", "Pc"):
+        if k not in host_batch:
+            raise ValueError("raw host batch has no %r (scans, image, K_raw, Pc[, offsets, seed])" % k)
+    scans = host_batch["scans"]
+    if isinstance(scans, (list, tuple)):
+        parts = [torch.as_tensor(s) for s in scans]
+        if any(p.dim() != 2 or p.shape[1] != 4 for p in parts):
+            raise ValueError("raw host batch: every scan must be [n, 4] (x, y, z, intensity)")
+        counts = [int(p.shape[0]) for p in parts]
+        offsets = torch.tensor(np.concatenate([[0], np.cumsum(counts)]), dtype=torch.int32)
+    else:
+        if host_batch.get("offsets") is None:
+            raise ValueError("raw host batch: a flat `scans` array needs `offsets` [B+1]")
+        flat = torch.as_tensor(scans)
+        if flat.dim() != 2 or flat.shape[1] != 4:
+            raise ValueError("raw host batch: flat scans must be [total, 4], got %s" % (tuple(flat.shape),))
+        offsets = torch.as_tensor(np.asarray(host_batch["offsets"])).to(torch.int32).reshape(-1)
+        o = offsets.tolist()
+        if len(o) < 1 or o[0] != 0 or any(b < a for a, b in zip(o, o[1:])) or o[-1] > flat.shape[0]:
+            raise ValueError("raw host batch: offsets must start at 0, not decrease and end within the %d rows of scans" % flat.shape[0])
+        parts = [flat[:o[-1]]]
+    if offsets.shape[0] != B + 1:
+        raise ValueError("raw host batch has %d frames, this executor was built (and its graphs captured) for B = %d" % (offsets.shape[0] - 1, B))
+    total = int(offsets[-1])
+    if total > cap_raw:
+        raise ValueError("raw host batch has %d points in all, above the cap_raw = %d rows this executor stages" % (total, cap_raw))
+    for p in parts:
+        if p.dtype != torch.float32:
+            raise ValueError("raw host batch: scans must be float32")
+    image = torch.as_tensor(host_batch["image"])
+    want = (B, int(raw_hw[0]), int(raw_hw[1]), 3)
+    if image.dtype != torch.uint8 or tuple(image.shape) != want:
+        raise ValueError("raw host batch: image must be uint8 %s (this executor's graphs were captured for that shape), got %s %s"
+                         % (want, image.dtype, tuple(image.shape)))
+    K_raw, Pc = torch.as_tensor(host_batch["K_raw"]), torch.as_tensor(host_batch["Pc"])
+    if tuple(K_raw.shape) != (B, 3, 3) or tuple(Pc.shape) != (B, 4, 4):
+        raise ValueError("raw host batch: K_raw must be [%d,3,3] and Pc [%d,4,4], got %s and %s" % (B, B, tuple(K_raw.shape), tuple(Pc.shape)))
+    seed = host_batch.get("seed")
+    return parts, offsets, image, K_raw, Pc, 0 if seed is None else int(seed)
+
+
+class RawFrameExecutor(RegistrationExecutor):
+    """executor = RawFrameExecutor(mm, pipe, opt, example_batch, cap_raw, max_frame_points, n_streams=4)
+    ticket = executor.submit(host_batch)          # dict: scans, image, K_raw, Pc[, offsets, seed] (host_frames)
+    out = executor.result(ticket)                 # the base executor's outputs + status i32[B], T_scan, P_scan f64[B,4,4]
+
+    opt: the option bag of sample_prep (img_H / img_W / input_pt_num / node numbers must be the classifier's).  Fixed per executor: B, the
+    raw image shape, cap_raw (rows of the pinned staging buffer: a batch with more points in all raises) and max_frame_points (a longer
+    frame is rejected ON THE DEVICE: status != 0, its pose is whatever the solver makes of zeros, the other frames are unaffected).
+    P_scan = P . T_scan maps raw-scan coordinates into the camera frame.  The seed of the preparation's draws is staged with the batch and
+    read from device memory inside the graph."""
+
+    def __init__(self, mm, pipe, opt, example_batch, cap_raw, max_frame_points, n_streams=4, use_graph=True, restarts=None, samples=None,
+                 labels_override=None, mode="val", dataset="kitti", normals_method="query", h2d_mode="copy_stream", post_fn=None):
+        raw_prep._check_dataset(dataset)
+        from . import scan_prep
+        scan_prep._normals_entry(normals_method)
+        if h2d_mode not in ("copy_stream", "eager"):
+            raise ValueError("RawFrameExecutor: h2d_mode must be 'copy_stream' or 'eager' (a captured copy has a fixed size; the raw copy has not)")
+        image = torch.as_tensor(example_batch["image"])
+        if image.dim() != 4:
+            raise ValueError("raw host batch: image must be uint8 [B, H, W, 3]")
+        self.opt, self.mode, self.dataset, self.normals_method = opt, mode, dataset, normals_method
+        self.B, self.raw_hw = int(image.shape[0]), (int(image.shape[1]), int(image.shape[2]))
+        self.cap_raw, self.max_frame_points = int(cap_raw), int(max_frame_points)
+        host_frames(example_batch, self.B, self.cap_raw, self.raw_hw)
+        super().__init__(mm, pipe, torch.eye(3, dtype=torch.float64), example_batch, n_streams=n_streams, use_graph=use_graph, restarts=restarts,
+                         labels_override=labels_override, post_fn=post_fn, h2d_mode=h2d_mode, samples=samples)
+
+    # ---------------------------------------------------------------------------------------------------------- staged inputs
+    def _batch_size(self, example_batch):
+        return self.B
+
+    def _staged_inputs(self, example_batch, B):
+        H, W = self.raw_hw
+        # points LAST: a step copies the buffer only up to its last row in use
+        return [("offsets", (B + 1,), torch.int32), ("seed", (1,), torch.int64), ("K_raw", (B, 3, 3), torch.float64), ("Pc", (B, 4, 4), torch.float64),
+                ("image", (B, H, W, 3), torch.uint8), ("points", (max(self.cap_raw, 1), 4), torch.float32)]
+
+    def _validate(self, slot, host_batch):
+        self._checked = (host_batch, host_frames(host_batch, self.B, self.cap_raw, self.raw_hw))      # submit stages it next: converted once
+
+    def _stage(self, slot, host_batch):
+        checked, self._checked = getattr(self, "_checked", None), None
+        staged = checked[1] if checked is not None and checked[0] is host_batch else host_frames(host_batch, self.B, self.cap_raw, self.raw_hw)
+        parts, offsets, image, K_raw, Pc, seed = staged
+        h = slot.host
+        h["offsets"].copy_(offsets)
+        h["seed"].fill_(seed)
+        h["K_raw"].copy_(K_raw)
+        h["Pc"].copy_(Pc)
+        h["image"].copy_(image)
+        row = 0
+        for p in parts:
+            h["points"][row:row + p.shape[0]].copy_(p)
+            row += int(p.shape[0])
+        # rows past offsets[B] stay stale: they are not copied and no kernel reads them
+        slot.copy_bytes = h["points"].data_ptr() - slot.host_flat.data_ptr() + 16 * row
+
+    def _stage_example(self, slot, example_batch):
+        slot.host["points"].zero_()
+        self._stage(slot, example_batch)
+
+    def _slot_ready(self, slot):
+        d = slot.devs[0]
+        plan = raw_prep.RawFramePlan(self.opt, self.B, self.cap_raw, self.max_frame_points, self.raw_hw, self.mode, self.dataset,
+                                     self.normals_method, self.device)
+        plan.sample.seed = d["seed"]          # the draws read the staged seed where the copy puts it
+        slot.plan = plan
+        slot.K64 = torch.zeros((self.B, 3, 3), dtype=torch.float64, device=self.device)
+        slot.P_scan = torch.zeros((self.B, 4, 4), dtype=torch.float64, device=self.device)
+        p = plan.sample
+        # what _net_part / _solve_part read: the plan's outputs, in place
+        d.update(zip(INPUT_NAMES, (p.points.pc, p.points.intensity, p.points.sn, p.points.nodes[0], p.points.nodes[1], p.image.img)))
+        d[K_NAME] = slot.K64
+
+    # ---------------------------------------------------------------------------------------------------------- one step
+    def _step(self, slot, with_h2d):
+        if with_h2d:
+            slot.copy_in()
+        d = slot.dev
+        prepared = slot.plan.run(d["points"], d["offsets"], d["image"], d["K_raw"], d["Pc"], None, seed=None)
+        slot.K64.copy_(prepared[7])                                          # the prepared f32 K, as the base executor stages it: f64
+        out = self._solve_part(slot, self._net_part(slot))
+        P = out["P"]
+        if P.dtype != torch.float64 or tuple(P.shape) != (self.B, 4, 4) or not P.is_contiguous():
+            raise ValueError("RawFrameExecutor: the pose solve must return P as contiguous f64 [B,4,4]")
+        call("di2p_compose_poses", ptr(P), ptr(prepared[10]), self.B, ptr(slot.P_scan), stream())
+        out.update(status=prepared[9], T_scan=prepared[10], P_scan=slot.P_scan)
+        return out

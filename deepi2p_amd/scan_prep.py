@@ -16,6 +16,8 @@ from ._lib import DeepI2PHipError, call, ptr, require_cuda, stream
 
 MAX_FRAME_POINTS = 1 << 20
 MAX_EXTENT = 2048.0          # default bound (m) on the bounding-box edge of a frame: frames above it are rejected (status 2)
+NORMALS_METHODS = {"query": "di2p_estimate_normals", "cells": "di2p_estimate_normals_cells"}
+NORMALS_CELL_CANDIDATES = 960          # di2p_normals_cells_candidates(): the LDS candidate capacity of a cell of the "cells" kernel
 _STATUS = {1: "more than max_frame_points points", 2: "bounding box above max_extent / voxel index span above 2^21", 3: "bad frame offsets"}
 
 
@@ -74,13 +76,22 @@ def voxel_down_sample(points, offsets, voxel, normals=None, min_points=0, want_k
     return VoxelState(B, cap, float(voxel), ws, out_off, pts, inten, nrm, keys, status)
 
 
-def estimate_normals(state, radius=0.6, max_nn=30, want_neighbors=False, max_extent=MAX_EXTENT):
-    """-> normals f32[cap,3] (+ nn_count i32[cap], nn_idx i32[cap,max_nn] with want_neighbors) for the points of `state`."""
+def _normals_entry(method):
+    if method not in NORMALS_METHODS:
+        raise ValueError("scan_prep: unknown normals method %r (query, cells)" % (method,))
+    return NORMALS_METHODS[method]
+
+
+def estimate_normals(state, radius=0.6, max_nn=30, want_neighbors=False, max_extent=MAX_EXTENT, method="query"):
+    """-> normals f32[cap,3] (+ nn_count i32[cap], nn_idx i32[cap,max_nn] with want_neighbors) for the points of `state`.
+    method "query": one wave per query point (di2p_estimate_normals); "cells": one workgroup per occupied grid cell
+    (di2p_estimate_normals_cells) -- the same outputs bit for bit."""
+    entry = _normals_entry(method)
     dev = state.points.device
     normals = torch.empty((max(state.cap, 1), 3), dtype=torch.float32, device=dev)
     cnt = torch.empty((max(state.cap, 1),), dtype=torch.int32, device=dev) if want_neighbors else None
     idx = torch.empty((max(state.cap, 1), int(max_nn)), dtype=torch.int32, device=dev) if want_neighbors else None
-    call("di2p_estimate_normals", ptr(state.offsets), state.B, state.cap, float(radius), int(max_nn), float(max_extent), ptr(normals), ptr(cnt),
+    call(entry, ptr(state.offsets), state.B, state.cap, float(radius), int(max_nn), float(max_extent), ptr(normals), ptr(cnt),
          ptr(idx), ptr(state.ws), stream())
     return (normals, cnt, idx) if want_neighbors else normals
 
@@ -137,12 +148,14 @@ def gather_ragged(points, intensity, normals, offsets, idx, transform=None, out=
 
 
 
-def preprocess_velodyne(scans, voxel=0.1, sn_radius=0.6, sn_max_nn=30, device=None):
+def preprocess_velodyne(scans, voxel=0.1, sn_radius=0.6, sn_max_nn=30, device=None, method="query"):
     """The offline script's record per raw scan ([n,4] f32 rows x, y, z, intensity): a list of f32[7, m] device tensors (points, the
-    intensity of the nearest raw point, oriented normals), rows in ascending voxel key.  Synchronises (ragged trim, status)."""
+    intensity of the nearest raw point, oriented normals), rows in ascending voxel key.  Synchronises (ragged trim, status).
+    method: the normals kernel (estimate_normals)."""
+    _normals_entry(method)
     points, offsets, _ = pack(scans, device)
     st = voxel_down_sample(points, offsets, voxel, cap=points.shape[0])
-    normals = estimate_normals(st, sn_radius, sn_max_nn)
+    normals = estimate_normals(st, sn_radius, sn_max_nn, method=method)
     _, inten, _ = nearest_raw(st, points, offsets)
     check_status(st.status[:st.B])
     host = st.offsets.cpu().tolist()

@@ -607,6 +607,18 @@ int di2p_image_prepare_ds(const uint8_t* images, int B, int H0, int W0, const di
                           const int32_t* ints, const float* factors, const int32_t* color_enable, int color, int reduce_blocks, float* out,
                           void* workspace, void* stream);
 
+/* ---- (additive, ABI 9; detect by symbol) raw frames in one call: cell-cooperative normals and pose composition ----
+ * di2p_estimate_normals_cells (csrc/scan_prep.hip): di2p_estimate_normals with the same arguments, the same workspace and the same
+ *   outputs BIT FOR BIT, computed by one workgroup per occupied grid cell (cell edge radius (1 + 2^-20)): the members of the cell's 27
+ *   neighbour cells are staged in LDS once for all queries of the cell.  A cell whose candidate set has more than
+ *   di2p_normals_cells_candidates() entries streams it from global memory instead; no candidate is ever dropped.
+ * di2p_compose_poses (csrc/sample_prep.hip): out[b] = A[b] . Bm[b] for n row-major f64 4x4 matrices (products rounded, summed in
+ *   ascending k; no FMA), one thread per frame; out may alias A or Bm. */
+int di2p_normals_cells_candidates(void);
+int di2p_estimate_normals_cells(const int32_t* voxel_offsets, int B, int cap, double radius, int max_nn, double max_extent, float* normals,
+                                int32_t* nn_count, int32_t* nn_idx, void* workspace, void* stream);
+int di2p_compose_poses(const double* A, const double* Bm, int n, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
