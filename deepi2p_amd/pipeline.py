@@ -27,6 +27,9 @@ INPUT_NAMES = ("pc", "intensity", "sn", "node_a", "node_b", "img")
 # Optional in a host batch: when present it is staged, copied and read by the step like the other six; when absent the slot keeps the
 # K it was constructed with / last given.
 K_NAME = "K"
+# evaluate=True only: the ground-truth pose of every frame ([B,3,4] or [B,4,4]; required) and an optional i32[B] frame mask (0: the frame
+# is padding and stays out of the statistics), staged behind K in the same flat buffer
+P_NAME, MASK_NAME = "P", "frame_mask"
 
 
 class Slot:
@@ -91,10 +94,17 @@ class RegistrationExecutor:
     ``pipe(pc, coarse, fine, K, samples)``; ``samples`` (i32[B,iters,6]) plays the role of ``restarts`` (one draw per executor, by
     ``pipe.draw`` when not given) and ``labels_override`` is a (coarse, fine) pair of i32[B,N].  Results: pred (coarse), fine_pred, P,
     outlier_ratio, n_inliers, n_corr, best.  Graphs, copy streams, double buffering, weight following and ``split_solver`` work as in the
-    Gauss-Newton mode."""
+    Gauss-Newton mode.
+
+    evaluate=True (evaluation.py; off by default, and then nothing here is launched or staged differently): every host batch carries the
+    ground-truth poses "P" ([B,3,4] or [B,4,4]; ValueError at submit without them) and optionally "frame_mask" (i32[B], 0 = padding).  The
+    step then ends with the ground-truth labels of the slot's points (prep.project_labels), the label accuracies of the network's OWN
+    prediction against them (whatever labels_override feeds the solver), the pose errors of P against "P" (in the pipeline's frame; the
+    solver's cost decides validity, in PnP mode every frame is valid) and one update of the slot's own accumulator.  Results gain rte,
+    rre, flags, accuracy, coarse_gt, fine_gt; eval_state() merges the slots' accumulators on the host, eval_reset() clears them."""
 
     def __init__(self, mm, pipe, K, example_batch, n_streams=8, use_graph=True, restarts=None, labels_override=None, step_fn=None,
-                 post_fn=None, h2d_mode="copy_stream", split_solver=False, double_buffer=False, samples=None):
+                 post_fn=None, h2d_mode="copy_stream", split_solver=False, double_buffer=False, samples=None, evaluate=False):
         from .registration_pnp import PnPPipeline
         self.pnp = isinstance(pipe, PnPPipeline)
         if self.pnp:
@@ -106,6 +116,9 @@ class RegistrationExecutor:
                 raise ValueError("in PnP mode the RANSAC draws are passed as `samples`, not `restarts`")
         elif samples is not None:
             raise ValueError("`samples` (RANSAC draws) needs a PnPPipeline; the Gauss-Newton pipeline takes `restarts`")
+        self.evaluate = bool(evaluate)
+        if self.evaluate and step_fn is not None:
+            raise ValueError("evaluate=True measures the pose of the executor's own step; a custom step_fn has none it knows of")
         self.mm, self.pipe = mm, pipe
         self.device = mm.device
         self.n_streams = max(1, int(n_streams))
@@ -151,6 +164,9 @@ class RegistrationExecutor:
             s.net_done = torch.cuda.Event()
             s.copy_stream = torch.cuda.Stream(device=self.device) if h2d_mode == "copy_stream" else None
             s.copied = torch.cuda.Event()
+            if self.evaluate:
+                from .evaluation import EvalAccumulator
+                s.eval_acc = EvalAccumulator(self.device)      # one per slot: the slots' steps run at the same time
             # one flat pinned buffer and one flat device buffer hold all seven inputs (256-byte aligned pieces): a step's transfer is ONE copy
             layout, off = [], 0
             for k, shape, dtype in self._staged_inputs(example_batch, B):
@@ -184,7 +200,10 @@ class RegistrationExecutor:
 
     def _staged_inputs(self, example_batch, B):
         """[(name, shape, dtype)] of the pieces of a slot's flat staging buffer, in order"""
-        return [(k, tuple(example_batch[k].shape), example_batch[k].dtype) for k in INPUT_NAMES] + [(K_NAME, (B, 3, 3), torch.float64)]
+        staged = [(k, tuple(example_batch[k].shape), example_batch[k].dtype) for k in INPUT_NAMES] + [(K_NAME, (B, 3, 3), torch.float64)]
+        if self.evaluate:
+            staged += [(P_NAME, (B, 4, 4), torch.float64), (MASK_NAME, (B,), torch.int32)]
+        return staged
 
     def _validate(self, slot, host_batch):
         """Raise for a host batch this executor was not built for; nothing has been enqueued or consumed yet."""
@@ -192,6 +211,17 @@ class RegistrationExecutor:
             if tuple(host_batch[k].shape) != tuple(slot.host[k].shape):
                 raise ValueError("host batch %r has shape %s, this executor was built (and its graphs captured) for %s -- pad the batch "
                                  "or build an executor for that shape" % (k, tuple(host_batch[k].shape), tuple(slot.host[k].shape)))
+        if self.evaluate:
+            self._validate_truth(slot, host_batch)
+
+    def _validate_truth(self, slot, host_batch):
+        B = slot.host[MASK_NAME].shape[0]
+        if P_NAME not in host_batch:
+            raise ValueError("evaluate=True: the host batch has no ground-truth pose %r ([B,3,4] or [B,4,4])" % P_NAME)
+        if tuple(host_batch[P_NAME].shape) not in ((B, 3, 4), (B, 4, 4)):
+            raise ValueError("evaluate=True: %r must be [%d,3,4] or [%d,4,4], got %s" % (P_NAME, B, B, tuple(host_batch[P_NAME].shape)))
+        if MASK_NAME in host_batch and tuple(host_batch[MASK_NAME].shape) != (B,):
+            raise ValueError("evaluate=True: %r must be i32 [%d], got %s" % (MASK_NAME, B, tuple(host_batch[MASK_NAME].shape)))
 
     def _stage(self, slot, host_batch):
         """Copy a (validated) host batch into the slot's pinned staging buffer."""
@@ -201,10 +231,23 @@ class RegistrationExecutor:
             slot.host[K_NAME].copy_(host_batch[K_NAME])       # f32 -> f64 on the way into the pinned buffer
         else:
             slot.host[K_NAME].copy_(self._K64_host)           # no K in this batch: the constructor's, not what the slot last held
+        if self.evaluate:
+            self._stage_truth(slot, host_batch)
+
+    def _stage_truth(self, slot, host_batch):
+        P = slot.host[P_NAME]
+        P.copy_(torch.eye(4, dtype=torch.float64))            # a 3-row pose gets the row 0 0 0 1 (registration_lsq.py:298-299); the example: identity
+        if P_NAME in host_batch:
+            gt = torch.as_tensor(host_batch[P_NAME])
+            P[:, :gt.shape[1]].copy_(gt)
+        if MASK_NAME in host_batch:
+            slot.host[MASK_NAME].copy_(torch.as_tensor(host_batch[MASK_NAME]))
+        else:
+            slot.host[MASK_NAME].fill_(1)
 
     def _stage_example(self, slot, example_batch):
         """The slot's first contents: the example's six inputs and the constructor's K."""
-        self._stage(slot, {k: example_batch[k] for k in INPUT_NAMES})
+        self._stage(slot, {k: example_batch[k] for k in INPUT_NAMES + (P_NAME, MASK_NAME) if k in example_batch})
 
     def _slot_ready(self, slot):
         """Called once per slot when its buffers exist."""
@@ -238,11 +281,74 @@ class RegistrationExecutor:
             coarse, fine = self.labels_override if self.labels_override is not None else (net["pred"], net["fine_pred"])
             out = self.pipe(d["pc"], coarse, fine, d[K_NAME], self.restarts)      # same stream: PnP follows its classification
             out.update(net)
-            return out
+            return self._eval_part(slot, out) if self.evaluate else out
         labels = self.labels_override if self.labels_override is not None else net["pred"]
         out = self.pipe(d["pc"], labels, d[K_NAME], self.restarts)           # same stream: the pose solve follows its classification
         out.update(net)
+        return self._eval_part(slot, out) if self.evaluate else out
+
+    # ------------------------------------------------------------------------------------------------------------ evaluation mode
+    def _eval_truth(self, slot):
+        """-> (ground-truth poses f64[B,3|4,4], the same and K in f32 for the label projection, frame mask i32[B]) of the slot's batch"""
+        d = slot.dev
+        return d[P_NAME], d[P_NAME].to(torch.float32), d[K_NAME].to(torch.float32), d[MASK_NAME]
+
+    def _eval_part(self, slot, out):
+        """The end of an evaluated step, on the step's stream and inside its capture: ground-truth labels, accuracies of the network's own
+        prediction, pose errors, one update of the slot's accumulator (visualize_and_save_data.py:100-147, registration_lsq.py:87-95,
+        registration_result_analysis.py:22-47)."""
+        from . import evaluation, prep
+        d = slot.dev
+        P_gt, P32, K32, mask = self._eval_truth(slot)
+        fine_scale = 1.0 / self.pipe.scale if self.pnp else 32
+        coarse_gt, fine_gt = prep.project_labels(d["pc"], P32, K32, self.pipe.H, self.pipe.W, fine_scale)
+        fine_pred = out.get("fine_pred")
+        accuracy = prep.label_accuracy(out["pred"], coarse_gt, fine_pred, fine_gt if fine_pred is not None else None)
+        rte, rre, flags = evaluation.pose_errors(out["P"], P_gt, None if self.pnp else out["cost"], frame=getattr(self.pipe, "frame", "cam"))
+        slot.eval_acc.update(rte, rre, flags, mask, accuracy)
+        out.update(rte=rte, rre=rre, flags=flags, accuracy=accuracy, coarse_gt=coarse_gt, fine_gt=fine_gt)
         return out
+
+    class _KeepAccumulators:
+        """Steps that are launched to capture or warm a graph are not results: the accumulators of `slots` come out as they went in."""
+
+        def __init__(self, executor, slots):
+            self.slots, self.device = (slots if executor.evaluate else []), executor.device
+
+        def __enter__(self):
+            self.saved = []
+            if self.slots:
+                torch.cuda.synchronize(self.device)           # with split_solver the steps end on another stream than the slot's
+            for s in self.slots:
+                with torch.cuda.stream(s.stream):
+                    self.saved.append(s.eval_acc.buf.clone())
+
+        def __exit__(self, *exc):
+            for s, b in zip(self.slots, self.saved):
+                with torch.cuda.stream(s.stream):
+                    s.eval_acc.buf.copy_(b)
+                s.stream.synchronize()
+
+    def eval_state(self):
+        """Waits for every slot's last step and merges the slots' accumulators in slot order on the host -> evaluation.EvalState"""
+        from .evaluation import EvalState
+        if not self.evaluate:
+            raise ValueError("eval_state() needs an executor built with evaluate=True")
+        self.synchronize()
+        state = EvalState()
+        for s in self.slots:
+            state = state.merge(s.eval_acc.state())
+        return state
+
+    def eval_reset(self):
+        """Clears every slot's accumulator (after the steps already submitted)."""
+        if not self.evaluate:
+            raise ValueError("eval_reset() needs an executor built with evaluate=True")
+        self.synchronize()
+        for s in self.slots:
+            with torch.cuda.stream(s.stream):
+                s.eval_acc.reset()
+        self.synchronize()
 
     def _capture(self, slot, with_h2d):
         """Capture the step once per input set of the slot (the sets' graphs share one memory pool: they never run at the same time)."""
@@ -296,6 +402,10 @@ class RegistrationExecutor:
         """Capture (or run once) every slot's step so that the first timed submit pays nothing extra.  A failed capture switches the
         executor to eager launches (and remembers why in `graph_error`)."""
         self._follow_weights()
+        with self._KeepAccumulators(self, self.slots):
+            self._warm_up(with_h2d)
+
+    def _warm_up(self, with_h2d):
         want_h2d = bool(with_h2d)
         with_h2d = with_h2d and self.h2d_mode == "graph"
         for slot in self.slots:
@@ -376,7 +486,8 @@ class RegistrationExecutor:
                 slot.stream.wait_event(slot.copied)
             if self.use_graph:
                 if (in_step, slot.cur) not in slot.graphs:
-                    self._capture(slot, in_step)
+                    with self._KeepAccumulators(self, [slot]):
+                        self._capture(slot, in_step)
                 g, out = slot.graphs[(in_step, slot.cur)]
                 self._replay(slot, g)
                 slot.outputs = out

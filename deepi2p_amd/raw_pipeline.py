@@ -69,10 +69,14 @@ class RawFrameExecutor(RegistrationExecutor):
     raw image shape, cap_raw (rows of the pinned staging buffer: a batch with more points in all raises) and max_frame_points (a longer
     frame is rejected ON THE DEVICE: status != 0, its pose is whatever the solver makes of zeros, the other frames are unaffected).
     P_scan = P . T_scan maps raw-scan coordinates into the camera frame.  The seed of the preparation's draws is staged with the batch and
-    read from device memory inside the graph."""
+    read from device memory inside the graph.
+
+    evaluate=True: the base executor's evaluation mode with the ground truth the preparation produces itself -- the pose P of the prepared
+    points (the sample's f32 [B,3,4]) against the solver's out["P"] -- and status != 0 as the frame mask: a rejected frame is absent from
+    the statistics.  No host "P" is needed."""
 
     def __init__(self, mm, pipe, opt, example_batch, cap_raw, max_frame_points, n_streams=4, use_graph=True, restarts=None, samples=None,
-                 labels_override=None, mode="val", dataset="kitti", normals_method="query", h2d_mode="copy_stream", post_fn=None):
+                 labels_override=None, mode="val", dataset="kitti", normals_method="query", h2d_mode="copy_stream", post_fn=None, evaluate=False):
         raw_prep._check_dataset(dataset)
         from . import scan_prep
         scan_prep._normals_entry(normals_method)
@@ -86,7 +90,7 @@ class RawFrameExecutor(RegistrationExecutor):
         self.cap_raw, self.max_frame_points = int(cap_raw), int(max_frame_points)
         host_frames(example_batch, self.B, self.cap_raw, self.raw_hw)
         super().__init__(mm, pipe, torch.eye(3, dtype=torch.float64), example_batch, n_streams=n_streams, use_graph=use_graph, restarts=restarts,
-                         labels_override=labels_override, post_fn=post_fn, h2d_mode=h2d_mode, samples=samples)
+                         labels_override=labels_override, post_fn=post_fn, h2d_mode=h2d_mode, samples=samples, evaluate=evaluate)
 
     # ---------------------------------------------------------------------------------------------------------- staged inputs
     def _batch_size(self, example_batch):
@@ -130,6 +134,9 @@ class RawFrameExecutor(RegistrationExecutor):
         slot.plan = plan
         slot.K64 = torch.zeros((self.B, 3, 3), dtype=torch.float64, device=self.device)
         slot.P_scan = torch.zeros((self.B, 4, 4), dtype=torch.float64, device=self.device)
+        if self.evaluate:
+            slot.P_gt64 = torch.zeros((self.B, 3, 4), dtype=torch.float64, device=self.device)
+            slot.mask = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
         p = plan.sample
         # what _net_part / _solve_part read: the plan's outputs, in place
         d.update(zip(INPUT_NAMES, (p.points.pc, p.points.intensity, p.points.sn, p.points.nodes[0], p.points.nodes[1], p.image.img)))
@@ -142,6 +149,7 @@ class RawFrameExecutor(RegistrationExecutor):
         d = slot.dev
         prepared = slot.plan.run(d["points"], d["offsets"], d["image"], d["K_raw"], d["Pc"], None, seed=None)
         slot.K64.copy_(prepared[7])                                          # the prepared f32 K, as the base executor stages it: f64
+        slot.prepared = prepared
         out = self._solve_part(slot, self._net_part(slot))
         P = out["P"]
         if P.dtype != torch.float64 or tuple(P.shape) != (self.B, 4, 4) or not P.is_contiguous():
@@ -149,3 +157,9 @@ class RawFrameExecutor(RegistrationExecutor):
         call("di2p_compose_poses", ptr(P), ptr(prepared[10]), self.B, ptr(slot.P_scan), stream())
         out.update(status=prepared[9], T_scan=prepared[10], P_scan=slot.P_scan)
         return out
+
+    def _eval_truth(self, slot):
+        prepared = slot.prepared
+        slot.P_gt64.copy_(prepared[5])                                       # the sample's own pose of the prepared points, f32 -> f64
+        slot.mask.copy_(prepared[9] == 0)                                    # a rejected frame (status != 0) is skipped entirely
+        return slot.P_gt64, prepared[5], prepared[7], slot.mask

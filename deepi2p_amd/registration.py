@@ -157,10 +157,17 @@ def solve_P_random_perturb(pc_np, coarse_predictions_np, K_np, H, W, init_t_ampl
 
 class RegistrationPipeline:
     """Device-resident labels -> pose for a batch of frames: initial guess, front filter, R restarts per
-    frame, argmin.  Nothing leaves HBM between the classifier and the pose."""
+    frame, argmin.  Nothing leaves HBM between the classifier and the pose.
+
+    frame="enu": the points are z-up (nuScenes).  The 2-D solve only rotates about y, so the reference swaps axes first (enu2cam,
+    registration_lsq.py:237-248, 301-302): the call converts the points (x, y, z) -> (x, -z, y), runs the same launches on them and
+    returns P_cam (the solver's pose of the converted points) next to P = P_cam . P_convert (the pose of the points as given)."""
 
     def __init__(self, H, W, R=60, ry_sigma=10 * math.pi / 180, init_t_amplitude=10.0,
-                 t_lowerbound=(-5, -0.1, -10), t_upperbound=(5, 0.1, 10), max_iter=500, is_2d=True, seed=0):
+                 t_lowerbound=(-5, -0.1, -10), t_upperbound=(5, 0.1, 10), max_iter=500, is_2d=True, seed=0, frame="cam"):
+        from . import evaluation
+        self.enu, self.frame = bool(evaluation.check_frame(frame)), frame
+        self._convert = {}
         self.H, self.W, self.R = H, W, R
         self.ry_sigma, self.amp = ry_sigma, init_t_amplitude
         self.lb, self.ub = list(t_lowerbound), list(t_upperbound)
@@ -184,6 +191,9 @@ class RegistrationPipeline:
         """pc f32[F,3,N], labels i32[F,N], K f64[F,3,3], restarts = (ry_noise f64[F,R], t_init f64[F,R,3])
         -> dict(P f64[F,4,4], cost f64[F], best i32[F], yaw0, costs f64[F,R], iters i32[F,R])."""
         F, _, N = pc_f32.shape
+        if self.enu:
+            from . import evaluation
+            pc_f32 = evaluation.enu2cam_points(pc_f32)
         pts64 = torch.empty((F, 3, N), dtype=torch.float64, device=pc_f32.device)
         ops.call("di2p_f32_to_f64", ops.ptr(pc_f32), ops.ptr(pts64), F * 3 * N, ops.stream())
         yaw0, lab_front, has_inside = ops.initial_guess(pts64, labels_i32)
@@ -192,4 +202,18 @@ class RegistrationPipeline:
         params, cost, iters = ops.solve_batched(pc_f32, lab_front, K_f64, noise, Ts, self.H, self.W, self.lb, self.ub,
                                                 self.max_iter, self.is_2d, yaw0=yaw0, sweeps=sweeps)
         best, P, bc = ops.select_best(params, cost, self.is_2d, has_inside=has_inside)
-        return dict(P=P, cost=bc, best=best, yaw0=yaw0, costs=cost, iters=iters, sweeps=sweeps, params=params, labels_front=lab_front)
+        out = dict(P=P, cost=bc, best=best, yaw0=yaw0, costs=cost, iters=iters, sweeps=sweeps, params=params, labels_front=lab_front)
+        if self.enu:
+            out["P_cam"], out["P"] = P, compose_convert(self._convert, P)
+        return out
+
+
+def compose_convert(cache, P_cam):
+    """P_cam . P_convert for f64[F,4,4] (di2p_compose_poses against a constant kept in `cache` per device and batch size)"""
+    key = (P_cam.device, P_cam.shape[0])
+    if key not in cache:
+        from . import evaluation
+        cache[key] = evaluation.convert_matrices(P_cam.shape[0], P_cam.device)
+    P = torch.empty_like(P_cam)
+    ops.call("di2p_compose_poses", ops.ptr(P_cam), ops.ptr(cache[key]), P_cam.shape[0], ops.ptr(P), ops.stream())
+    return P

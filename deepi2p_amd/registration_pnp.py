@@ -96,11 +96,16 @@ def solve_PnP(pc_np, coarse_predictions_np, fine_predictions_np, K_np, H, W, fin
 class PnPPipeline:
     """Device-resident labels -> pose by PnP for a batch of frames (the reference's second back end, registration_pnp.py:95-148): what
     RegistrationPipeline is for the Gauss-Newton solve, for pipeline.RegistrationExecutor.  Fixed per pipeline: the image size, the fine
-    grid (fine_resolution_scale, the reference's 1/32), the RANSAC settings; per call: the frames, their labels, K and the draws."""
+    grid (fine_resolution_scale, the reference's 1/32), the RANSAC settings; per call: the frames, their labels, K and the draws.
+    frame="enu" (z-up points): as in RegistrationPipeline -- the points are converted first, P_cam is the pose of the converted points and
+    P = P_cam . P_convert that of the points as given."""
 
-    def __init__(self, H, W, fine_resolution_scale=1 / 32, iterations=500, reproj_err=0.6, method="epnp", seed=0):
+    def __init__(self, H, W, fine_resolution_scale=1 / 32, iterations=500, reproj_err=0.6, method="epnp", seed=0, frame="cam"):
         if method not in ("epnp", "dlt_lo"):
             raise ValueError("method must be 'epnp' or 'dlt_lo'")
+        from . import evaluation
+        self.enu, self.frame = bool(evaluation.check_frame(frame)), frame
+        self._convert = {}
         self.H, self.W, self.scale = H, W, float(fine_resolution_scale)
         self.W_fine = int(round(W * self.scale))
         self.H_fine = int(round(H * self.scale))
@@ -121,5 +126,12 @@ class PnPPipeline:
         """pc f32[F,3,N], coarse / fine i32[F,N], K f64[F,3,3] (full-resolution camera), samples i32[F,iters,6]
         -> dict(P f64[F,4,4], outlier_ratio f64[F], n_inliers, n_corr, best i32[F]); a frame without an accepted pose comes back as identity
         with outlier ratio 1 (the reference's acceptance rules, registration_pnp.py:123-148, inside the kernels)."""
-        return pnp_ransac(pc, coarse, fine, self.scale_K(K), self.W_fine, samples, reproj_err=self.reproj_err, pixels=pixels,
-                          method=self.method)
+        if self.enu:
+            from . import evaluation
+            pc = evaluation.enu2cam_points(pc)
+        out = pnp_ransac(pc, coarse, fine, self.scale_K(K), self.W_fine, samples, reproj_err=self.reproj_err, pixels=pixels,
+                         method=self.method)
+        if self.enu:
+            from .registration import compose_convert
+            out["P_cam"], out["P"] = out["P"], compose_convert(self._convert, out["P"])
+        return out

@@ -619,6 +619,35 @@ int di2p_estimate_normals_cells(const int32_t* voxel_offsets, int B, int cap, do
                                 int32_t* nn_count, int32_t* nn_idx, void* workspace, void* stream);
 int di2p_compose_poses(const double* A, const double* Bm, int n, double* out, void* stream);
 
+/* ---- (additive, ABI 9; detect by symbol) evaluation mode (csrc/eval.hip): pose errors, success statistics, ENU frames ----
+ * di2p_pose_errors -- evaluation/registration_lsq.py:87-95 (get_P_diff) for F frames, one thread per frame, fp64.
+ *   P_pred f64[F,4,4] (its bottom row is taken as 0 0 0 1), P_gt f64[F,gt_rows,4] with gt_rows 3 or 4 (a 3-row matrix gets the row
+ *   0 0 0 1, :298-299), cost f64[F] or NULL.  D = P_pred^-1 P_gt (affine inverse from the 3x3 cofactors); rte = |D[0:3,3]|; rre = the sum
+ *   of the absolute extrinsic 'xzy' Euler angles of D[0:3,0:3] in degrees: with R = Ry(c) Rz(b) Rx(a), b = asin(R10), a = atan2(-R12, R11),
+ *   c = atan2(-R20, R00).  enu != 0: both matrices are first multiplied on the right by the inverse of the reference's P_convert (rows
+ *   1 0 0 0 / 0 0 -1 0 / 0 1 0 0 / 0 0 0 1; enu2cam, :237-248) -- the sum of |angles| is not invariant under that change of axes and the
+ *   reference measures it in the converted frame.  flags i32[F]: bit 0 valid (cost > 1e-6; always set when cost is NULL), bit 1 success
+ *   (rte < t_thresh and rre < r_thresh).  Within about 1e-3 deg of gimbal lock (|b| -> 90 deg) the individual angles are ill-conditioned:
+ *   the result is finite there and nothing more is promised.
+ * di2p_eval_accumulate -- evaluation/registration_result_analysis.py:22-47,59,63: folds one batch into the device accumulator `acc`
+ *   (di2p_eval_acc_bytes() bytes, 8-byte aligned, cleared by di2p_eval_acc_reset), as 8-byte words:
+ *     i64 [0] frames seen  [1] frames valid  [2] successes among the valid  [3] frames with a coarse accuracy  [4] frames with a fine accuracy
+ *         [5] RTE overflow  [6] RRE overflow  [7] 0
+ *     f64 [8] sum rte  [9] sum rte^2  [10] sum rre  [11] sum rre^2 (valid frames)  [12] sum coarse accuracy  [13] sum fine accuracy  [14] [15] 0
+ *     i64 [16..75] RTE histogram over [0, 15) m  [76..135] RRE histogram over [0, 30) deg, 60 bins each, valid frames (np.histogram's bins;
+ *         a value above the range, or NaN, goes to the overflow count)
+ *   frame_mask i32[F] or NULL: a frame with mask 0 is skipped entirely (a padded last batch, a rejected raw frame).  accuracy f32[F,2]
+ *   (di2p_label_accuracy's output) or NULL; a NaN accuracy (no ground-truth point inside the image) is not counted.  One workgroup; frames
+ *   are added in index order, so the accumulator depends on the sequence of calls alone.
+ * di2p_enu2cam_points: (x, y, z) -> (x, -z, y) for pc f32[B,3,N] (transform_pc_np(P_convert, pc) of enu2cam; exact); pc_out may be pc_in. */
+long long di2p_eval_acc_bytes(void);
+int di2p_pose_errors(const double* P_pred, const double* P_gt, int gt_rows, const double* cost, int enu, int F, double t_thresh,
+                     double r_thresh, double* rte, double* rre, int32_t* flags, void* stream);
+int di2p_eval_accumulate(const double* rte, const double* rre, const int32_t* flags, const int32_t* frame_mask, const float* accuracy, int F,
+                         void* acc, void* stream);
+int di2p_eval_acc_reset(void* acc, void* stream);
+int di2p_enu2cam_points(const float* pc_in, float* pc_out, int B, int N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
