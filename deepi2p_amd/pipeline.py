@@ -30,6 +30,7 @@ K_NAME = "K"
 # evaluate=True only: the ground-truth pose of every frame ([B,3,4] or [B,4,4]; required) and an optional i32[B] frame mask (0: the frame
 # is padding and stays out of the statistics), staged behind K in the same flat buffer
 P_NAME, MASK_NAME = "P", "frame_mask"
+VISUALIZE = (None, "registration", "classification", "both")
 
 
 class Slot:
@@ -101,10 +102,22 @@ class RegistrationExecutor:
     step then ends with the ground-truth labels of the slot's points (prep.project_labels), the label accuracies of the network's OWN
     prediction against them (whatever labels_override feeds the solver), the pose errors of P against "P" (in the pipeline's frame; the
     solver's cost decides validity, in PnP mode every frame is valid) and one update of the slot's own accumulator.  Results gain rte,
-    rre, flags, accuracy, coarse_gt, fine_gt; eval_state() merges the slots' accumulators on the host, eval_reset() clears them."""
+    rre, flags, accuracy, coarse_gt, fine_gt; eval_state() merges the slots' accumulators on the host, eval_reset() clears them.
+
+    visualize=None | "registration" | "classification" | "both" (visualization.py; None by default, and then nothing here is launched, staged
+    or allocated differently and the results gain no keys): the step ends with the reference's per-frame images, drawn into per-slot canvases
+    u8 [B, H + 200, W + 200, 3] from operands that are in the slot already (three launches each, inside the capture).
+    "registration" -> results["vis_registration"]: the slot's points projected with the step's own P and K, red where the network's
+    prediction (results["pred"], whatever labels_override feeds the solver) is 1 and blue elsewhere, over the network's image.  The
+    reference draws only the points its front filter keeps; here every point of the slot is drawn.  With a frame="enu" pipeline it is what
+    the reference draws at registration_lsq.py:366: the CONVERTED points (x, -z, y) with P_cam, the pose of the converted frame -- not the
+    points as given with P = P_cam . P_convert, which is the same projection mathematically but not to the last bit.
+    "classification" -> results["vis_classification"]: prediction against ground truth at the ground-truth projection (the third output of
+    the prep.project_labels call evaluation mode makes anyway), the fine variant with its grid when the model has the fine head, else the
+    coarse one; it needs evaluate=True for the ground truth (ValueError otherwise).  A custom step_fn with visualize raises, as with evaluate."""
 
     def __init__(self, mm, pipe, K, example_batch, n_streams=8, use_graph=True, restarts=None, labels_override=None, step_fn=None,
-                 post_fn=None, h2d_mode="copy_stream", split_solver=False, double_buffer=False, samples=None, evaluate=False):
+                 post_fn=None, h2d_mode="copy_stream", split_solver=False, double_buffer=False, samples=None, evaluate=False, visualize=None):
         from .registration_pnp import PnPPipeline
         self.pnp = isinstance(pipe, PnPPipeline)
         if self.pnp:
@@ -119,6 +132,13 @@ class RegistrationExecutor:
         self.evaluate = bool(evaluate)
         if self.evaluate and step_fn is not None:
             raise ValueError("evaluate=True measures the pose of the executor's own step; a custom step_fn has none it knows of")
+        if visualize not in VISUALIZE:
+            raise ValueError("visualize must be None, 'registration', 'classification' or 'both', got %r" % (visualize,))
+        if visualize in ("classification", "both") and not self.evaluate:
+            raise ValueError("visualize=%r draws the prediction against the ground-truth labels: it needs evaluate=True" % (visualize,))
+        if visualize is not None and step_fn is not None:
+            raise ValueError("visualize draws the pose and labels of the executor's own step; a custom step_fn has none it knows of")
+        self.visualize = visualize
         self.mm, self.pipe = mm, pipe
         self.device = mm.device
         self.n_streams = max(1, int(n_streams))
@@ -185,6 +205,11 @@ class RegistrationExecutor:
                 s.dev_flats.append(flat)
                 s.devs.append(_flat_views(flat, layout))
             self._slot_ready(s)
+            if self.visualize is not None:
+                from . import visualization
+                img = s.devs[0]["img"]                             # the network's image f32 [B,3,H,W]: its size is the canvases'
+                kinds = ("registration", "classification") if self.visualize == "both" else (self.visualize,)
+                s.vis = {kind: visualization.buffers(B, int(img.shape[2]), int(img.shape[3]), self.device) for kind in kinds}
             self.slots.append(s)
         self._next = 0
         self._h2d_warm = False
@@ -281,11 +306,16 @@ class RegistrationExecutor:
             coarse, fine = self.labels_override if self.labels_override is not None else (net["pred"], net["fine_pred"])
             out = self.pipe(d["pc"], coarse, fine, d[K_NAME], self.restarts)      # same stream: PnP follows its classification
             out.update(net)
-            return self._eval_part(slot, out) if self.evaluate else out
+            return self._finish(slot, out)
         labels = self.labels_override if self.labels_override is not None else net["pred"]
         out = self.pipe(d["pc"], labels, d[K_NAME], self.restarts)           # same stream: the pose solve follows its classification
         out.update(net)
-        return self._eval_part(slot, out) if self.evaluate else out
+        return self._finish(slot, out)
+
+    def _finish(self, slot, out):
+        if self.evaluate:
+            out = self._eval_part(slot, out)
+        return out if self.visualize is None else self._vis_part(slot, out)
 
     # ------------------------------------------------------------------------------------------------------------ evaluation mode
     def _eval_truth(self, slot):
@@ -301,12 +331,36 @@ class RegistrationExecutor:
         d = slot.dev
         P_gt, P32, K32, mask = self._eval_truth(slot)
         fine_scale = 1.0 / self.pipe.scale if self.pnp else 32
-        coarse_gt, fine_gt = prep.project_labels(d["pc"], P32, K32, self.pipe.H, self.pipe.W, fine_scale)
+        if self.visualize in ("classification", "both"):                     # the same launch with its third output: where the points project
+            coarse_gt, fine_gt, slot.vis_pxpy = prep.project_labels(d["pc"], P32, K32, self.pipe.H, self.pipe.W, fine_scale, want_pxpy=True)
+        else:
+            coarse_gt, fine_gt = prep.project_labels(d["pc"], P32, K32, self.pipe.H, self.pipe.W, fine_scale)
         fine_pred = out.get("fine_pred")
         accuracy = prep.label_accuracy(out["pred"], coarse_gt, fine_pred, fine_gt if fine_pred is not None else None)
         rte, rre, flags = evaluation.pose_errors(out["P"], P_gt, None if self.pnp else out["cost"], frame=getattr(self.pipe, "frame", "cam"))
         slot.eval_acc.update(rte, rre, flags, mask, accuracy)
         out.update(rte=rte, rre=rre, flags=flags, accuracy=accuracy, coarse_gt=coarse_gt, fine_gt=fine_gt)
+        return out
+
+    def _vis_part(self, slot, out):
+        """The overlays of a step, after the solve (and the evaluation), on the step's stream and inside its capture: into the slot's canvases."""
+        from . import evaluation, visualization
+        d = slot.dev
+        if "registration" in slot.vis:
+            pc, P = d["pc"], out["P"]
+            if getattr(self.pipe, "enu", False):                             # registration_lsq.py:301-302, 366: the converted points and their pose
+                pc, P = evaluation.enu2cam_points(pc), out["P_cam"]
+            out["vis_registration"] = visualization.registration_overlay_into(pc, P, d[K_NAME], out["pred"], d["img"], *slot.vis["registration"])
+        if "classification" in slot.vis:
+            canvas, workspace = slot.vis["classification"]
+            fine_pred = out.get("fine_pred")
+            if fine_pred is not None:
+                fine_scale = int(round(1.0 / self.pipe.scale)) if self.pnp else 32
+                out["vis_classification"] = visualization.classification_overlay_into(slot.vis_pxpy, out["pred"], out["coarse_gt"], fine_pred,
+                                                                                      out["fine_gt"], d["img"], canvas, workspace, fine_scale)
+            else:
+                out["vis_classification"] = visualization.classification_overlay_coarse_into(slot.vis_pxpy, out["pred"], out["coarse_gt"], d["img"],
+                                                                                             canvas, workspace)
         return out
 
     class _KeepAccumulators:

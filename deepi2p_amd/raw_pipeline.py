@@ -73,10 +73,14 @@ class RawFrameExecutor(RegistrationExecutor):
 
     evaluate=True: the base executor's evaluation mode with the ground truth the preparation produces itself -- the pose P of the prepared
     points (the sample's f32 [B,3,4]) against the solver's out["P"] -- and status != 0 as the frame mask: a rejected frame is absent from
-    the statistics.  No host "P" is needed."""
+    the statistics.  No host "P" is needed.
+
+    visualize: the base executor's option, passed through; the overlays are drawn over the PREPARED image (the network's input) from the
+    prepared points, with the prepared K."""
 
     def __init__(self, mm, pipe, opt, example_batch, cap_raw, max_frame_points, n_streams=4, use_graph=True, restarts=None, samples=None,
-                 labels_override=None, mode="val", dataset="kitti", normals_method="query", h2d_mode="copy_stream", post_fn=None, evaluate=False):
+                 labels_override=None, mode="val", dataset="kitti", normals_method="query", h2d_mode="copy_stream", post_fn=None, evaluate=False,
+                 visualize=None):
         raw_prep._check_dataset(dataset)
         from . import scan_prep
         scan_prep._normals_entry(normals_method)
@@ -90,7 +94,7 @@ class RawFrameExecutor(RegistrationExecutor):
         self.cap_raw, self.max_frame_points = int(cap_raw), int(max_frame_points)
         host_frames(example_batch, self.B, self.cap_raw, self.raw_hw)
         super().__init__(mm, pipe, torch.eye(3, dtype=torch.float64), example_batch, n_streams=n_streams, use_graph=use_graph, restarts=restarts,
-                         labels_override=labels_override, post_fn=post_fn, h2d_mode=h2d_mode, samples=samples, evaluate=evaluate)
+                         labels_override=labels_override, post_fn=post_fn, h2d_mode=h2d_mode, samples=samples, evaluate=evaluate, visualize=visualize)
 
     # ---------------------------------------------------------------------------------------------------------- staged inputs
     def _batch_size(self, example_batch):

@@ -648,6 +648,33 @@ int di2p_eval_accumulate(const double* rte, const double* rre, const int32_t* fl
 int di2p_eval_acc_reset(void* acc, void* stream);
 int di2p_enu2cam_points(const float* pc_in, float* pc_out, int B, int N, void* stream);
 
+/* ---- (additive, ABI 9; detect by symbol) result overlays (csrc/vis.hip): the reference's per-frame images, util/vis_tools.py:96-339 ----
+ * Canvas u8 [B, H + 2 H_delta, W + 2 W_delta, 3] (RGB): white, the frame's image at [H_delta : H_delta + H, W_delta : W_delta + W].  img is
+ *   u8 [B,H,W,3] (img_is_u8 != 0) or f32 [B,3,H,W], converted as img.round().to(uint8): round half to even, values outside 0..255 clamped
+ *   (a fork: torch leaves that conversion unspecified), NaN -> 0.
+ * Points n = 0 .. N-1 in index order, later over earlier: a point is skipped if px or py is inf / NaN; cx = int(round(px)) + W_delta,
+ *   cy = int(round(py)) + H_delta (half to even; tested in floating point, so 1e30 is never converted); skipped unless 0 <= cx < W_large - 1
+ *   and 0 <= cy < H_large - 1.  A drawn point paints cv2.circle(radius 1, filled): (cx, cy), (cx +- 1, cy), (cx, cy +- 1), clipped.
+ *   A canvas pixel therefore shows the colour of the LARGEST n whose stamp covers it: one atomicMax of ((n + 1) << 3) | colour code per stamp
+ *   pixel into a u32 key plane, then one compose pass (key 0: the base pixel).  Deterministic.  N <= 2^28.  Three launches per call.
+ * di2p_vis_classification -- get_classification_visualization(_coarse): pxpy f32[B,2,N] (di2p_project_labels' third output; no z test),
+ *   labels i32[B,N] with values 0 / 1.  pred == 1 and gt == 1: (0,255,0), or (255,255,0) in the fine variant when fine_pred != fine_gt;
+ *   gt == 1 only: (255,0,0); pred == 1 only: (0,0,255); neither: nothing is drawn and nothing is covered.  Fine variant (fine_pred, fine_gt
+ *   not NULL, grid_s >= 1 the cell size): before the points, white one-pixel rows at y = h grid_s + H_delta over the image's columns for
+ *   h = 1 .. n_rows and white columns at x = w grid_s + W_delta over the image's rows for w = 1 .. n_cols; the caller passes
+ *   n_rows = round(H / grid_s) - 1, n_cols = round(W / grid_s) - 1 with Python's round.  Coarse variant: fine_pred == fine_gt == NULL, grid_s == 0.
+ * di2p_vis_registration -- get_registration_visualization: pc f32[B,3,N] widened to f64, P f64[B,4,4], K f64[B,3,3]; q = rows 0..2 of
+ *   P [p; 1], k = K q (products rounded, summed left to right, no FMA), px = k0 / k2, py = k1 / k2; additionally skipped when k2 < 0.
+ *   labels i32[B,N]: (255,0,0) where 1, else (0,0,255).
+ * workspace: di2p_vis_workspace_bytes() bytes (the key plane, rounded up to 256; -1 for bad sizes), 16-byte aligned, cleared by every call.
+ * cv2.putText (t_ij_np) is not reproduced. */
+long long di2p_vis_workspace_bytes(int B, int H, int W, int H_delta, int W_delta);
+int di2p_vis_classification(const float* pxpy, const int32_t* coarse_pred, const int32_t* coarse_gt, const int32_t* fine_pred,
+                            const int32_t* fine_gt, const void* img, int img_is_u8, int B, int N, int H, int W, int H_delta, int W_delta,
+                            int grid_s, int n_rows, int n_cols, uint8_t* canvas, void* workspace, void* stream);
+int di2p_vis_registration(const float* pc, const double* P, const double* K, const int32_t* labels, const void* img, int img_is_u8, int B, int N,
+                          int H, int W, int H_delta, int W_delta, uint8_t* canvas, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
