@@ -801,6 +801,13 @@ extern "C" long long di2p_scan_prep_workspace_bytes(int B, int cap) {
     return (long long)layout(B, cap).total;
 }
 
+// Byte offset, inside the workspace of (B, cap), of the fp64 means f64[cap,3] di2p_voxel_down_sample leaves there (output point order):
+// later stages that go on in fp64 (submap.hip's camera transform) read them instead of the rounded out_points.
+extern "C" long long di2p_scan_prep_centroids_offset(int B, int cap) {
+    if (B < 0 || cap < 0) return -1;
+    return (long long)layout(B, cap).cen;
+}
+
 extern "C" int di2p_voxel_down_sample(const float* points, const int32_t* offsets, int B, int cap, int max_frame_points, double voxel,
                                       double max_extent, int min_points, const float* normals_in, int32_t* out_offsets, float* out_points,
                                       float* out_intensity, float* out_normals, int64_t* out_keys, int32_t* status, void* workspace,

@@ -316,6 +316,66 @@ def make_oxford_submap(rng, n, length=100.0, half_width=8.0, far_share=0.2, max_
     return np.stack([x, y, zz, inten]).astype(np.float32)
 
 
+def _rot(axis, a):
+    c, s = math.cos(a), math.sin(a)
+    i, j = [(1, 2), (2, 0), (0, 1)][axis]
+    R = np.eye(4)
+    R[i, i], R[i, j], R[j, i], R[j, j] = c, -s, s, c
+    return R
+
+
+def make_lms_traversal(rng, submaps, scans, points_per_scan, speed=10.0, skip_threshold=0.1 / 16.0, missing=0.03, rate=50.0):
+    """A stretch of an Oxford traversal as the raw stage reads it (deepi2p_amd.submap): `submaps` sub-maps of `scans` 2-D LMS profiles each
+    (an int, or one count per sub-map) with up to `points_per_scan` rows (x, y, reflectance) in the LASER frame (x to the ground, the
+    scan plane across the direction of travel): a road `height` below, walls at the sides, ragged row counts (returns drop out; now and
+    then a profile is cut short or empty).  The vehicle (x forward, y right, z down) drives a gentle S-curve at about `speed` m/s and
+    `rate` profiles per second, with stretches of every sub-map where it creeps slower than `skip_threshold` per profile; the poses are
+    relative to the middle profile of each sub-map.  About `missing` of the profiles have no scan file (None).
+    -> dict(submaps=[(scans, poses f64[S,4,4]), ...] (submap.pack_scans' host form), G_posesource_laser f64[4,4], G_cam f64[4,4])"""
+    counts = [int(scans)] * int(submaps) if np.ndim(scans) == 0 else [int(c) for c in scans]
+    # laser x (down) = vehicle z, laser y = vehicle y, laser z = - vehicle x; a small mounting error on top
+    G_laser = np.array([[0.0, 0.0, -1.0, 1.6], [0.0, 1.0, 0.0, 0.05], [1.0, 0.0, 0.0, -1.1], [0.0, 0.0, 0.0, 1.0]]) @ _rot(0, 0.02) @ _rot(1, -0.015)
+    # camera (x right, y down, z forward) from the vehicle frame, then the image convention of the camera model
+    G_cam = np.array([[0.0, 1.0, 0.0, 0.1], [0.0, 0.0, 1.0, 1.2], [1.0, 0.0, 0.0, -1.4], [0.0, 0.0, 0.0, 1.0]]) @ _rot(2, 0.01)
+    height, half_width, max_range = 1.1, 7.5, 50.0
+    out = []
+    for S in counts:
+        step = np.full(S, speed / rate)
+        for _ in range(max(1, S // 25)):                         # creeping stretches: well below the threshold per profile
+            a = int(rng.integers(0, max(S - 1, 1)))
+            step[a:a + int(rng.integers(2, 9))] = skip_threshold * rng.uniform(0.05, 0.45)
+        dist = np.cumsum(step) - step[0]
+        yaw = 0.15 * np.sin(dist / 35.0 + rng.uniform(0, 6.0))
+        pitch = 0.01 * np.sin(dist / 9.0)
+        xy = np.cumsum(np.stack([np.cos(yaw) * step, np.sin(yaw) * step], 1), 0)
+        T = np.tile(np.eye(4), (S, 1, 1))
+        for i in range(S):
+            T[i] = _rot(2, yaw[i]) @ _rot(1, pitch[i])
+            T[i, :3, 3] = [xy[i, 0], xy[i, 1], 0.02 * math.sin(dist[i] / 5.0)]
+        origin = np.linalg.inv(T[S // 2]) if S else np.eye(4)
+        poses = np.stack([origin @ T[i] for i in range(S)]) if S else np.zeros((0, 4, 4))
+        prof = []
+        for i in range(S):
+            if rng.random() < missing:
+                prof.append(None)
+                continue
+            n = int(points_per_scan)
+            r = rng.random()
+            if r < 0.04:
+                n = 0
+            elif r < 0.2:
+                n = int(rng.integers(0, n + 1))
+            ang = np.sort(rng.uniform(-2.2, 2.2, n))              # from straight down (x) past the horizon on both sides (y)
+            rng_road = np.where(np.cos(ang) > 1e-3, height / np.maximum(np.cos(ang), 1e-3), np.inf)
+            rng_wall = half_width / np.maximum(np.abs(np.sin(ang)), 1e-3)
+            d = np.minimum(rng_road, rng_wall) + rng.normal(0.0, 0.01, n)
+            keep = (d < max_range) & (rng.random(n) > 0.05)
+            refl = np.rint(np.clip(np.where(rng_road < rng_wall, 60.0, 140.0) + rng.normal(0.0, 25.0, n), 0.0, 255.0))
+            prof.append(np.ascontiguousarray(np.stack([d * np.cos(ang), d * np.sin(ang), refl], 1)[keep]))
+        out.append((prof, poses))
+    return dict(submaps=out, G_posesource_laser=G_laser, G_cam=G_cam)
+
+
 def make_camera_image(rng, H0=370, W0=1226):
     """A synthetic camera frame u8[H0, W0, 3] (HWC, as np.load gives the loader's images) that reaches every branch of the colour code:
     smooth gradients (every hue sector), per-pixel texture, saturated primaries, pure black / white, and exactly grey patches."""

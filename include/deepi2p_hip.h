@@ -675,6 +675,39 @@ int di2p_vis_classification(const float* pxpy, const int32_t* coarse_pred, const
 int di2p_vis_registration(const float* pc, const double* P, const double* K, const int32_t* labels, const void* img, int img_is_u8, int B, int N,
                           int H, int W, int H_delta, int W_delta, uint8_t* canvas, void* workspace, void* stream);
 
+/* ---- (additive, ABI 9; detect by symbol) Oxford sub-map building from LMS push-broom profiles (csrc/submap.hip) -----------------------------
+ * Replaces data/oxford/build_dataset.py:79-148 (my_build_pointcloud) and :310,319-321 (camera frame, float32 record); the voxel pass between
+ * them (:151-166) is di2p_voxel_down_sample at 0.1 m on the float32 rows di2p_submap_build writes.
+ * A batch of B sub-maps of one traversal, ragged on two levels (all device memory): scan_xyr f64[P_cap,3] the rows of the .bin files (x, y,
+ *   reflectance; x points to the ground), scan_offsets i32[S_cap+1] profile -> rows, submap_offsets i32[B+1] sub-map -> profiles, poses
+ *   f64[S_cap,4,4] the pose of each profile relative to its sub-map's origin time (rigid), present u8[S_cap] (may be NULL: all present; 0: the
+ *   scan file does not exist), G_posesource_laser f64[4,4].  S_cap / P_cap: the capacities of the profile / row buffers; entries past
+ *   submap_offsets[B] / the last scan offset are never read.
+ * di2p_submap_build, six launches, no allocation, no synchronisation:
+ *   keep rule, sequential per sub-map: a missing profile is passed over; a present one is skipped iff skip_threshold >= 0, a previous KEPT
+ *     profile exists and |R_prev^T (t - t_prev)|^2 < skip_threshold^2 in fp64 (products rounded, sums in ascending index; the translation of
+ *     inv(prev) . pose with the squares compared).  kept i32[S_cap]: 1 kept, 0 skipped, -1 missing or outside every accepted sub-map;
+ *     skip_count i32[B].  A kept profile is the next "previous" even if the ground filter leaves it no rows.
+ *   rows: with remove_ground != 0 a row survives iff x < ground_threshold (fp64).  M = pose . G_posesource_laser per kept profile, each entry
+ *     a dot product in ascending k; p = (M[:,0] x + M[:,1] y) + M[:,3], no fused multiply-add; out_points f32[cap,4] rows (p_x, p_y, p_z,
+ *     reflectance), each value rounded once, in profile order, then row order (stable); out_offsets i32[B+1].
+ *   status i32[B] (may be NULL): 0 ok; 1 more than max_frame_points (<= 2^20) surviving rows, or rows that would pass cap; 3 bad offsets
+ *     (submap_offsets[0 .. b+1] not a non-decreasing sequence in [0, S_cap] from 0, or a profile of the sub-map without
+ *     0 <= scan_offsets[s] <= scan_offsets[s+1] <= P_cap); 4 no profile or no surviving row.  A sub-map with a status has no output rows.
+ *   workspace: di2p_submap_workspace_bytes(B, S_cap) bytes, 256-byte aligned.
+ * di2p_scan_prep_centroids_offset (csrc/scan_prep.hip): byte offset, in the workspace di2p_voxel_down_sample ran with (same B, cap), of
+ *   its fp64 means f64[cap,3] in output point order (-1 for bad sizes); valid until the next call that uses the workspace.
+ * di2p_submap_to_camera: row v of sub-map b (voxel_offsets i32[B+1]) -> out_points f32[cap,4] = (G_cam[b] . (centroids[v], 1) in fp64,
+ *   ascending k, no fused multiply-add, rounded once; intensity[v]).  G_cam f64[B,4,4] = inv(G_camera_image) . G_camera_posesource. */
+long long di2p_submap_workspace_bytes(int B, int S_cap);
+int di2p_submap_build(const double* scan_xyr, const int32_t* scan_offsets, const int32_t* submap_offsets, const double* poses,
+                      const uint8_t* present, const double* G_posesource_laser, int B, int S_cap, int P_cap, int cap, int max_frame_points,
+                      double skip_threshold, double ground_threshold, int remove_ground, int32_t* kept, int32_t* skip_count,
+                      int32_t* out_offsets, float* out_points, int32_t* status, void* workspace, void* stream);
+long long di2p_scan_prep_centroids_offset(int B, int cap);
+int di2p_submap_to_camera(const double* centroids, const float* intensity, const int32_t* voxel_offsets, const double* G_cam, int B, int cap,
+                          float* out_points, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
