@@ -160,6 +160,9 @@ _SIGS = {
     "di2p_vis_registration": [c_void_p] * 5 + [c_int] * 7 + [c_void_p] * 3,
     "di2p_submap_build": [c_void_p] * 6 + [c_int] * 5 + [c_double, c_double, c_int] + [c_void_p] * 7,
     "di2p_submap_to_camera": [c_void_p] * 4 + [c_int, c_int, c_void_p, c_void_p],
+    "di2p_pose_matrices": [c_void_p, c_int, c_void_p, c_void_p],
+    "di2p_sweep_transforms": [c_void_p] * 5 + [c_int, c_int] + [c_void_p] * 3,
+    "di2p_sweep_accumulate": [c_void_p] * 4 + [c_int] * 6 + [c_float, c_float] + [c_void_p] * 6,
 }
 _WS_SIGS = {        # <name>_workspace_bytes helpers returning long long
     "di2p_channel_reduce_workspace_bytes": [c_int] * 3,
@@ -178,6 +181,7 @@ _WS_SIGS = {        # <name>_workspace_bytes helpers returning long long
     "di2p_vis_workspace_bytes": [c_int] * 5,
     "di2p_submap_workspace_bytes": [c_int, c_int],
     "di2p_scan_prep_centroids_offset": [c_int, c_int],
+    "di2p_sweep_workspace_bytes": [c_int, c_int],
 }
 EXPORTS = sorted(list(_SIGS) + ["di2p_last_error", "di2p_version", "di2p_solve_workspace_bytes", "di2p_solver_set_profile_buffer", "di2p_pnp_workspace_bytes",
                  "di2p_conv2d_workspace_bytes", "di2p_set_option", "di2p_get_option", "di2p_random_choice_workspace_bytes", "di2p_classifier_loss_workspace_bytes", "di2p_normals_cells_candidates"] + list(_WS_SIGS))

@@ -6,9 +6,11 @@
 
 in one call.  RawFramePlan is the fixed-capacity, preallocated form (the style of scan_prep.BatchPlan / sample_prep.SamplePlan): run()
 launches everything on the current stream with no allocation and no host synchronisation, so it can be captured in a hipGraph.  The
-result equals scan_prep.preprocess_velodyne followed by sample_prep.prepare_samples bit for bit.  Only the KITTI path has a raw-scan
-stage in the reference (the Oxford / nuScenes loaders read offline records without normals): other data sets raise ValueError.  The Oxford
-data set's own raw stage -- sub-maps from LMS profiles, data/oxford/build_dataset.py -- is deepi2p_amd.submap (SubmapPlan, OxfordRawPlan).
+result equals scan_prep.preprocess_velodyne followed by sample_prep.prepare_samples bit for bit.  This plan is the KITTI raw stage (a
+record with normals from one Velodyne scan): other data sets raise ValueError.  The Oxford loader reads offline records without normals;
+the raw stage that writes them -- sub-maps from LMS profiles, data/oxford/build_dataset.py -- is deepi2p_amd.submap (SubmapPlan,
+OxfordRawPlan).  The nuScenes loader reads no offline record: its __getitem__ reads up to seven raw LiDAR sweeps per sample, cuts the ego car
+out of each and accumulates them in the key sweep's frame; that raw stage is deepi2p_amd.sweeps (SweepPlan, NuScenesRawPlan).
 """
 import numpy as np
 import torch

@@ -376,6 +376,99 @@ def make_lms_traversal(rng, submaps, scans, points_per_scan, speed=10.0, skip_th
     return dict(submaps=out, G_posesource_laser=G_laser, G_cam=G_cam)
 
 
+def _quat_mul(a, b):
+    """Hamilton product of two quaternions (w, x, y, z)"""
+    aw, ax, ay, az = a
+    bw, bx, by, bz = b
+    return np.array([aw * bw - ax * bx - ay * by - az * bz, aw * bx + ax * bw + ay * bz - az * by,
+                     aw * by - ax * bz + ay * bw + az * bx, aw * bz + ax * by - ay * bx + az * bw])
+
+
+def _quat_axis(axis, a):
+    q = np.zeros(4)
+    q[0], q[1 + axis] = math.cos(a / 2.0), math.sin(a / 2.0)
+    return q
+
+
+def _quat_matrix(q, t):
+    """the 4x4 of a record in fp64 (no float32 rounding: the scene is built from the exact poses)"""
+    w, x, y, z = np.asarray(q, dtype=np.float64) / np.linalg.norm(q)
+    P = np.eye(4)
+    P[:3, :3] = [[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                 [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                 [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]]
+    P[:3, 3] = t
+    return P
+
+
+def make_nuscenes_sweeps(rng, B, sweeps_per_frame, rows, frame_skip=4, speed=8.0, rate=20.0, ego_share=0.04):
+    """B nuScenes samples as the raw stage reads them (deepi2p_amd.sweeps): per frame `sweeps_per_frame` LiDAR sweeps (an int, or one count per
+    frame; the key sweep first, then the `next` picks, then the `prev` picks, `frame_skip` sweeps of 1 / `rate` s apart) of `rows` rows (an int,
+    or one count per sweep of the batch) with the five float32 columns of a .pcd.bin file (x, y, z, intensity, ring) in the LiDAR frame
+    (x right, y forward, z up).  The scene is z-up and static: a road, walls along it, seen from an ego vehicle (x forward, y left, z up) that
+    drives a gentle curve at about `speed` m/s a few thousand metres from the map's origin, so the float32 rounding of the pose translations
+    matters.  About `ego_share` of the rows are returns on the ego car, inside the box the loader cuts out.  Every pose and calibration is a
+    record (w, x, y, z, tx, ty, tz) as the data set stores it.
+    -> dict(frames=[[f32[n,5], ...], ...], ego=[f64[S_b,7], ...], lidar_calib, cam_pose, cam_calib f64[B,7])"""
+    counts = [int(sweeps_per_frame)] * int(B) if np.ndim(sweeps_per_frame) == 0 else [int(c) for c in sweeps_per_frame]
+    n_rows = [int(rows)] * sum(counts) if np.ndim(rows) == 0 else [int(r) for r in rows]
+    if len(counts) != B or len(n_rows) != sum(counts):
+        raise ValueError("make_nuscenes_sweeps: one sweep count per frame and one row count per sweep")
+    lidar_q = _quat_mul(_quat_axis(2, -math.pi / 2 + 0.004), _quat_mul(_quat_axis(1, 0.003), _quat_axis(0, -0.002)))
+    lidar_t = np.array([0.943713, 0.0, 1.84023])
+    cam_q = _quat_mul(np.array([0.5, -0.5, 0.5, -0.5]), _quat_axis(1, 0.006))          # x right, y down, z forward; a small mounting error
+    cam_t = np.array([1.70079, 0.0159, 1.51095])
+    origin = np.array([2100.0, 1650.0, 0.0]) + rng.uniform(-400.0, 400.0, 3) * [1, 1, 0]
+    heading0 = rng.uniform(0, 2 * math.pi)
+
+    def ego_at(time):
+        """record of the ego pose `time` seconds along the drive"""
+        d = speed * time
+        yaw = heading0 + 0.2 * math.sin(d / 40.0)
+        pos = origin + d * np.array([math.cos(heading0), math.sin(heading0), 0.0]) + 8.0 * (1 - math.cos(d / 40.0)) * np.array(
+            [-math.sin(heading0), math.cos(heading0), 0.0])
+        q = _quat_mul(_quat_axis(2, yaw), _quat_mul(_quat_axis(1, 0.004 * math.sin(d / 7.0)), _quat_axis(0, 0.003 * math.cos(d / 5.0))))
+        return np.concatenate([q, pos + [0.0, 0.0, 0.01 * math.sin(d / 3.0)]])
+
+    axis, side = np.array([math.cos(heading0), math.sin(heading0), 0.0]), np.array([-math.sin(heading0), math.cos(heading0), 0.0])
+    frames, ego, cam_pose, k = [], [], [], 0
+    for b, S in enumerate(counts):
+        t0 = 2.0 + 1.5 * b
+        n_next = min(S - 1, (S - 1 + 1) // 2) if S else 0
+        times = [t0] + [t0 + (j + 1) * frame_skip / rate for j in range(n_next)] + [t0 - (j + 1) * frame_skip / rate for j in range(max(S - 1 - n_next, 0))]
+        recs, sweeps = [], []
+        for time in times[:S]:
+            rec = ego_at(time)
+            n = n_rows[k]
+            k += 1
+            world_from_lidar = _quat_matrix(rec[:4], rec[4:]) @ _quat_matrix(lidar_q, lidar_t)
+            centre = world_from_lidar[:3, 3]
+            n_car = int(round(ego_share * n))
+            n_wall = int(0.4 * (n - n_car))
+            n_road = n - n_car - n_wall
+            r, az = 3.0 + 57.0 * rng.random(n_road) ** 1.5, rng.uniform(0, 2 * math.pi, n_road)
+            road = centre + np.stack([r * np.cos(az), r * np.sin(az), np.zeros(n_road)], 1)
+            road[:, 2] = 0.0
+            along = np.dot(centre - origin, axis) + rng.uniform(-60.0, 60.0, n_wall)
+            wall = origin + along[:, None] * axis + (np.where(rng.random(n_wall) < 0.5, -9.0, 17.0))[:, None] * side
+            wall[:, 2] = rng.uniform(0.0, 6.0, n_wall)
+            world = np.concatenate([road, wall]) + rng.normal(0.0, 0.01, (n_road + n_wall, 3))
+            inv = np.linalg.inv(world_from_lidar)
+            local = world @ inv[:3, :3].T + inv[:3, 3]
+            car = np.stack([rng.uniform(-0.78, 0.78, n_car), rng.uniform(-2.6, 2.6, n_car), rng.uniform(-1.6, -0.4, n_car)], 1)
+            pts = np.concatenate([local, car])[rng.permutation(n)] if n else np.zeros((0, 3))
+            inten = np.rint(rng.uniform(0.0, 255.0, n))
+            ring = rng.integers(0, 32, n).astype(np.float64)
+            sweeps.append(np.ascontiguousarray(np.concatenate([pts, inten[:, None], ring[:, None]], 1).astype(np.float32)))
+            recs.append(rec)
+        frames.append(sweeps)
+        ego.append(np.stack(recs) if recs else np.zeros((0, 7)))
+        cam_pose.append(ego_at(t0 + 0.012))          # the camera frame closest in time has an ego pose of its own
+    lidar_calib = np.tile(np.concatenate([lidar_q, lidar_t]), (B, 1))
+    cam_calib = np.tile(np.concatenate([cam_q, cam_t]), (B, 1))
+    return dict(frames=frames, ego=ego, lidar_calib=lidar_calib, cam_pose=np.stack(cam_pose) if B else np.zeros((0, 7)), cam_calib=cam_calib)
+
+
 def make_camera_image(rng, H0=370, W0=1226):
     """A synthetic camera frame u8[H0, W0, 3] (HWC, as np.load gives the loader's images) that reaches every branch of the colour code:
     smooth gradients (every hue sector), per-pixel texture, saturated primaries, pure black / white, and exactly grey patches."""

@@ -708,6 +708,36 @@ long long di2p_scan_prep_centroids_offset(int B, int cap);
 int di2p_submap_to_camera(const double* centroids, const float* intensity, const int32_t* voxel_offsets, const double* G_cam, int B, int cap,
                           float* out_points, void* stream);
 
+/* ---- (additive, ABI 9; detect by symbol) nuScenes sweep accumulation (csrc/sweeps.hip) -------------------------------------------------------
+ * Replaces the raw stage of data/nuscenes_pc_img_pose_loader.py: :58-78 (pose and calibration matrices), :194-210 (the ego-box filter of a
+ * sweep), :213-267 (the accumulation of up to seven sweeps in the key sweep's LiDAR frame) and :292-293, :324-325, :351-354 (P_cam_pc).
+ * di2p_pose_matrices: records f64[n,7] (quaternion w, x, y, z, translation) -> out f64[n,4,4]: q / |q|, the closed form of the rotation
+ *   matrix in fp64 (products and sums rounded separately), every rotation entry and the translation rounded to float32; last row 0 0 0 1.
+ * A batch of B frames, ragged on two levels (all device memory): rows f32[P_cap,cols], cols 4 (x, y, z, intensity) or 5 (the .pcd.bin rows;
+ *   the ring is not read), sweep_offsets i32[S_cap+1] sweep -> rows, frame_offsets i32[B+1] frame -> sweeps, the key sweep first, then the
+ *   `next` picks, then the `prev` picks.  Entries past frame_offsets[B] / the last sweep offset are never read.
+ * di2p_sweep_transforms: P_ego f64[S_cap,4,4] the ego pose of every sweep, P_vehicle_lidar / P_ego_cam / P_vehicle_cam f64[B,4,4] the LiDAR
+ *   calibration, the camera's ego pose and the camera calibration of every frame (affine: the last row is taken as 0 0 0 1) ->
+ *   T f64[S_cap,4,4]: the exact identity for a frame's first sweep, else (inv(P_vehicle_lidar) . (inv(P_ego[key]) . P_ego[s])) . P_vehicle_lidar;
+ *   P_cam_pc f64[B,4,4] = inv(P_vehicle_cam) . (inv(P_ego_cam) . (P_ego[key] . P_vehicle_lidar)) (zeros for a frame without a sweep).  fp64,
+ *   4x4 products in ascending k, inverses as adj(M) / det(M) and -(M^-1 . t); no fused multiply-add.  A frame whose sweep range does not lie
+ *   in [0, S_cap] is left alone.
+ * di2p_sweep_accumulate, six launches, no allocation, no synchronisation: a row is removed iff -box_x < x < box_x and -box_y < y < box_y
+ *   in float32; the surviving rows of a frame in sweep order, then row order (stable) -> out_points f32[cap,4]: rows of the key sweep and every
+ *   intensity bit for bit, the coordinates of the other sweeps ((T[r,0] x + T[r,1] y) + T[r,2] z) + T[r,3] in fp64, rounded once to float32;
+ *   out_offsets i32[B+1]; kept i32[S_cap] surviving rows per sweep (0 outside the accepted frames).  Rows past out_offsets[B] are not written.
+ *   status i32[B] (may be NULL): 0 ok; 1 more than max_frame_points (<= 2^20) surviving rows, or rows that would pass cap; 3 bad offsets
+ *     (frame_offsets[0 .. b+1] not a non-decreasing sequence in [0, S_cap] from 0, or a sweep of the frame without
+ *     0 <= sweep_offsets[s] <= sweep_offsets[s+1] <= P_cap); 4 no sweep or no surviving row.  A frame with a status has no output rows.
+ *   workspace: di2p_sweep_workspace_bytes(B, S_cap) bytes (0 for bad sizes; S_cap <= 2^24), 256-byte aligned. */
+long long di2p_sweep_workspace_bytes(int B, int S_cap);
+int di2p_pose_matrices(const double* records, int n, double* out, void* stream);
+int di2p_sweep_transforms(const double* P_ego, const int32_t* frame_offsets, const double* P_vehicle_lidar, const double* P_ego_cam,
+                          const double* P_vehicle_cam, int B, int S_cap, double* T, double* P_cam_pc, void* stream);
+int di2p_sweep_accumulate(const float* rows, const int32_t* sweep_offsets, const int32_t* frame_offsets, const double* T, int B, int S_cap,
+                          int P_cap, int cols, int cap, int max_frame_points, float box_x, float box_y, int32_t* kept, int32_t* out_offsets,
+                          float* out_points, int32_t* status, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
