@@ -6,8 +6,17 @@
 // The routine is written once over a "point set" policy: every pass over the points is a for_each + a reduction, so the
 // same code runs with ONE THREAD per minimal sample (RANSAC hypotheses: 4-5 points in registers, reduce = identity) and with
 // ONE WAVEFRONT per frame (the re-fit on all inliers: lanes stride over the inliers, reduce = wave butterfly sum).
+//
+// The header uses nothing of common.h but the HIP qualifiers: with DI2P_EPNP_HOST defined it compiles as plain C++ (tests/epnp_host.cpp
+// runs the routine on the CPU against oracle/epnp_np.py).
 #pragma once
+#ifdef DI2P_EPNP_HOST
+#ifndef __device__
+#define __device__
+#endif
+#else
 #include "common.h"
+#endif
 
 #include <float.h>
 #include <math.h>
@@ -132,6 +141,10 @@ __device__ inline void solve(PS& ps, const Cam4& k, Pose& out, Polish polish = P
     {   // directions in descending eigenvalue order, as OpenCV's SVD delivers them
         int ord[3] = {0, 1, 2};
         for (int i = 0; i < 3; ++i) for (int j = i + 1; j < 3; ++j) if (C3[ord[j] * 3 + ord[j]] > C3[ord[i] * 3 + ord[i]]) { const int t = ord[i]; ord[i] = ord[j]; ord[j] = t; }
+        // coincident, collinear or coplanar points: the smallest eigenvalue of the scatter is rounding noise (the n-term sums and the
+        // eigen-solver leave about n eps of the largest one), its direction and length are arbitrary and there are no control points.  An
+        // absolute test of det(CC) below does not see this: the noise is ~1e-16 of the spread, not 1e-300.
+        if (!(C3[ord[2] * 3 + ord[2]] > 8.0 * n * DBL_EPSILON * C3[ord[0] * 3 + ord[0]])) return;
         for (int i = 0; i < 3; ++i) {
             const double kk = sqrt(fmax(C3[ord[i] * 3 + ord[i]], 0.0) / n);
             // sign convention of a principal direction: its largest component is positive (with noisy correspondences EPnP is

@@ -77,6 +77,17 @@ __device__ __forceinline__ bool inv3(const double* M, double* inv) {
     return true;
 }
 
+// max |R R^T - I| (NaN if an entry is)
+__device__ __forceinline__ double orth_defect(const double* R) {
+    double worst = 0.0;
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {
+            const double d = fabs(R[r * 3] * R[c * 3] + R[r * 3 + 1] * R[c * 3 + 1] + R[r * 3 + 2] * R[c * 3 + 2] - (r == c ? 1.0 : 0.0));
+            if (d > worst || d != d) worst = d;  // a NaN is taken and then kept
+        }
+    return worst;
+}
+
 // hypothesis layout: R (row-major 9), t (3), valid flag as double (12 + 1)
 constexpr int HYP = 13;
 
@@ -160,6 +171,18 @@ __global__ __launch_bounds__(64) void pnp_hypotheses_kernel(const Corr* __restri
         if (!inv3(R, inv)) return;
         for (int r = 0; r < 3; ++r) for (int a = 0; a < 3; ++a) R[r * 3 + a] = 0.5 * (R[r * 3 + a] + inv[a * 3 + r]);
     }
+    // Eight steps reach the rotation from any sample of inliers (the start is then a rotation up to noise).  The matrix of a sample that
+    // holds an outlier can be orders of magnitude away from one, each step only halves its largest singular value, and what the eight steps
+    // left used to be scored as if it were a rotation.  Go on until R R^T = I to rounding (untouched where the eight steps got there) and
+    // refuse the sample otherwise.
+    double orth = orth_defect(R);
+    for (int k = 8; k < 64 && orth > 1e-13; ++k) {
+        double inv[9];
+        if (!inv3(R, inv)) return;
+        for (int r = 0; r < 3; ++r) for (int a = 0; a < 3; ++a) R[r * 3 + a] = 0.5 * (R[r * 3 + a] + inv[a * 3 + r]);
+        orth = orth_defect(R);
+    }
+    if (!(orth <= 1e-9)) return;
     const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
     if (!(det > 0.5)) return;
     for (int a = 0; a < 9; ++a) { if (!isfinite(R[a])) return; h[a] = R[a]; }

@@ -39,14 +39,35 @@ def pack_correspondences(pc, coarse, fine, W_fine, pixels=None):
     return corr, n_corr
 
 
+def _align256(n):
+    return (n + 255) // 256 * 256
+
+
+def workspace_views(ws, F, N, iters):
+    """The intermediates both RANSAC entry points leave in their workspace (layout: include/deepi2p_hip.h, di2p_pnp_workspace_bytes), as
+    VIEWS of `ws` u8[>= di2p_pnp_workspace_bytes(F, N, iters)], readable after the call (tests, debugging):
+    corr f32[F,N,8] (the first n_corr[f] records of a frame valid), hyp f64[F,iters,13] = R (9, row-major), t (3), valid flag,
+    inliers i32[F,iters] (-1: invalid hypothesis), mask u8[F,N] (inliers of the final round; written for frames with a model only)."""
+    sizes = (F * N * 32, F * iters * 13 * 8, F * iters * 4, F * N)
+    offs = [0]
+    for s in sizes[:-1]:
+        offs.append(offs[-1] + _align256(s))
+    if ws.dtype != torch.uint8 or ws.dim() != 1 or ws.numel() < offs[3] + sizes[3]:
+        raise ValueError("workspace must be a flat uint8 tensor of at least di2p_pnp_workspace_bytes(F, N, iters) bytes")
+    part = [ws[o:o + s] for o, s in zip(offs, sizes)]
+    return dict(corr=part[0].view(torch.float32).view(F, N, 8), hyp=part[1].view(torch.float64).view(F, iters, 13),
+                inliers=part[2].view(torch.int32).view(F, iters), mask=part[3].view(F, N))
+
+
 def pnp_ransac(pc, coarse, fine, K_scaled, W_fine, samples, reproj_err=0.6, refine_rounds=20, refine_iters=5, pixels=None,
-               method="epnp"):
+               method="epnp", return_workspace=False):
     """Batched device entry.  pc f32[F,3,N], coarse/fine i32[F,N], K_scaled f64[F,3,3], samples i32[F,iters,6]
     -> dict(P f64[F,4,4], outlier_ratio f64[F], n_inliers, n_corr, best i32[F]).
     method "epnp" (default -- what the reference asks OpenCV for, registration_pnp.py:125-132): EPnP minimal-sample hypotheses (5 points,
     or 4 when a frame has only 4) + one EPnP re-fit on the inliers, the estimator of cv2.solvePnPRansac(flags=SOLVEPNP_EPNP);
     "dlt_lo": the builder's 6-point DLT hypotheses + locally optimised best model (more robust on cell-quantised observations, but not the
-    reference's algorithm; refine_rounds / refine_iters apply to it only)."""
+    reference's algorithm; refine_rounds / refine_iters apply to it only).
+    return_workspace: add the stage intermediates corr, hyp, inliers, mask (workspace_views: views of the call's workspace, no copies)."""
     require_cuda(pc, coarse, fine, K_scaled, samples, pixels)
     F, _, N = pc.shape
     iters = samples.shape[1]
@@ -65,7 +86,10 @@ def pnp_ransac(pc, coarse, fine, K_scaled, W_fine, samples, reproj_err=0.6, refi
              float(reproj_err), int(refine_rounds), int(refine_iters), F, N, ptr(P), ptr(ratio), ptr(n_in), ptr(n_corr), ptr(best), ptr(ws), stream())
     else:
         raise ValueError("method must be 'epnp' or 'dlt_lo'")
-    return dict(P=P, outlier_ratio=ratio, n_inliers=n_in, n_corr=n_corr, best=best)
+    out = dict(P=P, outlier_ratio=ratio, n_inliers=n_in, n_corr=n_corr, best=best)
+    if return_workspace:
+        out.update(workspace_views(ws, F, N, iters))
+    return out
 
 
 def solve_PnP(pc_np, coarse_predictions_np, fine_predictions_np, K_np, H, W, fine_resolution_scale, iterationsCount,

@@ -378,7 +378,15 @@ int di2p_pack_pc_label(const float* pc, const int32_t* coarse_pred, const int32_
  *   reproj_err in scaled pixels (reference: 0.6); local optimisation of the best model: refine_rounds rounds of
  *   {re-estimate inliers, refine_iters Gauss-Newton steps}, a round kept only if it loses no inliers.
  *   -> P f64[F,4,4] (identity when rejected), outlier_ratio f64[F] (1 when rejected), n_inliers, n_corr, best i32[F].
- *   workspace: di2p_pnp_workspace_bytes(F, N, iters). */
+ *   workspace: di2p_pnp_workspace_bytes(F, N, iters).
+ *   Both RANSAC entry points lay the workspace out the same way, each region starting where the one before it ends, rounded up to 256 bytes:
+ *     corr    f32[F][N][8]       the packed correspondences {x, y, z, u, v, 0, 0, 0}, the first n_corr[f] records of frame f valid
+ *     hyp     f64[F][iters][13]  per hypothesis R (9, row-major), t (3), valid flag (0 / 1); R and t are undefined where the flag is 0
+ *     inliers i32[F][iters]      per-hypothesis inlier count, -1 for an invalid hypothesis
+ *     mask    u8[F][N]           the inlier mask over the frame's records: of the winning hypothesis (EPnP), of the model the last
+ *                                refinement round started from (DLT); written for frames with a model only
+ *   The regions are READABLE AFTER THE CALL, for tests and debugging (deepi2p_amd/registration_pnp.py: workspace_views); nothing outside
+ *   them is defined, and the end of `mask` lies within di2p_pnp_workspace_bytes(F, N, iters). */
 long long di2p_pnp_workspace_bytes(int F, int N, int iters);
 /* The correspondence list alone: what solve_PnP (evaluation/registration_pnp.py:97-110) hands to cv2.solvePnPRansac (:125-127) -- points =
  * pc[:, coarse == 1], pixels = (fine - floor(fine / W) * W, floor(fine / W)), in point order.  corr f32[F][N][8] = {x, y, z, u, v, 0, 0, 0},

@@ -33,8 +33,15 @@ def accept(R, t, n_inliers, n_corr, success=True):
     return P, 1.0
 
 
-def dlt6(X, uv, K):
-    """X 3x6, uv 2x6 -> (R, t) or None."""
+def dlt6(X, uv, K, with_sv=False):
+    """X 3x6, uv 2x6 -> (R, t) or None.  with_sv: -> ((R, t) or None, s[10] / s[0]): the relative gap that separates the null vector of the
+    11 x 12 system from the rest -- its reciprocal is the condition of the hypothesis (0.0 when the sample is refused before the SVD)."""
+    gap = []
+    sol = _dlt6(X, uv, K, gap)
+    return (sol, gap[0] if gap else 0.0) if with_sv else sol
+
+
+def _dlt6(X, uv, K, gap):
     fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
     xh, yh = (uv[0] - cx) / fx, (uv[1] - cy) / fy
     cen = X.mean(axis=1, keepdims=True)
@@ -50,6 +57,7 @@ def dlt6(X, uv, K):
         rows.append([0, 0, 0, 0, x, y, z, 1, -yh[j] * x, -yh[j] * y, -yh[j] * z, -yh[j]])
     A = np.array(rows[:11])
     _, s, Vt = np.linalg.svd(A)
+    gap.append(float(s[10] / max(s[0], 1e-300)))
     if s[10] < 1e-10 * max(s[0], 1e-300):
         return None
     p = Vt[-1].reshape(3, 4)

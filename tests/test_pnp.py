@@ -1,13 +1,21 @@
 """PnP back end of BASELINE config 3 (evaluation/registration_pnp.py:95-148).  PARITY UNPINNED w.r.t. OpenCV (absent;
-internal RNG): the oracle (oracle/pnp_np.py) is pinned by pose recovery, the HIP kernel is compared with the oracle on
-identical RANSAC draws.  Tolerances: exact correspondences -> pose within 1e-6; HIP vs oracle -> per-hypothesis inlier
-counts equal for >= 99 % of the hypotheses (a count can differ when a reprojection error sits on the 0.6 px threshold),
-final pose within 1e-6 m / 1e-6 rad when both select the same model."""
+internal RNG).  What is asserted, and where:
+  * the oracles (oracle/pnp_np.py, oracle/epnp_np.py) by pose recovery from exact and from cell-quantised correspondences: here, on the CPU;
+  * csrc/epnp.h itself against oracle/epnp_np.py, on the CPU: tests/test_epnp_host.py;
+  * every stage of both HIP RANSAC variants on the device's own intermediates (pack bit for bit, per-hypothesis validity and poses on
+    clean samples, every per-hypothesis inlier count inside a 1e-9 threshold band, the argmax and its tie rule, mask, re-fit / refinement,
+    acceptance): tests/test_gpu_pnp_stages.py;
+  * here, on the GPU, whole RANSAC runs on identical draws.  The pose is compared UNCONDITIONALLY through the workspace (stages D and E of
+    the stage tests: best = the lowest index among the maxima of the device's counts; P = the oracle's re-fit / refinement of the device's
+    winner, EPnP within pnp_cases.REFIT_BOUND, DLT within 1e-8); where the device's and the oracle's per-hypothesis count arrays agree
+    the winner must be the oracle's; where the winner is the oracle's the pose must be the oracle's within 1e-6 m / 1e-6 rad; exact
+    correspondences -> ground truth within 1e-3 m / 1e-4 rad (DLT) and 5e-2 m / 5e-3 rad (EPnP with 30 % gross outliers)."""
 import numpy as np
 import pytest
 
 from deepi2p_amd import synthetic
 from oracle import pnp_np
+from tests import pnp_cases
 
 H, W, SCALE = 160, 512, 32
 
@@ -87,12 +95,22 @@ def test_hip_matches_oracle_on_identical_draws(dev):
     sm = torch.from_numpy(np.stack([fr[5] for fr in frames])).to(dev)
     Wf = frames[0][6]
     for use_pixels in (True, False):
-        out = rp.pnp_ransac(pc, co, fi, K, Wf, sm, pixels=px if use_pixels else None, method="dlt_lo")      # vs the DLT oracle
+        out = rp.pnp_ransac(pc, co, fi, K, Wf, sm, pixels=px if use_pixels else None, method="dlt_lo", return_workspace=True)      # vs the DLT oracle
+        o = {k: v.cpu().numpy() for k, v in out.items()}
+        left_out = 0
         for i, fr in enumerate(frames):
             P, ratio, nin, cnt, best, counts = pnp_np.pnp_ransac(fr[0]["pc"], fr[2], fr[3], fr[1], Wf, fr[5],
                                                                  pixels=fr[4] if use_pixels else None)
             assert int(out["n_corr"][i]) == cnt
             Pg = out["P"][i].cpu().numpy()
+            # unconditional: the winner by the device's own counts, the pose by the oracle's refinement of the device's winner
+            # (a frame of cell-quantised observations may have no model at all: no hypothesis with six inliers; check_select pins that output)
+            if pnp_cases.check_select(o, i, "dlt_lo"):
+                left_out += not pnp_cases.check_dlt_final(o, i, fr[1])
+            else:
+                assert not use_pixels
+            if np.array_equal(o["inliers"][i], counts):
+                assert int(out["best"][i]) == best, (use_pixels, i)
             if int(out["best"][i]) == best:
                 t, r = _pose_err(Pg, P)
                 assert t < 1e-6 and r < 1e-6, (use_pixels, i, t, r)
@@ -100,6 +118,7 @@ def test_hip_matches_oracle_on_identical_draws(dev):
             t, r = _pose_err(Pg, fr[0]["P_gt"])
             if use_pixels:
                 assert t < 1e-3 and r < 1e-4
+        assert left_out <= 1, left_out      # a record inside the 1e-9 threshold band in some refinement round: at most one frame of three
 
 
 @pytest.mark.gpu
@@ -164,8 +183,11 @@ def test_epnp_ransac_oracle_with_outliers():
 
 @pytest.mark.gpu
 def test_hip_epnp_ransac_matches_oracle(dev):
-    """HIP EPnP RANSAC vs the restatement on identical draws: per-hypothesis inlier counts (>= 99 % equal), the same winner, the
-    re-fitted pose to 1e-6; exact correspondences with 30 % gross outliers -> ground truth recovered."""
+    """HIP EPnP RANSAC vs the restatement on identical draws: the same winner, the inlier count within 2, the re-fitted pose to 1e-6 where the
+    inlier sets have the same size; UNCONDITIONALLY, through the workspace: best = the lowest index among the maxima of the device's counts,
+    the mask inside the threshold band of the device's winner, P = the oracle's EPnP on the device's masked records within
+    pnp_cases.REFIT_BOUND (2.21e-10 m / 4.32e-11 rad = 1000 x the host-header-vs-oracle maximum measured on these frames and the stage case);
+    exact correspondences with 30 % gross outliers -> ground truth recovered."""
     import torch
     from deepi2p_amd import registration_pnp as rp
     from oracle import epnp_np
@@ -184,7 +206,8 @@ def test_hip_epnp_ransac_matches_oracle(dev):
     pc, px, co = [torch.from_numpy(np.stack(a)).to(dev) for a in (pcs, pxs, cos)]
     Kt = torch.from_numpy(np.stack([K] * F)).to(dev)
     fi = torch.zeros((F, N), dtype=torch.int32, device=dev)
-    out = rp.pnp_ransac(pc, co, fi, Kt, 16, torch.from_numpy(samples).to(dev), pixels=px, method="epnp")
+    out = rp.pnp_ransac(pc, co, fi, Kt, 16, torch.from_numpy(samples).to(dev), pixels=px, method="epnp", return_workspace=True)
+    o = {k: v.cpu().numpy() for k, v in out.items()}
     out2 = rp.pnp_ransac(pc, co, fi, Kt, 16, torch.from_numpy(samples).to(dev), pixels=px, method="epnp")
     assert torch.equal(out["P"], out2["P"])
     for f in range(F):
@@ -192,6 +215,7 @@ def test_hip_epnp_ransac_matches_oracle(dev):
         X, uv = pcs[f][:, m].astype(np.float64), pxs[f][:, m].astype(np.float64)
         R, t, mask, best, counts = epnp_np.epnp_ransac(X, uv, K, samples[f], reproj_err=0.6)
         assert int(out["n_corr"][f]) == X.shape[1]
+        assert pnp_cases.check_select(o, f, "epnp") and pnp_cases.check_epnp_final(o, f, K) is not None
         assert int(out["best"][f]) == best and abs(int(out["n_inliers"][f]) - int(mask.sum())) <= 2
         Po = np.eye(4)
         Po[:3, :3], Po[:3, 3] = R, t
