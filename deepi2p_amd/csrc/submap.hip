@@ -7,22 +7,23 @@
 //           data/oxford/build_dataset.py:310,319-321  the camera-frame transform of the voxel means and the float32 record
 // The voxel pass between the two (:151-166, downsample) is di2p_voxel_down_sample (scan_prep.hip), unchanged.
 //
-// A batch is ragged on two levels: sub-map -> profiles (submap_offsets), profile -> rows (scan_offsets).  Stages:
-//   A  keep_kernel      one wave per sub-map: offset checks, then the sequential keep chain (poses staged through LDS 64 at a time)
+// A batch is ragged on two levels: sub-map -> profiles (submap_offsets), profile -> rows (scan_offsets).  What that shares with the
+// frames and sweeps of sweeps.hip is in ragged2.h: the offset acceptance (check_offsets2), the chunked 64-bit wave prefix (wave_prefix),
+// offsets_kernel, the status codes and the workspace helpers.  Stages:
+//   A  keep_kernel      one wave per sub-map: offset checks (ragged2.h), then the sequential keep chain (poses staged through LDS 64 at a time)
 //   B  count_kernel     one wave per profile: surviving rows (ballot + popcount)
-//      prefix_kernel    one wave per sub-map: exclusive prefix of the counts over its profiles, the sub-map's total
-//      offsets_kernel   one wave: exclusive prefix over the sub-maps, status
+//      prefix_kernel    one wave per sub-map: exclusive prefix of the counts over its profiles, the sub-map's total (ragged2.h's wave_prefix)
+//      offsets_kernel   (ragged2.h) one wave: exclusive prefix over the sub-maps, status
 //   C  write_kernel     one wave per profile: M = pose . G once, rows read as coalesced 8-byte loads through LDS, ordered compaction with the
 //                       ballot prefix, one 16-byte store per surviving row
 //   E  to_camera_kernel one thread per voxel mean: G_cam in fp64, the record row
 // All arithmetic that decides a bit is fp64 with explicit roundings (__dmul_rn / __dadd_rn) and FMA contraction off for this file (build.py),
 // so tests/submap_oracle.py restates it in numpy value for value.
 #include "common.h"
+#include "ragged2.h"
 
 namespace {
 
-constexpr int MAX_FRAME_POINTS = 1 << 20;
-constexpr int ST_OK = 0, ST_TOO_MANY = 1, ST_OFFSETS = 3, ST_EMPTY = 4;
 constexpr int WAVES = 4;          // waves of a workgroup in the per-profile kernels
 
 struct Layout {
@@ -31,21 +32,14 @@ struct Layout {
     size_t total;
 };
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 Layout layout(int B, int S_cap) {
     Layout L;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t r = o; o = align256(o + bytes); return r; };
+    Take take;
     L.prof_sub = take(4 * (size_t)S_cap); L.cnt = take(4 * (size_t)S_cap); L.prof_off = take(4 * (size_t)S_cap);
     L.sub_total = take(4 * (size_t)B); L.sub_stat = take(4 * (size_t)B);
-    L.total = o;
+    L.total = take.o;
     return L;
 }
-
-template <class T> T* at(void* ws, size_t off) { return (T*)((char*)ws + off); }
-
-__device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
 
 // Barrier between the LDS accesses of the lanes of ONE wave (the waves of a workgroup work on different profiles and never meet): a wave's
 // LDS instructions execute in order; the fences keep the compiler from moving accesses across the point.
@@ -71,19 +65,9 @@ __global__ __launch_bounds__(64) void keep_kernel(const int* __restrict__ scan_o
     __shared__ double sp[64][13];          // R | t of 64 profiles, row-major 3 x 4; 13: odd stride in doubles
     __shared__ int spres[64];
     const int b = blockIdx.x, lane = threadIdx.x;
-    bool bad = false;
-    for (int j = lane; j <= b; j += 64) {
-        const int o0 = sub_off[j], o1 = sub_off[j + 1];
-        bad |= o0 < 0 || o1 < o0 || o1 > S_cap || (j == 0 && o0 != 0);
-    }
-    bad = __any(bad);
-    const int s0 = bad ? 0 : sub_off[b], s1 = bad ? 0 : sub_off[b + 1];
-    for (int s = s0 + lane; s < s1; s += 64) {
-        const int r0 = scan_off[s], r1 = scan_off[s + 1];
-        bad |= r0 < 0 || r1 < r0 || r1 > P_cap;
-    }
-    bad = __any(bad);
-    if (bad) {
+    const Units u = check_offsets2(scan_off, sub_off, b, lane, S_cap, P_cap);
+    const int s0 = u.s0, s1 = u.s1;
+    if (u.bad) {
         if (lane == 0) { sub_stat[b] = ST_OFFSETS; skip_count[b] = 0; }
         return;
     }
@@ -151,46 +135,13 @@ __global__ __launch_bounds__(WAVES * 64) void count_kernel(const double* __restr
     if (lane == 0) cnt[s] = n;
 }
 
-// One wave per sub-map: prof_off[s] = surviving rows of the sub-map's profiles before s; sub_total[b] (a 64-bit running sum, clamped).
+// One wave per sub-map: prof_off[s] = surviving rows of the sub-map's profiles before s; sub_total[b] (wave_prefix: 64-bit lanes, clamped).
 __global__ __launch_bounds__(64) void prefix_kernel(const int* __restrict__ sub_off, const int* __restrict__ sub_stat, const int* __restrict__ cnt,
                                                     int* __restrict__ prof_off, int* __restrict__ sub_total) {
     const int b = blockIdx.x, lane = threadIdx.x;
     if (sub_stat[b] != ST_OK) { if (lane == 0) sub_total[b] = 0; return; }
-    const int s0 = sub_off[b], s1 = sub_off[b + 1];
-    long long run = 0;
-    for (int c0 = s0; c0 < s1; c0 += 64) {
-        const int s = c0 + lane;
-        const int c = s < s1 ? cnt[s] : 0;
-        int v = c;
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(v, o);
-            if (lane >= o) v += t;
-        }
-        if (s < s1) prof_off[s] = (int)min(run + (long long)(v - c), (long long)0x7fffffff);
-        run += (long long)__shfl(v, 63);
-        run = min(run, (long long)0x7fffffff);          // a chunk adds at most 64 * (2^31 - 1): no overflow of the 64-bit sum
-    }
-    if (lane == 0) sub_total[b] = (int)run;
-}
-
-// One wave: out_offsets over the sub-maps, the final status.  A sub-map above max_frame_points rows, or whose rows would pass cap, has none.
-__global__ __launch_bounds__(64) void offsets_kernel(int B, int cap, int max_frame_points, const int* __restrict__ sub_total,
-                                                     int* __restrict__ sub_stat, int* __restrict__ out_off, int* __restrict__ status) {
-    if (threadIdx.x != 0) return;
-    long long run = 0;
-    out_off[0] = 0;
-    for (int b = 0; b < B; ++b) {
-        int st = sub_stat[b];
-        const int n = sub_total[b];
-        if (st == ST_OK) {
-            if (n > max_frame_points || run + n > (long long)cap) st = ST_TOO_MANY;
-            else if (n == 0) st = ST_EMPTY;
-        }
-        if (st == ST_OK) run += n;
-        sub_stat[b] = st;
-        if (status) status[b] = st;
-        out_off[b + 1] = (int)run;
-    }
+    const int total = wave_prefix(cnt, sub_off[b], sub_off[b + 1], lane, prof_off);
+    if (lane == 0) sub_total[b] = total;
 }
 
 // Stage C: one wave per kept profile of a sub-map with status 0.

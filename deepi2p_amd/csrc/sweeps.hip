@@ -10,22 +10,24 @@
 //
 // A batch is ragged on two levels: frame -> sweeps (frame_offsets, key sweep first), sweep -> rows (sweep_offsets).  A sweep has about 35 k
 // rows, so the unit of work is not the sweep but one of its PARTS equal parts (a multiple of TILE rows each): a frame's rows are spread over
-// 32 x (its sweeps) workgroups.  Stages of the accumulation, the count / prefix / write split of submap.hip:
-//   check_kernel    one wave per frame: offset checks, sweep -> frame map
+// 32 x (its sweeps) workgroups.  Stages of the accumulation, the count / prefix / write split of submap.hip; what the two files share of it
+// is in ragged2.h: the offset acceptance (check_offsets2), the chunked 64-bit wave prefix (wave_prefix), offsets_kernel, the status codes
+// and the workspace helpers.
+//   check_kernel    one wave per frame: offset checks (ragged2.h), sweep -> frame map
 //   count_kernel    one workgroup per part: rows outside the ego box (ballot + popcount)
-//   prefix_kernel   one wave per frame: exclusive prefix of the counts over the frame's parts, the kept rows per sweep, the frame's total
-//   offsets_kernel  one wave: exclusive prefix over the frames, status
+//   prefix_kernel   one wave per frame: exclusive prefix of the counts over the frame's parts (ragged2.h's wave_prefix), the kept rows per
+//                   sweep, the frame's total
+//   offsets_kernel  (ragged2.h) one wave: exclusive prefix over the frames, status
 //   write_kernel    one workgroup per part: one 16-byte load and one 16-byte store per row, ordered compaction with the ballot prefix
 // Every value that decides a bit is fp64 with explicit roundings (__dmul_rn / __dadd_rn) and FMA contraction off for this file (build.py), so
 // tests/sweeps_oracle.py restates it in numpy value for value.  The box test is float32, as numpy compares a float32 column with a Python
 // constant.
 #include "common.h"
+#include "ragged2.h"
 
 namespace {
 
-constexpr int MAX_FRAME_POINTS = 1 << 20;
 constexpr int MAX_SWEEPS = 1 << 24;          // PARTS * S_cap stays an int
-constexpr int ST_OK = 0, ST_TOO_MANY = 1, ST_OFFSETS = 3, ST_EMPTY = 4;
 constexpr int PARTS = 32;                    // workgroups a sweep is cut into
 constexpr int TILE = 256;                    // rows a workgroup takes per iteration: one per thread
 
@@ -36,22 +38,15 @@ struct Layout {
     size_t total;
 };
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 Layout layout(int B, int S_cap) {
     Layout L;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t r = o; o = align256(o + bytes); return r; };
+    Take take;
     L.sweep_frame = take(4 * (size_t)S_cap);
     L.part_cnt = take(4 * (size_t)S_cap * PARTS); L.part_off = take(4 * (size_t)S_cap * PARTS);
     L.frame_total = take(4 * (size_t)B); L.frame_stat = take(4 * (size_t)B);
-    L.total = o;
+    L.total = take.o;
     return L;
 }
-
-template <class T> T* at(void* ws, size_t off) { return (T*)((char*)ws + off); }
-
-__device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
 
 // ---------------------------------------------------------------------------------------------------------------- poses
 // One thread per record (w, x, y, z, tx, ty, tz): q / |q|, the closed form of the rotation matrix in fp64, every entry and the translation
@@ -163,21 +158,10 @@ __global__ __launch_bounds__(256) void init_kernel(int S_cap, int* __restrict__ 
 __global__ __launch_bounds__(64) void check_kernel(const int* __restrict__ sweep_off, const int* __restrict__ frame_off, int S_cap, int P_cap,
                                                    int* __restrict__ sweep_frame, int* __restrict__ frame_stat) {
     const int b = blockIdx.x, lane = threadIdx.x;
-    bool bad = false;
-    for (int j = lane; j <= b; j += 64) {
-        const int o0 = frame_off[j], o1 = frame_off[j + 1];
-        bad |= o0 < 0 || o1 < o0 || o1 > S_cap || (j == 0 && o0 != 0);
-    }
-    bad = __any(bad);
-    const int s0 = bad ? 0 : frame_off[b], s1 = bad ? 0 : frame_off[b + 1];
-    for (int s = s0 + lane; s < s1; s += 64) {
-        const int r0 = sweep_off[s], r1 = sweep_off[s + 1];
-        bad |= r0 < 0 || r1 < r0 || r1 > P_cap;
-    }
-    bad = __any(bad);
-    if (!bad)
-        for (int s = s0 + lane; s < s1; s += 64) sweep_frame[s] = b;
-    if (lane == 0) frame_stat[b] = bad ? ST_OFFSETS : ST_OK;
+    const Units u = check_offsets2(sweep_off, frame_off, b, lane, S_cap, P_cap);
+    if (!u.bad)
+        for (int s = u.s0 + lane; s < u.s1; s += 64) sweep_frame[s] = b;
+    if (lane == 0) frame_stat[b] = u.bad ? ST_OFFSETS : ST_OK;
 }
 
 // rows of one part of a sweep of n rows: a multiple of TILE, PARTS of them cover the sweep
@@ -223,45 +207,13 @@ __global__ __launch_bounds__(64) void prefix_kernel(const int* __restrict__ fram
     const int b = blockIdx.x, lane = threadIdx.x;
     if (frame_stat[b] != ST_OK) { if (lane == 0) frame_total[b] = 0; return; }
     const int s0 = frame_off[b], s1 = frame_off[b + 1];
-    const long long j0 = (long long)s0 * PARTS, j1 = (long long)s1 * PARTS;
-    long long run = 0;
-    for (long long c0 = j0; c0 < j1; c0 += 64) {
-        const long long j = c0 + lane;
-        const long long c = j < j1 ? part_cnt[j] : 0;
-        long long v = c;          // 64 bits: sweeps of one frame may overlap in rows, so 64 parts can hold more than 2^31 - 1 kept rows together
-        for (int o = 1; o < 64; o <<= 1) {
-            const long long t = __shfl_up(v, o);
-            if (lane >= o) v += t;
-        }
-        if (j < j1) part_off[j] = (int)min(run + (v - c), (long long)0x7fffffff);
-        run = min(run + __shfl(v, 63), (long long)0x7fffffff);          // a chunk adds at most 64 * (2^31 - 1): no overflow of the 64-bit sum
-    }
+    const int total = wave_prefix(part_cnt, (long long)s0 * PARTS, (long long)s1 * PARTS, lane, part_off);
     for (int s = s0 + lane; s < s1; s += 64) {
         long long t = 0;
         for (int p = 0; p < PARTS; ++p) t += part_cnt[(long long)s * PARTS + p];          // the parts of a sweep are disjoint: at most 2^31 - 1
         kept[s] = (int)t;
     }
-    if (lane == 0) frame_total[b] = (int)run;
-}
-
-// One wave: out_offsets over the frames, the final status.  A frame above max_frame_points rows, or whose rows would pass cap, has none.
-__global__ __launch_bounds__(64) void offsets_kernel(int B, int cap, int max_frame_points, const int* __restrict__ frame_total, int* __restrict__ frame_stat,
-                                                     int* __restrict__ out_off, int* __restrict__ status) {
-    if (threadIdx.x != 0) return;
-    long long run = 0;
-    out_off[0] = 0;
-    for (int b = 0; b < B; ++b) {
-        int st = frame_stat[b];
-        const int n = frame_total[b];
-        if (st == ST_OK) {
-            if (n > max_frame_points || run + n > (long long)cap) st = ST_TOO_MANY;
-            else if (n == 0) st = ST_EMPTY;
-        }
-        if (st == ST_OK) run += n;
-        frame_stat[b] = st;
-        if (status) status[b] = st;
-        out_off[b + 1] = (int)run;
-    }
+    if (lane == 0) frame_total[b] = total;
 }
 
 // One workgroup per part of a sweep of a frame with status 0.  Thread t of iteration i holds row a + 256 i + t: the loads and, after the

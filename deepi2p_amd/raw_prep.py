@@ -91,12 +91,7 @@ def prepare_raw(scans, images, K_raw, Pc, opt, mode="val", seed=0, Pji=None, dev
     arrays; images u8[B,H0,W0,3]; K_raw [B,3,3]; Pc [B,4,4] -> RawFramePlan.run's tuple."""
     _check_dataset(dataset)
     scan_prep._normals_entry(normals_method)
-    if images is None:
-        raise ValueError("raw_prep: images is None")
-    images = torch.as_tensor(images)
-    if images.dim() != 4 or images.shape[0] != len(scans):
-        raise ValueError("raw_prep: images must be [B, H0, W0, 3] with one image per scan")
-    raw_hw = (images.shape[1], images.shape[2])
+    images, raw_hw = sample_prep._host_images(images, len(scans), "raw_prep", "scan")
     sample_prep.option_block(opt, raw_hw, mode)          # argument errors before anything touches the device
     dev = device or scan_prep._dev()
     points, offsets, host = scan_prep.pack(scans, dev)

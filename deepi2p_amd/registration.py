@@ -20,7 +20,7 @@ from . import ops
 __version__ = "deepi2p_amd-1"
 
 
-def _dev():
+def _hip_dev():
     if not torch.cuda.is_available():
         raise RuntimeError("deepi2p_amd.registration needs a HIP device (there is no CPU fallback)")
     return torch.device("cuda", torch.cuda.current_device())
@@ -30,7 +30,7 @@ def solvePGivenK_batched(points, labels, K, init_y_angles, init_Ts, H, W, t_xyz_
                          max_iter, is_2d, return_all=False):
     """R hypotheses of ONE frame in one launch.  numpy in / numpy out.
     -> (P[R,4,4], cost[R], best) ; with return_all also (params[R,np], iters[R])."""
-    dev = _dev()
+    dev = _hip_dev()
     pts = torch.as_tensor(np.ascontiguousarray(points, dtype=np.float64), device=dev).unsqueeze(0)
     lab = torch.as_tensor(np.ascontiguousarray(labels).astype(np.int32), device=dev).unsqueeze(0)
     Kt = torch.as_tensor(np.ascontiguousarray(K, dtype=np.float64), device=dev).reshape(1, 3, 3)
@@ -52,7 +52,7 @@ def solvePGivenK_batched(points, labels, K, init_y_angles, init_Ts, H, W, t_xyz_
 def solvePGivenK(points, labels, K, init_y_angle, init_T, H, W, t_xyz_lower_bound, t_xyz_upper_bound, max_iter,
                  is_debug, is_2d):
     """Drop-in for FrustumRegistration.solvePGivenK: -> (P 4x4, final_cost, residuals[3*N_in+N_out])."""
-    dev = _dev()
+    dev = _hip_dev()
     pts = torch.as_tensor(np.ascontiguousarray(points, dtype=np.float64), device=dev).unsqueeze(0)
     lab = torch.as_tensor(np.ascontiguousarray(labels).astype(np.int32), device=dev).unsqueeze(0)
     Kt = torch.as_tensor(np.ascontiguousarray(K, dtype=np.float64), device=dev).reshape(1, 3, 3)
@@ -86,7 +86,7 @@ def wrap_in_pi(x):
 
 def get_initial_guess(pc_np, coarse_predictions_np):
     """-> (P_init, init_y_angle, pc_front, labels_front); the reduction runs on the device."""
-    dev = _dev()
+    dev = _hip_dev()
     pts = torch.as_tensor(np.ascontiguousarray(pc_np, dtype=np.float64), device=dev).unsqueeze(0)
     lab = torch.as_tensor(np.ascontiguousarray(coarse_predictions_np).astype(np.int32), device=dev).unsqueeze(0)
     yaw0, lab_out, has = ops.initial_guess(pts, lab)
@@ -147,7 +147,7 @@ def solve_P_random_perturb(pc_np, coarse_predictions_np, K_np, H, W, init_t_ampl
         return None, 1e20, None
     P, cost, best, params, _ = solvePGivenK_batched(pc_np, coarse_predictions_np, K_np, ys, Ts, H, W, t_lowerbound,
                                                     t_upperbound, max_iter, is_2d, return_all=True)
-    dev = _dev()
+    dev = _hip_dev()
     pts = torch.as_tensor(np.ascontiguousarray(pc_np, dtype=np.float64), device=dev).unsqueeze(0)
     lab = torch.as_tensor(np.ascontiguousarray(coarse_predictions_np).astype(np.int32), device=dev).unsqueeze(0)
     Kt = torch.as_tensor(np.ascontiguousarray(K_np, dtype=np.float64), device=dev).reshape(1, 3, 3)

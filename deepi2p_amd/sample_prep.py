@@ -28,6 +28,7 @@ import torch
 
 from . import _lib, scan_prep
 from ._lib import call, ptr, require_cuda, stream
+from ._ragged import _dev
 
 MODES = {"train": 0, "val": 1, "val_random_Ry": 2}
 # the loader fields of kitti/options.py; an option bag without them gets these
@@ -69,10 +70,6 @@ def _resize_k(scale):
                          "implemented; any other scale, even k included, has fractional bilinear weights and would have to reproduce OpenCV's "
                          "fixed-point coefficients and intermediate rounding, which cannot be checked here" % (scale,))
     return k
-
-
-def _dev():
-    return torch.device("cuda", torch.cuda.current_device())
 
 
 def option_block(opt, raw_hw, mode, color_ranges=COLOR_RANGES, dataset="kitti"):
@@ -143,6 +140,16 @@ def _check_images(images, B, raw_hw):
         raise ValueError("sample_prep: images is None")
     if not torch.is_tensor(images) or images.dtype != torch.uint8 or tuple(images.shape) != (B, raw_hw[0], raw_hw[1], 3):
         raise ValueError("sample_prep: images must be a uint8 tensor [%d, %d, %d, 3] (HWC)" % (B, raw_hw[0], raw_hw[1]))
+
+
+def _host_images(images, n, prefix, unit):
+    """the images of a convenience call (prepare_raw and its Oxford / nuScenes kin): [B, H0, W0, 3], one per `unit` of the n -> (tensor, raw_hw)"""
+    if images is None:
+        raise ValueError("%s: images is None" % prefix)
+    images = torch.as_tensor(images)
+    if images.dim() != 4 or images.shape[0] != n:
+        raise ValueError("%s: images must be [B, H0, W0, 3] with one image per %s" % (prefix, unit))
+    return images, (images.shape[1], images.shape[2])
 
 
 def _f64(a, shape, dev):
@@ -226,6 +233,12 @@ class ImagePlan:
         return self.ws[:self.B].cpu().numpy().astype(np.int64) & 0xFFFFFFFF
 
 
+# SamplePlan.run's nine tensors in order, then the two a raw plan's run (raw_prep.RawFramePlan, sweeps.NuScenesRawPlan) appends; the positions
+# the executors of raw_pipeline read by name
+PREPARED = ("pc", "intensity", "sn", "node_a", "node_b", "P", "img", "K", "t_ji", "status", "T_scan")
+I_P, I_K, I_STATUS, I_T_SCAN = (PREPARED.index(k) for k in ("P", "K", "status", "T_scan"))
+
+
 class SamplePlan:
     """scan_prep.BatchPlan + draws + image path, preallocated.  run() launches everything on the current stream with no host
     synchronisation and no allocation (torch.cuda.graph-safe); plan.status (i32[B]) stays on the device (scan_prep.check_status).
@@ -276,7 +289,7 @@ class SamplePlan:
             torch.maximum(self.points.status, fstat, out=self.status)
         img = self.image.run(images_u8, self.table)
         B = self.B
-        return pc, intensity, self.sn, node_a, node_b, self.table.P[:B], img, self.table.K[:B], self.table.t_ij[:B]
+        return pc, intensity, self.sn, node_a, node_b, self.table.P[:B], img, self.table.K[:B], self.table.t_ij[:B]          # PREPARED[:9]
 
     def run(self, points, normals, offsets, images_u8, K_raw, Pc, Pji=None, seed=None):
         """points f32[>=total,4], normals f32[>=total,3], offsets i32[B+1], images u8[B,H0,W0,3], K_raw f64[B,3,3], Pc f64[B,4,4] (camera
@@ -296,7 +309,7 @@ class SamplePlan:
         if Pji is not None:
             self.t_ji.copy_(Pji[:, :3, 3])
         B = self.B
-        return pc, intensity, sn, node_a, node_b, self.table.P[:B], img, self.table.K[:B], self.t_ji[:B]
+        return pc, intensity, sn, node_a, node_b, self.table.P[:B], img, self.table.K[:B], self.t_ji[:B]          # PREPARED[:9]
 
 
 def prepare_images(images_u8, K_raw, opt, mode="val", seed=0, dataset="kitti"):

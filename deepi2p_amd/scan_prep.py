@@ -11,18 +11,14 @@ here synchronise only to trim ragged outputs and to check the per-frame status; 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _ragged
 from ._lib import DeepI2PHipError, call, ptr, require_cuda, stream
+from ._ragged import MAX_FRAME_POINTS, _dev
 
-MAX_FRAME_POINTS = 1 << 20
 MAX_EXTENT = 2048.0          # default bound (m) on the bounding-box edge of a frame: frames above it are rejected (status 2)
 NORMALS_METHODS = {"query": "di2p_estimate_normals", "cells": "di2p_estimate_normals_cells"}
 NORMALS_CELL_CANDIDATES = 960          # di2p_normals_cells_candidates(): the LDS candidate capacity of a cell of the "cells" kernel
 _STATUS = {1: "more than max_frame_points points", 2: "bounding box above max_extent / voxel index span above 2^21", 3: "bad frame offsets"}
-
-
-def _dev():
-    return torch.device("cuda", torch.cuda.current_device())
 
 
 def pack(frames, device=None, cols=4):
@@ -37,15 +33,12 @@ def pack(frames, device=None, cols=4):
 
 
 def workspace(B, cap, device=None):
-    return torch.empty((max(256, _lib.load().di2p_scan_prep_workspace_bytes(B, cap)),), dtype=torch.uint8, device=device or _dev())
+    return _ragged.workspace("di2p_scan_prep_workspace_bytes", B, cap, device)
 
 
 def check_status(status):
     """Raise DeepI2PHipError for a rejected frame (synchronises)."""
-    st = status.cpu().numpy()
-    bad = np.nonzero(st)[0]
-    if len(bad):
-        raise DeepI2PHipError("scan_prep: frame %d rejected: %s" % (int(bad[0]), _STATUS.get(int(st[bad[0]]), "status %d" % int(st[bad[0]]))))
+    _ragged.check_status("scan_prep", "frame", _STATUS, status)
 
 
 class VoxelState:

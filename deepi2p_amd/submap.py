@@ -22,8 +22,9 @@ status per sub-map: 0 ok, 1 more than max_frame_points surviving rows (or more t
 import numpy as np
 import torch
 
-from . import _lib, sample_prep, scan_prep
+from . import _lib, _ragged, sample_prep, scan_prep
 from ._lib import DeepI2PHipError, call, ptr, require_cuda, stream
+from ._ragged import _dev
 
 MAX_FRAME_POINTS = scan_prep.MAX_FRAME_POINTS
 VOXEL = 0.1          # voxel_grid_downsample_size of build_dataset.py
@@ -31,16 +32,9 @@ _STATUS = dict(scan_prep._STATUS)
 _STATUS.update({1: "more than max_frame_points surviving rows", 4: "no profile or no surviving row"})
 
 
-def _dev():
-    return torch.device("cuda", torch.cuda.current_device())
-
-
 def check_status(status):
     """Raise DeepI2PHipError for a rejected sub-map (synchronises)."""
-    st = status.cpu().numpy()
-    bad = np.nonzero(st)[0]
-    if len(bad):
-        raise DeepI2PHipError("submap: sub-map %d rejected: %s" % (int(bad[0]), _STATUS.get(int(st[bad[0]]), "status %d" % int(st[bad[0]]))))
+    _ragged.check_status("submap", "sub-map", _STATUS, status)
 
 
 def _threshold(value, name):
@@ -63,26 +57,6 @@ def _ground_args(ground_threshold):
     """the reference removes ground only when the threshold is not None and > -1"""
     v = _threshold(ground_threshold, "ground_threshold")
     return (0.0, 0) if v is None or not v > -1 else (v, 1)
-
-
-def _check_max_frame_points(max_frame_points):
-    if int(max_frame_points) < 0 or int(max_frame_points) > MAX_FRAME_POINTS:
-        raise ValueError("submap: max_frame_points must be in [0, 2^20] (the voxel stage's limit)")
-    return int(max_frame_points)
-
-
-def _offsets(x, name, length, dev):
-    """device tensor: shape and dtype only (its values are checked on the device: status 3); host values: also non-decreasing from 0"""
-    if torch.is_tensor(x) and x.is_cuda:
-        if x.dtype != torch.int32 or tuple(x.shape) != (length,) or not x.is_contiguous():
-            raise ValueError("submap: %s must be a contiguous int32 tensor [%d]" % (name, length))
-        return x
-    a = np.asarray(x.numpy() if torch.is_tensor(x) else x)
-    if a.ndim != 1 or a.shape[0] != length or a.dtype.kind not in "iu":
-        raise ValueError("submap: %s must be an integer array [%d]" % (name, length))
-    if a[0] != 0 or np.any(np.diff(a.astype(np.int64)) < 0) or a[-1] >= 2 ** 31:
-        raise ValueError("submap: %s must start at 0 and be non-decreasing (int32)" % name)
-    return torch.as_tensor(a.astype(np.int32)).to(dev or _dev())
 
 
 def _check_batch(scan_xyr, poses, present, B, S_cap=None, P_cap=None):
@@ -153,7 +127,7 @@ def pack_scans(submaps, device=None):
 
 
 def workspace(B, S_cap, device=None):
-    return torch.empty((max(256, _lib.load().di2p_submap_workspace_bytes(B, S_cap)),), dtype=torch.uint8, device=device or _dev())
+    return _ragged.workspace("di2p_submap_workspace_bytes", B, S_cap, device)
 
 
 def voxel_centroids(state):
@@ -177,13 +151,13 @@ def build_raw(scan_xyr, scan_offsets, submap_offsets, poses, present, G_posesour
     """Stages A-C, eager: -> (points f32[cap,4] rows (x, y, z, reflectance) in the frame of each sub-map's origin, offsets i32[B+1],
     kept i32[S] (1 kept, 0 skipped, -1 missing), skip_count i32[B], status i32[B]).  Offsets may be host arrays (checked here) or device
     tensors (checked on the device: status 3).  No synchronisation."""
-    mfp = _check_max_frame_points(max_frame_points)
+    mfp = _ragged._check_max_frame_points("submap", max_frame_points)
     skip, ground = _skip_arg(skip_threshold), _ground_args(ground_threshold)
     B = len(submap_offsets) - 1
     S, P = _check_batch(scan_xyr, poses, present, B)
     dev = scan_xyr.device
-    sub_off = _offsets(submap_offsets, "submap_offsets", B + 1, dev)
-    scan_off = _offsets(scan_offsets, "scan_offsets", S + 1, dev)
+    sub_off = _ragged._offsets("submap", submap_offsets, "submap_offsets", B + 1, dev)
+    scan_off = _ragged._offsets("submap", scan_offsets, "scan_offsets", S + 1, dev)
     G = _g44(G_posesource_laser, "G_posesource_laser", dev)
     require_cuda(scan_xyr, scan_off, sub_off, poses, present, G)
     cap = P if cap is None else int(cap)
@@ -230,7 +204,7 @@ class SubmapPlan:
     unaffected).  ws: a scan_prep workspace of (B, cap_raw) to share."""
 
     def __init__(self, B, S_cap, P_cap, cap_raw, max_frame_points, voxel=VOXEL, skip_threshold=None, ground_threshold=None, device=None, ws=None):
-        self.max_src = _check_max_frame_points(max_frame_points)
+        self.max_src = _ragged._check_max_frame_points("submap", max_frame_points)
         self.skip, self.ground = _skip_arg(skip_threshold), _ground_args(ground_threshold)
         if not 0.0 < float(voxel) < 1e30:
             raise ValueError("submap: voxel must be positive and finite")
@@ -260,12 +234,9 @@ class SubmapPlan:
         plan's buffers."""
         B = self.B
         _check_batch(scan_xyr, poses, present, B, self.S_cap, self.P_cap)
-        for t, name, n in ((scan_offsets, "scan_offsets", self.S_cap + 1), (submap_offsets, "submap_offsets", B + 1)):
-            if not torch.is_tensor(t) or t.dtype != torch.int32 or tuple(t.shape) != (n,) or not t.is_contiguous():
-                raise ValueError("submap: %s must be a contiguous int32 device tensor [%d]" % (name, n))
-        for t, name, shape in ((G_posesource_laser, "G_posesource_laser", (4, 4)), (G_cam, "G_cam", (max(B, 1), 4, 4))):
-            if not torch.is_tensor(t) or t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous():
-                raise ValueError("submap: %s must be a contiguous float64 device tensor %s" % (name, list(shape)))
+        for t, name, dtype, shape in ((scan_offsets, "scan_offsets", torch.int32, (self.S_cap + 1,)), (submap_offsets, "submap_offsets", torch.int32, (B + 1,)),
+                                      (G_posesource_laser, "G_posesource_laser", torch.float64, (4, 4)), (G_cam, "G_cam", torch.float64, (max(B, 1), 4, 4))):
+            _ragged._check_tensor("submap", t, name, dtype, shape)
         require_cuda(scan_xyr, scan_offsets, submap_offsets, poses, present, G_posesource_laser, G_cam)
         s = stream()
         _launch_build(scan_xyr, scan_offsets, submap_offsets, poses, present, G_posesource_laser, B, self.S_cap, self.P_cap, self.cap, self.max_src,
@@ -284,7 +255,7 @@ class OxfordRawPlan:
 
     def __init__(self, opt, B, S_cap, P_cap, cap_raw, max_frame_points, raw_hw=None, mode="val", voxel=VOXEL, skip_threshold=None,
                  ground_threshold=None, device=None, jitter=sample_prep.JITTER, color=None):
-        _check_max_frame_points(max_frame_points)
+        _ragged._check_max_frame_points("submap", max_frame_points)
         _skip_arg(skip_threshold)
         sample_prep.option_block(opt, sample_prep.RAW_HW["oxford"] if raw_hw is None else raw_hw, mode, dataset="oxford")          # argument errors first
         dev = device or _dev()
@@ -313,12 +284,7 @@ def prepare_oxford_raw(submaps, G_posesource_laser, G_cam, images, K_raw, P_cam_
                        ground_threshold=None, voxel=VOXEL, device=None):
     """Convenience: packs the sub-maps (pack_scans' host form), builds a plan, runs it and checks the status (synchronises).
     images u8[B,H0,W0,3]; K_raw [B,3,3]; P_cam_pc [B,4,4] -> OxfordRawPlan.run's tuple."""
-    if images is None:
-        raise ValueError("submap: images is None")
-    images = torch.as_tensor(images)
-    if images.dim() != 4 or images.shape[0] != len(submaps):
-        raise ValueError("submap: images must be [B, H0, W0, 3] with one image per sub-map")
-    raw_hw = (images.shape[1], images.shape[2])
+    images, raw_hw = sample_prep._host_images(images, len(submaps), "submap", "sub-map")
     sample_prep.option_block(opt, raw_hw, mode, dataset="oxford")          # argument errors before anything touches the device
     _skip_arg(skip_threshold)
     _ground_args(ground_threshold)

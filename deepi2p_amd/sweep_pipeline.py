@@ -1,18 +1,17 @@
-"""Raw-sweep executor: "here are a nuScenes sample's LiDAR sweeps, its records and a camera frame, give me the pose" on the machinery of
-pipeline.RegistrationExecutor.
+"""Raw-sweep executor: "here are a nuScenes sample's LiDAR sweeps, its records and a camera frame, give me the pose" on
+raw_pipeline.PreparedFrameExecutor.
 
 One STEP = H2D copy of the raw batch -> sweeps.NuScenesRawPlan (pose matrices, sweep transforms and P_cam_pc, ego-box filter and
 accumulation, the loader's sample preparation, image path) -> classifier -> pose solve (Gauss-Newton restarts or PnP-RANSAC) ->
-P_scan = P . T_scan.  Streams, slots, pinned staging, copy streams, one captured graph per slot, weight following and submit / result tickets
-are the base class's; this class only describes other staged inputs and puts the preparation in front of the step, as
-raw_pipeline.RawFrameExecutor does for KITTI scans.  nuScenes clouds are z-up: build the pipeline with frame="enu".
+P_scan = P . T_scan.  The staging, the step and the evaluation mode are the base class's, shared with raw_pipeline.RawFrameExecutor; this
+module has the host check of a sweep batch (host_sweep_frames) and the subclass that names the staged inputs, the plan and P_cam_pc.
+nuScenes clouds are z-up: build the pipeline with frame="enu".
 """
 import numpy as np
 import torch
 
-from . import sweeps
-from ._lib import call, ptr, stream
-from .pipeline import INPUT_NAMES, K_NAME, RegistrationExecutor
+from . import _ragged, sample_prep, sweeps
+from .raw_pipeline import PreparedFrameExecutor
 
 RECORDS = ("lidar_calib", "cam_pose", "cam_calib")
 
@@ -77,7 +76,7 @@ def host_sweep_frames(host_batch, B, S_cap, cap_raw, raw_hw, cols=None):
             image, K_raw, 0 if seed is None else int(seed), cols)
 
 
-class SweepFrameExecutor(RegistrationExecutor):
+class SweepFrameExecutor(PreparedFrameExecutor):
     """executor = SweepFrameExecutor(mm, pipe, opt, example_batch, S_cap, cap_raw, max_frame_points, n_streams=4)
     ticket = executor.submit(host_batch)          # dict: sweeps, ego, lidar_calib, cam_pose, cam_calib, image, K_raw[, offsets, seed]
     out = executor.result(ticket)                 # the base executor's outputs + status i32[B], T_scan, P_cam_pc, P_scan f64[B,4,4]
@@ -93,48 +92,35 @@ class SweepFrameExecutor(RegistrationExecutor):
     points (the sample's f32 [B,3,4]) against the solver's out["P"] -- and status == 0 as the frame mask.  visualize: passed through; the
     overlays are drawn over the PREPARED image from the prepared points, with the prepared K."""
 
+    BATCH, ROWS = "raw sweep batch", "rows"
+    cols = None          # while the example batch itself is checked: whatever it has
+
     def __init__(self, mm, pipe, opt, example_batch, S_cap, cap_raw, max_frame_points, n_streams=4, use_graph=True, restarts=None, samples=None,
                  labels_override=None, mode="val", box=sweeps.BOX, h2d_mode="copy_stream", post_fn=None, evaluate=False, visualize=None):
-        if h2d_mode not in ("copy_stream", "eager"):
-            raise ValueError("SweepFrameExecutor: h2d_mode must be 'copy_stream' or 'eager' (a captured copy has a fixed size; the raw copy has not)")
-        sweeps._check_max_frame_points(max_frame_points)
+        self._check_h2d_mode(h2d_mode)
+        _ragged._check_max_frame_points("sweeps", max_frame_points)
         sweeps._box(box)
-        if "image" not in example_batch or torch.as_tensor(example_batch["image"]).dim() != 4:
-            raise ValueError("raw sweep batch: image must be uint8 [B, H, W, 3]")
-        image = torch.as_tensor(example_batch["image"])
+        self._read_example(example_batch.get("image"))
         self.opt, self.mode, self.box = opt, mode, box
-        self.B, self.raw_hw = int(image.shape[0]), (int(image.shape[1]), int(image.shape[2]))
         self.S_cap, self.cap_raw, self.max_frame_points = int(S_cap), int(cap_raw), int(max_frame_points)
-        from . import sample_prep
         sample_prep.option_block(opt, self.raw_hw, mode, dataset="nuscenes")
-        self.cols = host_sweep_frames(example_batch, self.B, self.S_cap, self.cap_raw, self.raw_hw)[-1]          # 4 or 5: the example's
-        super().__init__(mm, pipe, torch.eye(3, dtype=torch.float64), example_batch, n_streams=n_streams, use_graph=use_graph, restarts=restarts,
-                         labels_override=labels_override, post_fn=post_fn, h2d_mode=h2d_mode, samples=samples, evaluate=evaluate, visualize=visualize)
+        self.cols = self._check_batch(example_batch)[-1]          # 4 or 5: the example's
+        super().__init__(mm, pipe, example_batch, n_streams=n_streams, use_graph=use_graph, restarts=restarts, labels_override=labels_override,
+                         post_fn=post_fn, h2d_mode=h2d_mode, samples=samples, evaluate=evaluate, visualize=visualize)
 
-    # ---------------------------------------------------------------------------------------------------------- staged inputs
-    def _batch_size(self, example_batch):
-        return self.B
+    def _check_batch(self, host_batch):
+        return host_sweep_frames(host_batch, self.B, self.S_cap, self.cap_raw, self.raw_hw, self.cols)
 
     def _staged_inputs(self, example_batch, B):
         H, W = self.raw_hw
         S = max(self.S_cap, 1)
-        # rows LAST: a step copies the buffer only up to its last row in use
         return [("frame_offsets", (B + 1,), torch.int32), ("sweep_offsets", (S + 1,), torch.int32), ("seed", (1,), torch.int64),
                 ("K_raw", (B, 3, 3), torch.float64), ("lidar_calib", (B, 7), torch.float64), ("cam_pose", (B, 7), torch.float64),
                 ("cam_calib", (B, 7), torch.float64), ("ego", (S, 7), torch.float64), ("image", (B, H, W, 3), torch.uint8),
                 ("rows", (max(self.cap_raw, 1), self.cols), torch.float32)]
 
-    def _check(self, host_batch):
-        return host_sweep_frames(host_batch, self.B, self.S_cap, self.cap_raw, self.raw_hw, self.cols)
-
-    def _validate(self, slot, host_batch):
-        self._checked = (host_batch, self._check(host_batch))      # submit stages it next: converted once
-
-    def _stage(self, slot, host_batch):
-        checked, self._checked = getattr(self, "_checked", None), None
-        staged = checked[1] if checked is not None and checked[0] is host_batch else self._check(host_batch)
+    def _copy_staged(self, h, staged):
         parts, so, fo, ego, recs, image, K_raw, seed, _ = staged
-        h = slot.host
         S = int(fo[-1])
         h["frame_offsets"].copy_(fo)
         h["sweep_offsets"][:S + 1].copy_(so)
@@ -146,52 +132,18 @@ class SweepFrameExecutor(RegistrationExecutor):
         h["ego"][:S].copy_(ego)
         h["ego"][S:] = torch.tensor([1.0, 0, 0, 0, 0, 0, 0], dtype=torch.float64)
         h["image"].copy_(image)
-        row = 0
-        for p in parts:
-            h["rows"][row:row + p.shape[0]].copy_(p)
-            row += int(p.shape[0])
-        # rows past the last sweep offset stay stale: they are not copied and no kernel reads them
-        slot.copy_bytes = h["rows"].data_ptr() - slot.host_flat.data_ptr() + 4 * self.cols * row
+        return self._lay_rows(h["rows"], parts)
 
-    def _stage_example(self, slot, example_batch):
-        slot.host["rows"].zero_()
-        self._stage(slot, example_batch)
-
-    def _slot_ready(self, slot):
-        d = slot.devs[0]
-        plan = sweeps.NuScenesRawPlan(self.opt, self.B, max(self.S_cap, 1), max(self.cap_raw, 1), self.cap_raw, self.max_frame_points, self.raw_hw,
+    def _make_plan(self):
+        return sweeps.NuScenesRawPlan(self.opt, self.B, max(self.S_cap, 1), max(self.cap_raw, 1), self.cap_raw, self.max_frame_points, self.raw_hw,
                                       self.mode, self.cols, self.box, self.device)
-        plan.sample.seed = d["seed"]          # the draws read the staged seed where the copy puts it
-        slot.plan = plan
-        slot.K64 = torch.zeros((self.B, 3, 3), dtype=torch.float64, device=self.device)
-        slot.P_scan = torch.zeros((self.B, 4, 4), dtype=torch.float64, device=self.device)
-        if self.evaluate:
-            slot.P_gt64 = torch.zeros((self.B, 3, 4), dtype=torch.float64, device=self.device)
-            slot.mask = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
-        p = plan.sample
-        # what _net_part / _solve_part read: the plan's outputs, in place (the nuScenes records have no normals: sn is the plan's zero buffer)
-        d.update(zip(INPUT_NAMES, (p.points.pc, p.points.intensity, p.sn, p.points.nodes[0], p.points.nodes[1], p.image.img)))
-        d[K_NAME] = slot.K64
 
-    # ---------------------------------------------------------------------------------------------------------- one step
-    def _step(self, slot, with_h2d):
-        if with_h2d:
-            slot.copy_in()
-        d = slot.dev
-        prepared = slot.plan.run(d["rows"], d["sweep_offsets"], d["frame_offsets"], d["ego"], d["lidar_calib"], d["cam_pose"], d["cam_calib"],
-                                 d["image"], d["K_raw"], seed=None)
-        slot.K64.copy_(prepared[7])                                          # the prepared f32 K, as the base executor stages it: f64
-        slot.prepared = prepared
-        out = self._solve_part(slot, self._net_part(slot))
-        P = out["P"]
-        if P.dtype != torch.float64 or tuple(P.shape) != (self.B, 4, 4) or not P.is_contiguous():
-            raise ValueError("SweepFrameExecutor: the pose solve must return P as contiguous f64 [B,4,4]")
-        call("di2p_compose_poses", ptr(P), ptr(prepared[10]), self.B, ptr(slot.P_scan), stream())
-        out.update(status=prepared[9], T_scan=prepared[10], P_cam_pc=slot.plan.P_cam_pc, P_scan=slot.P_scan)
-        return out
+    def _run_plan(self, plan, d):
+        return plan.run(d["rows"], d["sweep_offsets"], d["frame_offsets"], d["ego"], d["lidar_calib"], d["cam_pose"], d["cam_calib"], d["image"],
+                        d["K_raw"], seed=None)
 
-    def _eval_truth(self, slot):
-        prepared = slot.prepared
-        slot.P_gt64.copy_(prepared[5])                                       # the sample's own pose of the prepared points, f32 -> f64
-        slot.mask.copy_(prepared[9] == 0)                                    # a rejected frame (status != 0) is skipped entirely
-        return slot.P_gt64, prepared[5], prepared[7], slot.mask
+    def _normals(self, plan):
+        return plan.sample.sn          # the nuScenes records have no normals: the plan's zero buffer
+
+    def _extra_outputs(self, slot):
+        return dict(P_cam_pc=slot.plan.P_cam_pc)

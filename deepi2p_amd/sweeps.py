@@ -23,8 +23,9 @@ box above its limit, 3 bad offsets, 4 no sweep or no surviving row.  A frame wit
 import numpy as np
 import torch
 
-from . import _lib, sample_prep, scan_prep
+from . import _lib, _ragged, sample_prep, scan_prep
 from ._lib import DeepI2PHipError, call, ptr, require_cuda, stream
+from ._ragged import _dev
 
 MAX_FRAME_POINTS = scan_prep.MAX_FRAME_POINTS
 BOX = (0.8, 2.7)          # half-extents (x, y) of the ego car's box, get_lidar_pc_intensity_by_token
@@ -32,16 +33,9 @@ _STATUS = dict(scan_prep._STATUS)
 _STATUS.update({1: "more than max_frame_points surviving rows", 4: "no sweep or no surviving row"})
 
 
-def _dev():
-    return torch.device("cuda", torch.cuda.current_device())
-
-
 def check_status(status):
     """Raise DeepI2PHipError for a rejected frame (synchronises)."""
-    st = status.cpu().numpy()
-    bad = np.nonzero(st)[0]
-    if len(bad):
-        raise DeepI2PHipError("sweeps: frame %d rejected: %s" % (int(bad[0]), _STATUS.get(int(st[bad[0]]), "status %d" % int(st[bad[0]]))))
+    _ragged.check_status("sweeps", "frame", _STATUS, status)
 
 
 def sweep_picks(available_next, available_prev, frame_num=3, frame_skip=4):
@@ -55,12 +49,6 @@ def sweep_picks(available_next, available_prev, frame_num=3, frame_skip=4):
         raise ValueError("sweeps: available_next and available_prev must be >= 0")
     walk = lambda n: [k * frame_skip for k in range(1, frame_num + 1) if k * frame_skip <= int(n)]
     return walk(available_next), walk(available_prev)
-
-
-def _check_max_frame_points(max_frame_points):
-    if int(max_frame_points) < 0 or int(max_frame_points) > MAX_FRAME_POINTS:
-        raise ValueError("sweeps: max_frame_points must be in [0, 2^20] (the voxel stage's limit)")
-    return int(max_frame_points)
 
 
 def _check_cols(cols):
@@ -79,20 +67,6 @@ def _box(box):
     return bx, by
 
 
-def _offsets(x, name, length, dev):
-    """device tensor: shape and dtype only (its values are checked on the device: status 3); host values: also non-decreasing from 0"""
-    if torch.is_tensor(x) and x.is_cuda:
-        if x.dtype != torch.int32 or tuple(x.shape) != (length,) or not x.is_contiguous():
-            raise ValueError("sweeps: %s must be a contiguous int32 tensor [%d]" % (name, length))
-        return x
-    a = np.asarray(x.numpy() if torch.is_tensor(x) else x)
-    if a.ndim != 1 or a.shape[0] != length or a.dtype.kind not in "iu":
-        raise ValueError("sweeps: %s must be an integer array [%d]" % (name, length))
-    if a[0] != 0 or np.any(np.diff(a.astype(np.int64)) < 0) or a[-1] >= 2 ** 31:
-        raise ValueError("sweeps: %s must start at 0 and be non-decreasing (int32)" % name)
-    return torch.as_tensor(a.astype(np.int32)).to(dev or _dev())
-
-
 def _records(x, n, name, dev):
     """f64[n,7] on the device; n=None: any number of rows"""
     if torch.is_tensor(x) and x.is_cuda:
@@ -108,9 +82,8 @@ def _records(x, n, name, dev):
 
 
 def _m44(x, n, name):
-    if not torch.is_tensor(x) or x.dtype != torch.float64 or tuple(x.shape) != (n, 4, 4) or not x.is_contiguous():
-        raise ValueError("sweeps: %s must be a contiguous float64 tensor [%d, 4, 4]" % (name, n))
-    return x
+    """contiguous f64 [n,4,4]; n a string: any number of matrices"""
+    return _ragged._check_tensor("sweeps", x, name, torch.float64, (n, 4, 4), "tensor")
 
 
 def _check_rows(rows, cols=None, P_cap=None):
@@ -140,12 +113,11 @@ def sweep_transforms(P_ego, frame_offsets, P_vehicle_lidar, P_ego_cam, P_vehicle
     B = len(frame_offsets) - 1
     if B < 0:
         raise ValueError("sweeps: frame_offsets must have at least one entry")
-    if not torch.is_tensor(P_ego) or P_ego.dtype != torch.float64 or P_ego.dim() != 3 or tuple(P_ego.shape[1:]) != (4, 4) or not P_ego.is_contiguous():
-        raise ValueError("sweeps: P_ego must be a contiguous float64 tensor [S, 4, 4]")
+    _m44(P_ego, "S", "P_ego")
     for t, name in ((P_vehicle_lidar, "P_vehicle_lidar"), (P_ego_cam, "P_ego_cam"), (P_vehicle_cam, "P_vehicle_cam")):
         _m44(t, B, name)
     S, dev = int(P_ego.shape[0]), P_ego.device
-    off = _offsets(frame_offsets, "frame_offsets", B + 1, dev)
+    off = _ragged._offsets("sweeps", frame_offsets, "frame_offsets", B + 1, dev)
     require_cuda(P_ego, off, P_vehicle_lidar, P_ego_cam, P_vehicle_cam)
     T = torch.zeros((max(S, 1), 4, 4), dtype=torch.float64, device=dev)
     P_cam_pc = torch.zeros((max(B, 1), 4, 4), dtype=torch.float64, device=dev)
@@ -200,7 +172,7 @@ def pack_sweeps(frames, device=None, cols=None):
 
 
 def workspace(B, S_cap, device=None):
-    return torch.empty((max(256, _lib.load().di2p_sweep_workspace_bytes(B, S_cap)),), dtype=torch.uint8, device=device or _dev())
+    return _ragged.workspace("di2p_sweep_workspace_bytes", B, S_cap, device)
 
 
 def _launch(rows, sweep_off, frame_off, T, B, S_cap, P_cap, cols, cap, mfp, box, kept, out_off, out_pts, status, ws):
@@ -212,16 +184,15 @@ def accumulate_sweeps(rows, sweep_offsets, frame_offsets, T, box=BOX, max_frame_
     """Eager: rows f32[P,4|5], T f64[S,4,4] (device), the offsets host arrays (checked here) or device tensors (checked on the device: status
     3) -> (points f32[cap,4] rows (x, y, z, intensity) in each frame's key-sweep LiDAR frame, offsets i32[B+1], kept i32[S] surviving rows per
     sweep, status i32[B]).  No synchronisation."""
-    mfp, box = _check_max_frame_points(max_frame_points), _box(box)
+    mfp, box = _ragged._check_max_frame_points("sweeps", max_frame_points), _box(box)
     P, cols = _check_rows(rows)
     B = len(frame_offsets) - 1
     if B < 0:
         raise ValueError("sweeps: frame_offsets must have at least one entry")
-    if not torch.is_tensor(T) or T.dtype != torch.float64 or T.dim() != 3 or tuple(T.shape[1:]) != (4, 4) or not T.is_contiguous():
-        raise ValueError("sweeps: T must be a contiguous float64 tensor [S, 4, 4]")
+    _m44(T, "S", "T")
     S, dev = int(T.shape[0]), rows.device
-    frame_off = _offsets(frame_offsets, "frame_offsets", B + 1, dev)
-    sweep_off = _offsets(sweep_offsets, "sweep_offsets", S + 1, dev)
+    frame_off = _ragged._offsets("sweeps", frame_offsets, "frame_offsets", B + 1, dev)
+    sweep_off = _ragged._offsets("sweeps", sweep_offsets, "sweep_offsets", S + 1, dev)
     cap = P if cap is None else int(cap)
     if cap < 0:
         raise ValueError("sweeps: cap must be >= 0")
@@ -242,7 +213,7 @@ class SweepPlan:
     rows, the others unaffected).  ws: a workspace of at least workspace(B, S_cap) bytes to use instead of an own one."""
 
     def __init__(self, B, S_cap, P_cap, cap_raw, max_frame_points, cols=4, box=BOX, device=None, ws=None):
-        self.max_src, self.box, self.cols = _check_max_frame_points(max_frame_points), _box(box), _check_cols(cols)
+        self.max_src, self.box, self.cols = _ragged._check_max_frame_points("sweeps", max_frame_points), _box(box), _check_cols(cols)
         if min(int(B), int(S_cap), int(P_cap), int(cap_raw)) < 0:
             raise ValueError("sweeps: B, S_cap, P_cap and cap_raw must be >= 0")
         dev = device or _dev()
@@ -264,12 +235,10 @@ class SweepPlan:
         plan's buffers."""
         B, S = self.B, self.S_cap
         _check_rows(rows, self.cols, self.P_cap)
-        for t, name, n in ((sweep_offsets, "sweep_offsets", S + 1), (frame_offsets, "frame_offsets", B + 1)):
-            if not torch.is_tensor(t) or t.dtype != torch.int32 or tuple(t.shape) != (n,) or not t.is_contiguous():
-                raise ValueError("sweeps: %s must be a contiguous int32 device tensor [%d]" % (name, n))
-        for t, name, n in ((ego, "ego", S), (lidar_calib, "lidar_calib", B), (cam_pose, "cam_pose", B), (cam_calib, "cam_calib", B)):
-            if not torch.is_tensor(t) or t.dtype != torch.float64 or tuple(t.shape) != (n, 7) or not t.is_contiguous():
-                raise ValueError("sweeps: %s must be a contiguous float64 device tensor [%d, 7]" % (name, n))
+        for t, name, dtype, shape in ((sweep_offsets, "sweep_offsets", torch.int32, (S + 1,)), (frame_offsets, "frame_offsets", torch.int32, (B + 1,)),
+                                      (ego, "ego", torch.float64, (S, 7)), (lidar_calib, "lidar_calib", torch.float64, (B, 7)),
+                                      (cam_pose, "cam_pose", torch.float64, (B, 7)), (cam_calib, "cam_calib", torch.float64, (B, 7))):
+            _ragged._check_tensor("sweeps", t, name, dtype, shape)
         require_cuda(rows, sweep_offsets, frame_offsets, ego, lidar_calib, cam_pose, cam_calib)
         s = stream()
         for rec, n, out in ((ego, S, self.P_ego), (lidar_calib, B, self.P_vehicle_lidar), (cam_pose, B, self.P_ego_cam), (cam_calib, B, self.P_vehicle_cam)):
@@ -289,7 +258,7 @@ class NuScenesRawPlan:
 
     def __init__(self, opt, B, S_cap, P_cap, cap_raw, max_frame_points, raw_hw=None, mode="val", cols=4, box=BOX, device=None,
                  jitter=sample_prep.JITTER, color=None):
-        _check_max_frame_points(max_frame_points)
+        _ragged._check_max_frame_points("sweeps", max_frame_points)
         _check_cols(cols)
         _box(box)
         sample_prep.option_block(opt, sample_prep.RAW_HW["nuscenes"] if raw_hw is None else raw_hw, mode, dataset="nuscenes")      # argument errors first
@@ -327,12 +296,7 @@ def prepare_nuscenes_raw(frames, ego, lidar_calib, cam_pose, cam_calib, images, 
     """Convenience: packs the frames (host_sweeps' form; ego: per frame an [S_b, 7] array, or all of them [S, 7]), builds a plan, runs it and
     checks the status (synchronises).  images u8[B,H0,W0,3]; K_raw [B,3,3]; lidar_calib / cam_pose / cam_calib [B,7] -> NuScenesRawPlan.run's
     tuple."""
-    if images is None:
-        raise ValueError("sweeps: images is None")
-    images = torch.as_tensor(images)
-    if images.dim() != 4 or images.shape[0] != len(frames):
-        raise ValueError("sweeps: images must be [B, H0, W0, 3] with one image per frame")
-    raw_hw = (images.shape[1], images.shape[2])
+    images, raw_hw = sample_prep._host_images(images, len(frames), "sweeps", "frame")
     sample_prep.option_block(opt, raw_hw, mode, dataset="nuscenes")          # argument errors before anything touches the device
     _box(box)
     parts, so, fo, cols = host_sweeps(frames)

@@ -108,6 +108,28 @@ def test_build_submaps(dev, on_device, g, s):
     assert dc <= (3 ** 0.5 + 1) * U24 * R and di <= 2 * U24 * ref["raw_refl"].max()
 
 
+def test_build_raw_at_the_chunk_edges_of_the_prefix(dev):
+    """The per-sub-map prefix over the profile counts runs in chunks of 64 profiles: sub-maps of exactly 64, 65 (one profile in the second
+    chunk), 128 (two full chunks) and 1 profile, 258 profiles and 1705 rows in all, without the skip rule, with it, and with the ground filter.
+    Offsets, kept, skip_count, status and every row against the numpy restatement, bit for bit."""
+    trav = synthetic.make_lms_traversal(np.random.default_rng(23), 4, [64, 65, 128, 1], 8)
+    h = dict(zip(KEYS, (_np(t) for t in submap.pack_scans(trav["submaps"], device="cpu"))))
+    assert list(h["submap_offsets"]) == [0, 64, 129, 257, 258] and len(h["scan_xyr"]) == 1705
+    d = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in h.items()}
+    Gl = trav["G_posesource_laser"]
+    for (skip, ground), offsets in zip(((None, None), (0.1 / 16, None), (0.1 / 16, 0.5)),
+                                       ([0, 443, 862, 1697, 1705], [0, 404, 752, 1473, 1481], [0, 106, 205, 407, 409])):
+        want = smo.build_raw(h["scan_xyr"], h["scan_offsets"], h["submap_offsets"], h["poses"], h["present"], Gl, skip, ground)
+        assert list(want["status"]) == [0, 0, 0, 0] and list(want["offsets"]) == offsets, (skip, ground)
+        pts, off, kept, skip_count, status = (_np(t) for t in submap.build_raw(d["scan_xyr"], d["scan_offsets"], d["submap_offsets"], d["poses"],
+                                                                                d["present"], Gl, skip, ground))
+        total = int(off[-1])
+        assert np.array_equal(off, want["offsets"]) and np.array_equal(kept, want["kept"]) and np.array_equal(skip_count, want["skip_count"]), (skip, ground)
+        assert np.array_equal(status, want["status"]) and list(status) == [0, 0, 0, 0], (skip, ground)
+        assert _bits(pts[:total], want["points"]), (skip, ground)
+        assert np.all(pts[total:] == 0), (skip, ground)
+
+
 def test_status_1_leaves_the_other_submaps_alone(dev, on_device):
     full = [_np(t) for t in _raw(on_device, "gnone", "s16")]
     counts = np.diff(full[1])

@@ -160,6 +160,24 @@ def test_accumulate_with_several_tiles_per_part(dev):
         assert np.all(pts[total:] == 0), cols
 
 
+def test_accumulate_at_the_chunk_edges_of_the_prefix(dev):
+    """The per-frame prefix over the part counts runs in chunks of 64 parts, 32 parts to a sweep: frames of 2, 4, 3 and 1 sweeps are 64 (exactly
+    one chunk), 128 (two), 96 (one and a half) and 32 (half a chunk) parts.  Sweeps of 300 rows: 256-row parts, two of them filled.  Offsets,
+    kept counts, status and every row against the numpy restatement, bit for bit."""
+    s = synthetic.make_nuscenes_sweeps(np.random.default_rng(29), 4, [2, 4, 3, 1], 300)
+    rows, so, fo = (_np(t) for t in sweeps.pack_sweeps(s["frames"], device="cpu"))
+    P = [swo.pose_matrices(r) for r in (np.concatenate(s["ego"]), s["lidar_calib"], s["cam_pose"], s["cam_calib"])]
+    T, _ = swo.sweep_transforms(P[0], fo, P[1], P[2], P[3])
+    want = swo.accumulate(rows, so, fo, T)
+    assert list(want["status"]) == [0, 0, 0, 0] and list(want["offsets"]) == [0, 576, 1728, 2592, 2880] and list(want["kept"]) == [288] * 10
+    pts, off, kept, status = _acc(dict(rows=_t(rows, dev), sweep_offsets=so, frame_offsets=fo), _t(T, dev))
+    total = int(off[-1])
+    assert np.array_equal(off, want["offsets"]) and np.array_equal(kept, want["kept"])
+    assert np.array_equal(status, want["status"]) and list(status) == [0, 0, 0, 0]
+    assert _bits(pts[:total], want["points"])
+    assert np.all(pts[total:] == 0)
+
+
 def test_status_1_leaves_the_other_frames_alone(dev, on_device):
     T = _t(G["T"], dev)
     full = _acc(on_device, T)
