@@ -25,6 +25,10 @@ SLP_ON = set(os.environ.get("DI2P_SLP_ON", "pnp.hip prep.hip").split())
 # scan_prep.hip: voxel keys, means and distances are compared with numpy bit for bit; no multiply-add pair may become an FMA.
 PER_FILE_FLAGS = {"solver.hip": os.environ.get("DI2P_SOLVER_FLAGS", "-mllvm -disable-machine-licm").split(),
                   "scan_prep.hip": ["-ffp-contract=off"],
+                  # point_ops.hip: the kNN distances and weights and the interpolation sums are written with __fmul_rn / __fadd_rn and documented
+                  # as separately rounded, but hipcc expands those to plain * and + and contracted them into FMAs all the same (a third of the
+                  # interpolated values and a tenth of the weights were an ulp off their numpy float32 restatement).  +2 instructions per (query, node).
+                  "point_ops.hip": ["-ffp-contract=off"],
                   # sample_prep.hip: PIL's blend rounds its multiply and its add separately, K' and the draws are compared with numpy bit for bit
                   "sample_prep.hip": ["-ffp-contract=off"],
                   # vis.hip: the registration overlay's fp64 projection is compared with numpy; its roundings decide which pixel a point lands on

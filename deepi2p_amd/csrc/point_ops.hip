@@ -10,8 +10,11 @@
 namespace {
 
 // ----------------------------------------------------------------------------------------------
-// k nearest nodes, ascending (distance, node id).  Distance is sqrtf((dx*dx + dy*dy) + dz*dz) with
-// separately rounded operations, the same value torch.norm(dim=1) produces for 3 components.
+// k nearest nodes: selected by (squared distance, node id), written in ascending (distance, node id).  Distance is
+// sqrtf((dx*dx + dy*dy) + dz*dz) with separately rounded operations (the suite restates it in numpy float32 and compares bit for
+// bit; torch.norm(dim=1) sums in another order and differs from it by an ulp in about one entry in ten).  This file is built with
+// -ffp-contract=off (build.py): __fmul_rn / __fadd_rn are plain * and + to hipcc, which would otherwise fuse them into FMAs.  The root is
+// sqrtf, which hipcc rounds correctly by default; __fsqrt_rn, despite its name, is the native v_sqrt_f32 here (1 ulp).
 // The scan orders the candidates by the SQUARED distance (sqrtf is monotone: a quarter-rate instruction per node and lane is
 // only spent on the k winners) and the node coordinates are wave-uniform reads straight from global memory (scalar loads
 // through the constant cache: no LDS staging, no LDS traffic in the loop); the k winners are then re-ordered on the rounded
@@ -63,7 +66,7 @@ __global__ __launch_bounds__(256) void knn_nodes_kernel(const float* __restrict_
     float bd[KN];
     int bi[KN];
 #pragma unroll
-    for (int j = 0; j < KN; ++j) { bd[j] = __fsqrt_rn(__uint_as_float(kd[j])); bi[j] = ki[j]; }
+    for (int j = 0; j < KN; ++j) { bd[j] = sqrtf(__uint_as_float(kd[j])); bi[j] = ki[j]; }
     // equal rounded distances: lowest node id first (insertion sort on (d, id); the squared order is already almost that)
 #pragma unroll
     for (int a = 1; a < KN; ++a)
@@ -88,9 +91,11 @@ __global__ __launch_bounds__(256) void knn_nodes_kernel(const float* __restrict_
 }
 
 // Node-level queries (a few hundred per frame: the kNN-fusion layer's k = 16 over cluster means, node_a <- node_b): one
-// WAVEFRONT per query instead of one lane.  Each lane holds up to 4 candidate keys (distance bits << 32 | node id: unsigned
-// order = ascending (distance, id) for the non-negative distances), a round picks the wave-wide minimum with a butterfly and
-// retires it; k rounds give the k nearest in order.  Same distances, same tie rule, same weight arithmetic as the kernel above.
+// WAVEFRONT per query instead of one lane.  Each lane holds up to 4 candidate keys (SQUARED distance bits << 32 | node id: unsigned
+// order = ascending (d^2, id) for the non-negative distances), a round picks the wave-wide minimum with a butterfly and
+// retires it; k rounds give the k winners of the kernel above, in (d^2, id) order, wave-uniform in every lane's registers.  They are
+// then re-ordered on the rounded distance by the same insertion sort (every lane runs it redundantly: k <= 16 values once per query),
+// so both kernels select by (d^2, id) and order by (d, id): the same neighbours, order and weights whichever one a frame's size picks.
 template <int KN>
 __global__ __launch_bounds__(256) void knn_nodes_wave_kernel(const float* __restrict__ query, const float* __restrict__ nodes,
                                                              int* __restrict__ idx, float* __restrict__ weights, int Nq, int M) {
@@ -108,14 +113,13 @@ __global__ __launch_bounds__(256) void knn_nodes_wave_kernel(const float* __rest
         key[u] = ~0ull;
         if (m < M) {
             const float dx = __fsub_rn(qx, nb[m]), dy = __fsub_rn(qy, nb[M + m]), dz = __fsub_rn(qz, nb[2 * M + m]);
-            const float d = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
+            const float d = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
             key[u] = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)m;
             if (d != d) key[u] = ~0ull - 1 - (unsigned)(M - m);       // NaN distances rank last, by id
         }
     }
     float bd[KN];
-    int mine_i = 0;
-    float mine_d = 0.0f;
+    int bi[KN];
 #pragma unroll
     for (int j = 0; j < KN; ++j) {
         unsigned long long best = key[0] < key[1] ? key[0] : key[1];
@@ -128,9 +132,24 @@ __global__ __launch_bounds__(256) void knn_nodes_wave_kernel(const float* __rest
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) if (key[u] == best) key[u] = ~0ull;      // node ids are unique: exactly one lane retires it
-        bd[j] = __uint_as_float((unsigned)(best >> 32));
-        if (lane == j) { mine_i = best == ~0ull ? 0 : (int)(unsigned)(best & 0xffffffffull); mine_d = bd[j]; }
+        bd[j] = sqrtf(__uint_as_float((unsigned)(best >> 32)));
+        bi[j] = best == ~0ull ? 0 : (int)(unsigned)(best & 0xffffffffull);
     }
+    // equal rounded distances: lowest node id first (the insertion sort of the kernel above)
+#pragma unroll
+    for (int a = 1; a < KN; ++a)
+#pragma unroll
+        for (int j = a; j > 0; --j) {
+            const bool sw = bd[j] == bd[j - 1] && bi[j] < bi[j - 1];
+            const int t = bi[j];
+            bi[j] = sw ? bi[j - 1] : t;
+            bi[j - 1] = sw ? t : bi[j - 1];
+        }
+    int mine_i = 0;
+    float mine_d = 0.0f;
+#pragma unroll
+    for (int j = 0; j < KN; ++j)
+        if (lane == j) { mine_i = bi[j]; mine_d = bd[j]; }
     if (lane < KN) idx[((long long)b * Nq + n) * KN + lane] = mine_i;
     if (weights) {
         float sum = bd[0];
@@ -306,7 +325,7 @@ extern "C" int di2p_knn_nodes(const float* query, const float* nodes, int32_t* i
                               int k, void* stream) {
     DI2P_CHECK_ARG(B >= 0 && Nq >= 0 && M > 0, "bad size");
     DI2P_CHECK_ARG(k >= 1 && k <= 16 && k <= M, "k must be in [1,16] and <= M");
-    DI2P_CHECK_ARG(M <= 4096, "M too large for the LDS node table");
+    DI2P_CHECK_ARG(M <= 4096, "M must be <= 4096");
     if (B == 0 || Nq == 0) return 0;
     const dim3 grid(di2p_cdiv(Nq, 256), B), block(256);
     hipStream_t st = (hipStream_t)stream;

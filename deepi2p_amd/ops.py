@@ -53,20 +53,36 @@ def ball_query(node_to_point_dist, radius, K):
     return out
 
 
+def _shape(t, shape, name, what):
+    """shape: expected sizes, None = any; the operands of one call must agree on B / N / M / k before a pointer is handed over"""
+    if t.dim() != len(shape) or any(e is not None and int(s) != int(e) for s, e in zip(t.shape, shape)):
+        raise RuntimeError("%s must be %s, got %s" % (name, what, list(t.shape)))
+
+
 def knn_nodes(query, nodes, k, want_weights=False):
     """query f32[B,3,Nq], nodes f32[B,3,M] -> idx i32[B,Nq,k] (+ weights f32[B,Nq,k])."""
     require_cuda(query, nodes)
+    _chk(query, _f32, "query")
+    _chk(nodes, _f32, "nodes")
+    _shape(query, (None, 3, None), "query", "f32[B, 3, Nq]")
     B, _, Nq = query.shape
-    M = nodes.shape[2]
+    _shape(nodes, (B, 3, None), "nodes", "f32[B, 3, M] for query f32[B, 3, Nq]")
+    M, k = nodes.shape[2], int(k)             # the library checks 1 <= k <= 16, k <= M <= 4096 before it launches
     idx = torch.empty((B, Nq, k), dtype=_i32, device=query.device)
     w = torch.empty((B, Nq, k), dtype=_f32, device=query.device) if want_weights else None
-    call("di2p_knn_nodes", ptr(query), ptr(nodes), ptr(idx), ptr(w), B, Nq, M, int(k), stream())
+    call("di2p_knn_nodes", ptr(query), ptr(nodes), ptr(idx), ptr(w), B, Nq, M, k, stream())
     return (idx, w) if want_weights else idx
 
 
 def cluster_stats(pc, knn_idx, M):
+    """pc f32[B,3,N], knn_idx i32[B,N,k] (column 0 = nearest node) -> mean f32[B,3,M], mask f32[B,M], min_idx i32[B,N]."""
     require_cuda(pc, knn_idx)
+    _chk(pc, _f32, "pc")
+    _chk(knn_idx, _i32, "knn_idx")
+    _shape(pc, (None, 3, None), "pc", "f32[B, 3, N]")
     B, _, N = pc.shape
+    _shape(knn_idx, (B, N, None), "knn_idx", "i32[B, N, k] for pc f32[B, 3, N]")
+    M = int(M)
     mean = torch.empty((B, 3, M), dtype=_f32, device=pc.device)
     mask = torch.empty((B, M), dtype=_f32, device=pc.device)
     min_idx = torch.empty((B, N), dtype=_i32, device=pc.device)
@@ -75,8 +91,17 @@ def cluster_stats(pc, knn_idx, M):
 
 
 def build_point_input(pc, intensity, sn, cluster_mean, min_idx):
+    """pc f32[B,3,N], intensity f32[B,1,N], sn f32[B,3,N], cluster_mean f32[B,3,M], min_idx i32[B,N] -> centers f32[B,3,N], aug f32[B,7,N]."""
     require_cuda(pc, intensity, sn, cluster_mean, min_idx)
+    for t, name in ((pc, "pc"), (intensity, "intensity"), (sn, "sn"), (cluster_mean, "cluster_mean")):
+        _chk(t, _f32, name)
+    _chk(min_idx, _i32, "min_idx")
+    _shape(pc, (None, 3, None), "pc", "f32[B, 3, N]")
     B, _, N = pc.shape
+    _shape(intensity, (B, 1, N), "intensity", "f32[B, 1, N] for pc f32[B, 3, N]")
+    _shape(sn, (B, 3, N), "sn", "f32[B, 3, N] for pc f32[B, 3, N]")
+    _shape(cluster_mean, (B, 3, None), "cluster_mean", "f32[B, 3, M] for pc f32[B, 3, N]")
+    _shape(min_idx, (B, N), "min_idx", "i32[B, N] for pc f32[B, 3, N]")
     centers = torch.empty_like(pc)
     aug = torch.empty((B, 7, N), dtype=_f32, device=pc.device)
     call("di2p_build_point_input", ptr(pc), ptr(intensity), ptr(sn), ptr(cluster_mean), ptr(min_idx), ptr(centers),
@@ -85,17 +110,31 @@ def build_point_input(pc, intensity, sn, cluster_mean, min_idx):
 
 
 def interpolate(feats, idx, weights):
+    """feats f32[B,C,M], idx i32[B,Nq,k], weights f32[B,Nq,k] -> f32[B,C,Nq]."""
     require_cuda(feats, idx, weights)
+    _chk(feats, _f32, "feats")
+    _chk(idx, _i32, "idx")
+    _chk(weights, _f32, "weights")
+    _shape(feats, (None, None, None), "feats", "f32[B, C, M]")
     B, C, M = feats.shape
+    _shape(idx, (B, None, None), "idx", "i32[B, Nq, k] for feats f32[B, C, M]")
     Nq, k = idx.shape[1], idx.shape[2]
+    _shape(weights, (B, Nq, k), "weights", "f32[B, Nq, k] for idx i32[B, Nq, k]")
     out = torch.empty((B, C, Nq), dtype=_f32, device=feats.device)
     call("di2p_interpolate", ptr(feats), ptr(idx), ptr(weights), ptr(out), B, C, M, Nq, k, stream())
     return out
 
 
 def gather_neighbors(database, query, idx):
+    """database f32[B,3,Md], query f32[B,3,Mq], idx i32[B,Mq,K] -> f32[B,3,Mq*K] = database[:, idx] - query."""
     require_cuda(database, query, idx)
+    _chk(database, _f32, "database")
+    _chk(query, _f32, "query")
+    _chk(idx, _i32, "idx")
+    _shape(database, (None, 3, None), "database", "f32[B, 3, Md]")
     B, _, Md = database.shape
+    _shape(query, (B, 3, None), "query", "f32[B, 3, Mq] for database f32[B, 3, Md]")
+    _shape(idx, (B, query.shape[2], None), "idx", "i32[B, Mq, K] for query f32[B, 3, Mq]")
     Mq, K = idx.shape[1], idx.shape[2]
     out = torch.empty((B, 3, Mq * K), dtype=_f32, device=database.device)
     call("di2p_gather_neighbors", ptr(database), ptr(query), ptr(idx), ptr(out), B, Md, Mq, K, stream())
@@ -115,7 +154,10 @@ def argmax_channels(scores):
 
 
 def channel_max(x):
+    """x f32[B,C,N] -> f32[B,C], the maximum over N (NaN if the row holds one)."""
     require_cuda(x)
+    _chk(x, _f32, "x")
+    _shape(x, (None, None, None), "x", "f32[B, C, N]")
     B, C, N = x.shape
     out = torch.empty((B, C), dtype=_f32, device=x.device)
     call("di2p_channel_max", ptr(x), ptr(out), B, C, N, stream())

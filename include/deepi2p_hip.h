@@ -61,9 +61,13 @@ int di2p_ball_query_forward(const float* node_to_point_dist, int32_t* out_idx, f
  * di2p_knn_nodes: the dense-distance + torch.topk(k smallest, sorted) idiom of
  *   models/networks_pc.py:61-65, models/networks_united.py:158-161,176-178,
  *   models/layers_pc.py:798-799.   query f32[B,3,Nq], nodes f32[B,3,M] ->
- *   idx i32[B,Nq,k] ascending distance, ties -> lower node id.  weights (may be NULL) f32[B,Nq,k]
+ *   idx i32[B,Nq,k].  The k neighbours are SELECTED by (squared distance, node id) and WRITTEN in
+ *   ascending (distance, node id), distance = the rounded fp32 root of the fp32 squared distance
+ *   (dx*dx + dy*dy) + dz*dz: exact ties go to the lower node id, and two nodes whose squared
+ *   distances differ but whose roots round to the same float are told apart only at the k-th
+ *   place.  One rule for every B, Nq, M.  weights (may be NULL) f32[B,Nq,k]
  *   = 1 - d_k/sum_j d_j, the interpolation weights of networks_united.py:97-98.
- *   k <= 16, M <= 1024.
+ *   k <= 16, k <= M <= 4096.
  * di2p_cluster_stats: networks_pc.py:66-76.  pc f32[B,3,N], knn idx (nearest = idx[b,n,0], row
  *   stride idx_stride) -> cluster_mean f32[B,3,M] = sum/(count+1e-5), mask f32[B,M] (1 if the
  *   node owns >=1 point), min_idx i32[B,N] (compact copy of the nearest id).

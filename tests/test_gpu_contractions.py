@@ -134,6 +134,48 @@ def test_attention_pool(dev):
     assert (out - ref).abs().max() <= _tol(ref, 320)
 
 
+@pytest.mark.parametrize("C,HW,Mn", [(1, 1, 1), (65, 33, 65), (256, 320, 128), (70, 2, 130)])
+def test_attention_pool_vs_fp64(dev, C, HW, Mn):
+    """Against fp64 within the forward bound of an fp32 dot product of HW terms (any summation order) and one more rounding for the division:
+    (HW + 2) * 2^-24 * sum |feat * score| / HW per output.  Derived, not measured."""
+    from deepi2p_amd import ops
+    g = torch.Generator().manual_seed(C + HW + Mn)
+    feat, score = torch.randn(2, C, HW, generator=g), torch.randn(2, HW, Mn, generator=g)
+    out = ops.attention_pool(feat.to(dev), score.to(dev)).cpu().double()
+    ref = torch.bmm(feat.double(), score.double()) / HW
+    bound = (HW + 2) * 2.0 ** -24 * torch.bmm(feat.double().abs(), score.double().abs()) / HW
+    print("attention_pool C=%d HW=%d Mn=%d: max err / bound = %.3f" % (C, HW, Mn, float(((out - ref).abs() / bound).max())))
+    assert torch.all((out - ref).abs() <= bound)
+
+
+@pytest.mark.parametrize("k0", [0, 7])
+@pytest.mark.parametrize("Kv", [1, 2, 3, 5, 40, 257])
+@pytest.mark.parametrize("M", [1, 64, 65, 200])
+def test_batch_gemv_vs_fp64(dev, M, Kv, k0):
+    """Against fp64 within (Kv + 2) * 2^-24 * sum_k |W v| per output: the standard forward bound of an fp32 dot product (Kv products and the
+    partial sums of four slices times four accumulators).  Derived, not measured."""
+    from deepi2p_amd import ops
+    g = torch.Generator().manual_seed(1000 * M + 10 * Kv + k0)
+    B = 3
+    Wt, v = torch.randn(k0 + Kv + 3, M, generator=g), torch.randn(B, Kv, generator=g)      # rows below k0 and above k0 + Kv are never read
+    out = ops.batch_gemv(Wt.to(dev), k0, v.to(dev)).cpu().double()
+    rows = Wt[k0:k0 + Kv].double()
+    ref = v.double() @ rows
+    bound = (Kv + 2) * 2.0 ** -24 * (v.double().abs() @ rows.abs())
+    assert tuple(out.shape) == (B, M)
+    assert torch.all((out - ref).abs() <= bound)
+
+
+@pytest.mark.parametrize("M,Kv0,Kv1,k0,k1", [(1, 1, 1, 0, 1), (64, 3, 40, 0, 7), (65, 257, 5, 7, 0), (200, 40, 257, 256, 280),(200, 2, 2, 5, 0)])
+def test_batch_gemv2_is_the_sum_of_two_gemvs(dev, M, Kv0, Kv1, k0, k1):
+    """the kernel promises that each half is summed as a single call would be: bit-equal to the two launches and one fp32 add"""
+    from deepi2p_amd import ops
+    g = torch.Generator().manual_seed(M + Kv0 + Kv1)
+    Wt = torch.randn(max(k0 + Kv0, k1 + Kv1), M, generator=g).to(dev)
+    v0, v1 = torch.randn(3, Kv0, generator=g).to(dev), torch.randn(3, Kv1, generator=g).to(dev)
+    assert torch.equal(ops.batch_gemv2(Wt, k0, v0, k1, v1), ops.batch_gemv(Wt, k0, v0) + ops.batch_gemv(Wt, k1, v1))
+
+
 @pytest.mark.parametrize("B,Cin,H,W,Cout,k,s,p", [(2, 3, 64, 128, 64, 7, 2, 3), (2, 64, 16, 32, 64, 3, 1, 1),
                                                   (1, 64, 16, 32, 128, 3, 2, 1), (2, 64, 16, 32, 128, 1, 2, 0),
                                                   (3, 256, 5, 16, 512, 3, 2, 1), (1, 512, 5, 16, 512, 3, 1, 1),
