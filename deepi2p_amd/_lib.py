@@ -117,6 +117,7 @@ _SIGS = {
     "di2p_conv3x3_winograd": [c_void_p] * 6 + [c_int] * 6 + [c_void_p],
     "di2p_conv3x3_x3": [c_void_p] * 6 + [c_int] * 7 + [c_void_p] * 4 + [c_int, c_void_p],
     "di2p_conv3x3_x3_supported": [c_int] * 7,
+    "di2p_conv3x3_x3_plan": [c_int] * 7 + [ctypes.POINTER(ctypes.c_int32)],
     "di2p_head_x3_pack": [c_void_p, c_int, c_void_p, c_void_p],
     "di2p_stem_x3_pack": [c_void_p, c_void_p, c_void_p],
     "di2p_stem_x3_supported": [c_int, c_int],

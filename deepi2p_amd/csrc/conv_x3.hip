@@ -476,6 +476,25 @@ extern "C" int di2p_conv3x3_x3_supported(int B, int Cin, int H, int W, int Cout,
     return best.cfg >= 0 && cx_size_limit(B, Cin, H, W, Cout, &best) == nullptr ? 1 : 0;
 }
 
+// What di2p_conv3x3_x3 would launch for this layer (host code: nothing is launched): the same cx_best call as the launch entry.  0 where
+// di2p_conv3x3_x3_supported is 0, else 1 and out[0..13] = configuration, instance (index in kInst), number of instances, fallback to the
+// single-buffered instance taken, dbuf, the plan's items, the instance's items, the instance's PWT, tiles_per_frame, n_mt, most output rows
+// of a tile, nseg % NSEG, Cout % MT, Cin / KS.  The tests ask it which instance a shape runs on (tests/conv_x3_cases.py).
+extern "C" int di2p_conv3x3_x3_plan(int B, int Cin, int H, int W, int Cout, int stride, int cfg, int32_t* out) {
+    if (!out || !di2p_conv3x3_x3_supported(B, Cin, H, W, Cout, stride, cfg)) return 0;
+    int inst = -1;
+    const CxPlan best = cx_best(B, Cin, H, W, Cout, stride, cfg >= 0 ? cfg : di2p_opt(DI2P_OPT_CONV_X3_CFG), &inst);
+    if (best.cfg < 0 || inst < 0) return 0;
+    const CxCfg& c = kCfgs[best.cfg];
+    const int KS = c.MF == 32 ? 16 : 32, NSEG = c.TN * c.WN, MT = c.MF * c.TM * c.WM;
+    const CxPlan own = cx_plan(best.cfg, B, Cin, H, W, Cout, stride);      // before cx_best's fallback and its items = the instance's
+    const int rows = (best.PPU / best.PW - 3) / stride + 1;
+    const int v[14] = {best.cfg, inst, (int)(sizeof(kInst) / sizeof(kInst[0])), own.dbuf != best.dbuf, best.dbuf, own.items, kInst[inst].items,
+                       kInst[inst].pwt, best.tiles_per_frame, best.n_mt, rows, best.nseg % NSEG, Cout % MT, Cin / KS};
+    for (int i = 0; i < 14; ++i) out[i] = v[i];
+    return 1;
+}
+
 // y f32[B,Cout,OH,OW] = relu?( scale * conv3x3(x f32[B,Cin,H,W]; pad 1, stride 1|2) + shift + residual ), weights Wp = di2p_bf16x3_pack of
 // the tap-major matrix Wt[(kh*3+kw)*Cin + ci][Cout].  Optional second output of the SAME input (stride 2 only): y_ds f32[B,Cout,OH,OW] =
 // scale_ds * conv1x1/stride-2(x) + shift_ds with Wp_ds = di2p_bf16x3_pack of Wt_ds[Cin][Cout] (the BasicBlock's downsample branch,

@@ -648,6 +648,22 @@ def conv3x3_x3_supported(x_shape, Cout, stride, cfg=-1):
     return bool(_lib.load().di2p_conv3x3_x3_supported(B, Cin, H, W, int(Cout), int(stride), int(cfg)))
 
 
+CONV_X3_PLAN_FIELDS = ("cfg", "instance", "instances", "fallback", "dbuf", "plan_items", "instance_items", "pwt", "tiles_per_frame", "n_mt",
+                       "max_rows", "ragged_segments", "partial_cout", "chunks")
+
+
+def conv3x3_x3_plan(x_shape, Cout, stride, cfg=-1):
+    """What di2p_conv3x3_x3 would launch for this layer (di2p_conv3x3_x3_plan; host code, no GPU needed): None where conv3x3_x3_supported
+    is False, else a dict of CONV_X3_PLAN_FIELDS -- the configuration, the kernel instance (index, of `instances`), whether the
+    double-buffered plan fell back to a single-buffered instance, the staging items of plan and instance, the instance's compile-time patch
+    row length, and the tile geometry (ragged_segments = nseg % NSEG, partial_cout = Cout % MT, chunks = Cin / KS)."""
+    B, Cin, H, W = (int(v) for v in x_shape)
+    out = (ctypes.c_int32 * len(CONV_X3_PLAN_FIELDS))()
+    if not _lib.load().di2p_conv3x3_x3_plan(B, Cin, H, W, int(Cout), int(stride), int(cfg), out):
+        return None
+    return dict(zip(CONV_X3_PLAN_FIELDS, (int(v) for v in out)))
+
+
 def conv3x3_x3(x, Wp, Cout, scale, shift, stride, relu, residual=None, downsample=None, cfg=-1):
     """3x3 / pad 1 convolution on the bf16 matrix instructions with exact three-way fp32 splits (di2p_conv3x3_x3):
     y = relu?(scale * conv(x) + shift + residual).  Wp = bf16x3_pack(tap-major Wt[9 Cin, Cout]).  stride 2 takes

@@ -277,8 +277,15 @@ int di2p_point_head_labels_x3(const di2p_head_labels_x3_t* h, int B, int N, void
  *   cfg   = the tile configuration: 0..3 forces one, -1 takes the knob "conv_x3_cfg" (whose default -1 is the cheapest by a cost model).
  * di2p_conv3x3_x3_supported: 1 if a kernel instance of configuration cfg exists for the shape (OW % 32 == 0 and Cin % 16 == 0, or
  * OW % 16 == 0 and Cin % 32 == 0; the input patch of a tile must fit the LDS), else 0 -- the caller then uses di2p_conv3x3_winograd /
- * di2p_conv2d.  (ABI 8: cfg added to both.) */
+ * di2p_conv2d.  (ABI 8: cfg added to both.)
+ * di2p_conv3x3_x3_plan (additive, ABI 9; detect by symbol): which kernel instance the call would run (host code, launches nothing; for
+ * tests and tools: tests/conv_x3_cases.py keeps one layer shape per instance by it).  0 where
+ * di2p_conv3x3_x3_supported is 0, else 1 and out[0..13] = configuration, instance index, instance count, fallback to the single-buffered
+ * instance taken (0/1), double-buffered (0/1), staging items the plan needs, items of the instance, the instance's compile-time patch row
+ * length (0: run-time), workgroup tiles per frame, Cout tiles, most output rows under one tile, nseg % NSEG (segments in the ragged last
+ * tile, 0: none), Cout % MT (rows of the partial Cout tile, 0: none), Cin / KS (chunks of the K loop). */
 int di2p_conv3x3_x3_supported(int B, int Cin, int H, int W, int Cout, int stride, int cfg);
+int di2p_conv3x3_x3_plan(int B, int Cin, int H, int W, int Cout, int stride, int cfg, int32_t* out);
 int di2p_conv3x3_x3(const float* x, const void* Wp, const float* scale, const float* shift, const float* residual, float* y, int B,
                     int Cin, int H, int W, int Cout, int stride, int relu, const void* Wp_ds, const float* scale_ds,
                     const float* shift_ds, float* y_ds, int cfg, void* stream);
