@@ -18,6 +18,7 @@
 //     in LDS and is advanced by thread 0 between sweeps.
 // The algorithm statement is the oracle's (oracle/frustum_lm.cpp); DESIGN.md lists it step by step.
 #include "common.h"
+#include "solver_prep.h"
 
 #include <float.h>
 #include <math.h>
@@ -104,649 +105,6 @@ __device__ __forceinline__ void make_rot(const double* x, Rot<NP>& r) {
             skew_add(r.dR[1], 1.0, 0, 1, 0);
             skew_add(r.dR[2], 1.0, 0, 0, 1);
         }
-    }
-}
-
-// Packed, front-filtered point records: ONE aligned vector load per point per sweep.
-//   PT=float : float4 {x, y, z, label bits}            (16 B)
-//   PT=double: {double x, y, z; long long label}       (32 B)
-// Points whose label is not 0/1 (incl. the -1 the front filter writes) are dropped here once, in stable
-// order, so the hot sweeps never see them (registration.cpp:87-125 skips them per residual block).
-template <typename PT> struct Rec;
-template <> struct __attribute__((aligned(16))) Rec<float> { float x, y, z; int lab; };
-template <> struct __attribute__((aligned(16))) Rec<double> { double x, y, z; long long lab; };
-
-// Frame preparation (once per solve call, one 1024-thread workgroup per frame):
-//   1. records with label 0/1 are sorted by (label: 1 first, Morton code of the (x,z) ground-plane cell) with an
-//      in-workgroup bitonic sort on unique 64-bit keys (key << 32 | point index): deterministic, data-independent
-//      network, 64 KB LDS chunks with the wide strides done in the (L2-resident) global scratch;
-//   2. consecutive groups of CL = 64 sorted records of one label form a CLUSTER with an axis-aligned bounding box.
-// The solver's sweeps test each box against the five planes of the camera frustum of the current iterate and
-// classify the points of a cluster individually only when the box touches a plane (see sweep_clusters).
-constexpr int CL = 64;
-// axis-aligned bounds of a cluster (centre, half extents) in fp32, rounded OUTWARD: the fp32 box contains every point of the cluster
-// rxz / r3: the largest ground-plane radius sqrt(x^2 + z^2) and the largest norm of a point of the cluster, rounded UP -- how far a point of
-// the cluster can move per radian of iterate rotation (2-D solver: about the y axis; 3-D: any axis), see the classification cache below.
-struct __attribute__((aligned(16))) Box { float cx, cy, cz, hx, hy, hz, rxz, r3; };
-
-__device__ __forceinline__ unsigned spread10(unsigned v) {
-    v &= 0x3ffu;
-    v = (v | (v << 8)) & 0x00ff00ffu; v = (v | (v << 4)) & 0x0f0f0f0fu; v = (v | (v << 2)) & 0x33333333u; v = (v | (v << 1)) & 0x55555555u;
-    return v;
-}
-
-// Index of cell (x, y) of a 1024 x 1024 grid along the Hilbert curve.  Unlike the Z-order (Morton) curve it has no jumps: 64 consecutive
-// records always form one connected patch of the ground plane, so the cluster boxes are tighter (modelled on the config-2 scene,
-// tools/model_cluster_keys.py: 145 instead of 168 of 321 clusters per frame touch a frustum plane).
-__device__ __forceinline__ unsigned hilbert10(unsigned x, unsigned y) {
-    unsigned d = 0;
-#pragma unroll
-    for (unsigned s = 512; s > 0; s >>= 1) {
-        const unsigned rx = (x & s) ? 1u : 0u, ry = (y & s) ? 1u : 0u;
-        d += s * s * ((3u * rx) ^ ry);
-        if (ry == 0) {
-            if (rx == 1) { x = s - 1 - x; y = s - 1 - y; }
-            const unsigned t = x; x = y; y = t;
-        }
-    }
-    return d;
-}
-
-// Wave-wide min / max of four floats at once by DPP (rows of 16 lanes, then row_bcast15 / row_bcast31 into lane 63; v_min / v_max drop NaNs like
-// fmin / fmax).  One asm block per call: hipcc expands fminf(v, dpp(v)) into four instructions per join; the four values are interleaved so that
-// a value's consecutive joins are three instructions apart (a DPP read needs two wait states after a write of the same register).
-#define DI2P_RED4(OP, CTRL)                          \
-    OP " %0, %0, %0 " CTRL "\n\t" OP " %1, %1, %1 " CTRL "\n\t" OP " %2, %2, %2 " CTRL "\n\t" OP " %3, %3, %3 " CTRL "\n\t"
-#define DI2P_RED4_ALL(OP)                                                        \
-    asm volatile("s_nop 1\n\t"                                                  \
-                 DI2P_RED4(OP, "quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf") \
-                 DI2P_RED4(OP, "quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf") \
-                 DI2P_RED4(OP, "row_half_mirror row_mask:0xf bank_mask:0xf")     \
-                 DI2P_RED4(OP, "row_mirror row_mask:0xf bank_mask:0xf")          \
-                 DI2P_RED4(OP, "row_bcast:15 row_mask:0xa bank_mask:0xf")        \
-                 DI2P_RED4(OP, "row_bcast:31 row_mask:0xc bank_mask:0xf")        \
-                 : "+v"(a), "+v"(b), "+v"(c), "+v"(d))
-__device__ __forceinline__ void wave_min4_f32(float& a, float& b, float& c, float& d) {
-    DI2P_RED4_ALL("v_min_f32_dpp");
-    a = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, a), 63)); b = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, b), 63));
-    c = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, c), 63)); d = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, d), 63));
-}
-__device__ __forceinline__ void wave_max4_f32(float& a, float& b, float& c, float& d) {
-    DI2P_RED4_ALL("v_max_f32_dpp");
-    a = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, a), 63)); b = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, b), 63));
-    c = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, c), 63)); d = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, d), 63));
-}
-#undef DI2P_RED4_ALL
-
-template <typename PT>
-__global__ __launch_bounds__(1024) void prepare_kernel(const PT* __restrict__ points, const int* __restrict__ labels, int N, int P,
-                                                       int NCMAX, unsigned long long* __restrict__ keys_all,
-                                                       Rec<PT>* __restrict__ packed, Box* __restrict__ boxes_all,
-                                                       int* __restrict__ counts, int force_bitonic, const double* __restrict__ Kmat, double H,
-                                                       double W, float* __restrict__ camf_all, const int* __restrict__ only_flagged) {
-    // only_flagged != nullptr: this launch is the FALLBACK behind the multi-workgroup preparation (prep_*_kernel below): it runs for the
-    // frames whose flag is set (a bucket above 4096 keys: a degenerate scene) and leaves the others alone
-    if (only_flagged && only_flagged[blockIdx.x] == 0) return;
-    constexpr int CH = 8192;                       // LDS chunk (64 KB)
-    __shared__ unsigned long long chunk[CH];
-    __shared__ float s_f[4][16];
-    __shared__ int s_i[2][16];
-    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const PT* px = points + (long long)f * 3 * N;
-    const PT* py = px + N;
-    const PT* pz = px + 2 * (long long)N;
-    const int* lab = labels + (long long)f * N;
-    unsigned long long* keys = keys_all + (long long)f * 2 * P;      // two buffers of P keys: scattered / ranked (the bitonic network sorts the first in place)
-    unsigned long long* keys2 = keys + P;
-    Rec<PT>* out = packed + (long long)f * (N + 2 * CL);      // frame stride: N records + the padding of the two label blocks
-    Box* boxes = boxes_all + (long long)f * NCMAX;
-
-    // 1. ground-plane bounding box of the valid points, label counts (fixed-order reductions)
-    float mnx = __builtin_inff(), mxx = -__builtin_inff(), mnz = __builtin_inff(), mxz = -__builtin_inff();
-    int c1 = 0, c0 = 0;
-    for (int n = tid; n < N; n += 1024) {
-        const int l = lab[n];
-        if (l == 0 || l == 1) {
-            const float x = (float)px[n], z = (float)pz[n];
-            mnx = fminf(mnx, x); mxx = fmaxf(mxx, x); mnz = fminf(mnz, z); mxz = fmaxf(mxz, z);
-            c1 += l == 1; c0 += l == 0;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        mnx = fminf(mnx, __shfl_xor(mnx, o)); mxx = fmaxf(mxx, __shfl_xor(mxx, o));
-        mnz = fminf(mnz, __shfl_xor(mnz, o)); mxz = fmaxf(mxz, __shfl_xor(mxz, o));
-        c1 += __shfl_xor(c1, o); c0 += __shfl_xor(c0, o);
-    }
-    if (lane == 0) { s_f[0][wave] = mnx; s_f[1][wave] = mxx; s_f[2][wave] = mnz; s_f[3][wave] = mxz; s_i[0][wave] = c1; s_i[1][wave] = c0; }
-    __syncthreads();
-    mnx = s_f[0][0]; mxx = s_f[1][0]; mnz = s_f[2][0]; mxz = s_f[3][0];
-    int n1 = s_i[0][0], n0 = s_i[1][0];
-    for (int w = 1; w < 16; ++w) {
-        mnx = fminf(mnx, s_f[0][w]); mxx = fmaxf(mxx, s_f[1][w]); mnz = fminf(mnz, s_f[2][w]); mxz = fmaxf(mxz, s_f[3][w]);
-        n1 += s_i[0][w]; n0 += s_i[1][w];
-    }
-    const float ext = fmaxf(mxx - mnx, mxz - mnz);
-    const float scale = (ext > 0.0f && ext < __builtin_inff()) ? 1023.0f / ext : 0.0f;
-
-    // 2. sort keys: [label != 1][20-bit Hilbert index of the cell] << 32 | index (unique); points with other labels get ~0 (sort to the end)
-    // (branch-free: the three loads are unconditional from a clamped index, so that the 4-way unrolled passes below keep them all in flight)
-    auto key_of = [&](int n) -> unsigned long long {
-        const int nc = min(n, N - 1);
-        const int l = lab[nc];
-        const float qx = fminf(fmaxf(((float)px[nc] - mnx) * scale, 0.0f), 1023.0f);
-        const float qz = fminf(fmaxf(((float)pz[nc] - mnz) * scale, 0.0f), 1023.0f);
-        const unsigned m = hilbert10((unsigned)qx, (unsigned)qz);
-        const unsigned long long k = ((unsigned long long)((l == 1 ? 0u : 1u << 20) | m) << 32) | (unsigned)nc;
-        return (n < N && (l == 0 || l == 1)) ? k : ~0ull;
-    };
-    // 3a. FAST sort (round 4): the keys are nearly uniform over their 21 significant bits, so a counting sort on the top 11 bits (label +
-    //     a 32 x 32 grid of the Hilbert curve: 2048 buckets, LDS atomics) leaves buckets of ~10-25 keys; every key is then ranked inside its
-    //     bucket by counting (one thread per key, the bucket read as broadcasts), which puts it at its final position in the second key buffer.
-    //     A bucket above 4096 keys (a degenerate scene) sends the frame to the bitonic network of 3b.  The result is the SAME total order either
-    //     way (tests compare the two paths): the preparation takes ~0.1 ms per frame instead of 0.53 (120 passes of a 32768-key network with a
-    //     1024-thread barrier each).
-    constexpr int NBK = 2048;
-    int* cntv = reinterpret_cast<int*>(chunk);            // [NBK] bucket counts, then fill cursors
-    int* basev = cntv + NBK;                              // [NBK + 1] exclusive offsets
-    __shared__ int s_flag[4];                             // [1]: fall back to the bitonic network
-    bool sorted = false;
-    if (!force_bitonic) {
-        for (int i = tid; i < NBK; i += 1024) cntv[i] = 0;
-        if (tid < 4) s_flag[tid] = 0;
-        __syncthreads();
-        for (int n = tid; n < N; n += 4096) {
-            unsigned long long k4[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) k4[u] = key_of(n + 1024 * u);
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (k4[u] != ~0ull) atomicAdd(&cntv[(int)(k4[u] >> 42)], 1);
-        }
-        __syncthreads();
-        {   // exclusive scan of the 2048 counts: two per thread, wave scan, 16 wave totals
-            const int a0 = cntv[2 * tid], a1 = cntv[2 * tid + 1];
-            int v = a0 + a1;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(v, o); if (lane >= o) v += u; }
-            if (lane == 63) s_i[0][wave] = v;
-            __syncthreads();
-            int woff = 0;
-            for (int w = 0; w < wave; ++w) woff += s_i[0][w];
-            const int excl = woff + v - (a0 + a1);
-            basev[2 * tid] = excl; basev[2 * tid + 1] = excl + a0;
-            if (tid == 1023) basev[NBK] = excl + a0 + a1;
-        }
-        __syncthreads();
-        for (int i = tid; i < NBK; i += 1024) cntv[i] = 0;
-        __syncthreads();
-        for (int n = tid; n < N; n += 4096) {
-            unsigned long long k4[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) k4[u] = key_of(n + 1024 * u);
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (k4[u] != ~0ull) { const int bk = (int)(k4[u] >> 42); keys[basev[bk] + atomicAdd(&cntv[bk], 1)] = k4[u]; }
-        }
-        __syncthreads();
-        // rank every key inside its bucket by counting (#{j : key_j < key}; the keys are unique), one THREAD per key: neighbouring threads sit
-        // in the same bucket and read the same addresses (broadcast).  The ranked keys go to the second key buffer.  A bucket above 4096 keys
-        // (a degenerate scene: everything in a few cells) sends the frame to the bitonic network instead.
-        for (int i = tid; i < NBK; i += 1024)
-            if (basev[i + 1] - basev[i] > 4096) s_flag[1] = 1;
-        __syncthreads();
-        if (s_flag[1] == 0) {
-            const int nv = basev[NBK];
-            for (int p = tid; p < nv; p += 1024) {
-                const unsigned long long k = keys[p];
-                const int bk = (int)(k >> 42), b0 = basev[bk], c = basev[bk + 1] - b0;
-                int rank = 0;
-                for (int j = 0; j < c; j += 8) {            // eight loads in flight (clamped; the duplicates do not count)
-                    unsigned long long q[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) q[u] = keys[b0 + min(j + u, c - 1)];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) rank += (j + u < c && q[u] < k) ? 1 : 0;
-                }
-                keys2[b0 + rank] = k;
-            }
-        }
-        sorted = s_flag[1] == 0;
-        __syncthreads();
-    }
-    if (!sorted) {      // workgroup-uniform
-    for (int n = tid; n < P; n += 1024) keys[n] = key_of(n);
-    __syncthreads();
-
-    // 3b. bitonic sort, ascending
-    const int CHe = P < CH ? P : CH;
-    const int nchunks = P / CHe;
-    auto chunk_stages = [&](int base, int k, int j_first) {     // stages j_first, j_first/2, ..., 1 of merge size k on the LDS chunk
-        for (int j = j_first; j > 0; j >>= 1) {
-            for (int t = tid; t < CHe / 2; t += 1024) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                const bool up = ((base + i) & k) == 0;
-                const unsigned long long a = chunk[i], b = chunk[i + j];
-                if ((a > b) == up) { chunk[i] = b; chunk[i + j] = a; }
-            }
-            __syncthreads();
-        }
-    };
-    for (int c = 0; c < nchunks; ++c) {
-        const int base = c * CHe;
-        for (int i = tid; i < CHe; i += 1024) chunk[i] = keys[base + i];
-        __syncthreads();
-        for (int k = 2; k <= CHe; k <<= 1) chunk_stages(base, k, k >> 1);
-        for (int i = tid; i < CHe; i += 1024) keys[base + i] = chunk[i];
-        __syncthreads();
-    }
-    for (int k = CHe << 1; k <= P; k <<= 1) {
-        for (int j = k >> 1; j >= CHe; j >>= 1) {
-            for (int t = tid; t < P / 2; t += 1024) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                const bool up = (i & k) == 0;
-                const unsigned long long a = keys[i], b = keys[i + j];
-                if ((a > b) == up) { keys[i] = b; keys[i + j] = a; }
-            }
-            __syncthreads();
-        }
-        for (int c = 0; c < nchunks; ++c) {
-            const int base = c * CHe;
-            for (int i = tid; i < CHe; i += 1024) chunk[i] = keys[base + i];
-            __syncthreads();
-            chunk_stages(base, k, CHe >> 1);
-            for (int i = tid; i < CHe; i += 1024) keys[base + i] = chunk[i];
-            __syncthreads();
-        }
-    }
-
-    }
-    // 4. records in sorted order, every label block CLUSTER-ALIGNED: label-1 block [0, n1), padded to nc1 * CL, label-0 block
-    //    [nc1 * CL, nc1 * CL + n0), padded to (nc1 + nc0) * CL -- cluster c is always the records [c * CL, c * CL + CL), all of them
-    //    addressable (the padding repeats the block's last record; the sweeps mask those lanes out)
-    const int nv = n1 + n0;
-    const int nc1 = (n1 + CL - 1) / CL, nc0 = (n0 + CL - 1) / CL;
-    const unsigned long long* skeys = sorted ? keys2 : keys;
-    const int nrec = (nc1 + nc0) * CL;
-    for (int i0 = tid; i0 < nrec; i0 += 4096) {          // four records per trip: key loads, then the 16 gathers, all in flight together
-        int nn[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int i = min(i0 + 1024 * u, nrec - 1);
-            const bool first = i < nc1 * CL;
-            const int rank = first ? min(i, n1 - 1) : n1 + min(i - nc1 * CL, n0 - 1);       // position in the sorted key list
-            nn[u] = (int)(unsigned)(skeys[rank] & 0xffffffffull);
-        }
-        Rec<PT> r4[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { r4[u].x = px[nn[u]]; r4[u].y = py[nn[u]]; r4[u].z = pz[nn[u]]; r4[u].lab = lab[nn[u]]; }
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            if (i0 + 1024 * u < nrec) out[i0 + 1024 * u] = r4[u];
-    }
-    __syncthreads();
-
-    // 5. bounding boxes: one wavefront REDUCES a cluster (its 64 records), the cluster's eight reduced values are parked in one lane, and after up
-    //    to 64 clusters every lane finishes its own box (centre, half extents, radii: ~60 fp64 instructions that used to run on lane 0 once per
-    //    cluster, serially)
-    const int nct = nc1 + nc0;
-    for (int t0 = 0; wave + 16 * t0 < nct; t0 += 64) {
-        double mlo[3] = {0, 0, 0}, mhi[3] = {0, 0, 0};
-        float mrxz = 0.0f, mr3 = 0.0f;
-        bool mnan = false;
-        for (int tt = 0; tt < 64 && wave + 16 * (t0 + tt) < nct; ++tt) {
-            const int c = wave + 16 * (t0 + tt);
-            const int start = c * CL;
-            const int end = c < nc1 ? min(start + CL, n1) : min(start + CL, nc1 * CL + n0);
-            const bool valid = start + lane < end;
-            double x = 0, y = 0, z = 0;
-            if (valid) { const Rec<PT> r = out[start + lane]; x = (double)r.x; y = (double)r.y; z = (double)r.z; }
-            double lo[3] = {valid ? x : __builtin_inf(), valid ? y : __builtin_inf(), valid ? z : __builtin_inf()};
-            double hi[3] = {valid ? x : -__builtin_inf(), valid ? y : -__builtin_inf(), valid ? z : -__builtin_inf()};
-            double rxz = valid ? x * x + z * z : 0.0, r3 = valid ? x * x + y * y + z * z : 0.0;
-            float frxz, fr3;
-            if (sizeof(PT) == 4) {
-                // fp32 records: the coordinates ARE floats, so the eight reductions run on fp32 values by DPP (no LDS round trips) and give the
-                // very same box -- min / max of floats are exact, and sqrt / scaling / rounding to float are monotone, so the radii may be
-                // rounded per lane before the maximum (round 3: 100 ds_bpermute with their latencies per cluster)
-                float l0 = (float)lo[0], l1 = (float)lo[1], l2 = (float)lo[2], h0 = (float)hi[0], h1 = (float)hi[1], h2 = (float)hi[2];
-                float pad0 = __builtin_inff(), pad1 = 0.0f;
-                frxz = (float)(sqrt(rxz) * (1.0 + 1e-6)) + 1e-30f; fr3 = (float)(sqrt(r3) * (1.0 + 1e-6)) + 1e-30f;
-                wave_min4_f32(l0, l1, l2, pad0);
-                wave_max4_f32(h0, h1, h2, pad1);
-                float pad2 = 0.0f, pad3 = 0.0f;
-                wave_max4_f32(frxz, fr3, pad2, pad3);
-                lo[0] = l0; lo[1] = l1; lo[2] = l2; hi[0] = h0; hi[1] = h1; hi[2] = h2;
-            } else {
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-                    for (int a = 0; a < 3; ++a) { lo[a] = fmin(lo[a], __shfl_xor(lo[a], o)); hi[a] = fmax(hi[a], __shfl_xor(hi[a], o)); }
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) { rxz = fmax(rxz, __shfl_xor(rxz, o)); r3 = fmax(r3, __shfl_xor(r3, o)); }
-                frxz = (float)(sqrt(rxz) * (1.0 + 1e-6)) + 1e-30f; fr3 = (float)(sqrt(r3) * (1.0 + 1e-6)) + 1e-30f;
-            }
-            // a NaN coordinate must poison the box (fmin/fmax drop it): such clusters are always classified per point
-            const bool nan_any = __any(valid && !(x == x && y == y && z == z)) != 0;
-            if (lane == tt) {
-#pragma unroll
-                for (int a = 0; a < 3; ++a) { mlo[a] = lo[a]; mhi[a] = hi[a]; }
-                mrxz = frxz; mr3 = fr3; mnan = nan_any;
-            }
-        }
-        const int c = wave + 16 * (t0 + lane);
-        if (c < nct) {
-            Box bx;
-            float* bc = &bx.cx;
-            float* bh = &bx.hx;
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const double cd = 0.5 * (mlo[a] + mhi[a]);
-                const float cf = (float)cd;
-                // half extent measured from the ROUNDED centre, grown by 1e-6 (>> 2^-24): centre +- half extent contains lo and hi
-                const double hd = fmax(mhi[a] - (double)cf, (double)cf - mlo[a]);
-                bc[a] = cf;
-                bh[a] = (float)(hd * (1.0 + 1e-6)) + 1e-30f;
-            }
-            if (mnan) bx.hx = __builtin_nanf("");
-            bx.rxz = mrxz;
-            bx.r3 = mr3;
-            boxes[c] = bx;
-        }
-    }
-    if (tid == 0) {
-        counts[4 * f] = n1; counts[4 * f + 1] = n0; counts[4 * f + 2] = nc1; counts[4 * f + 3] = nc0;
-        // the frame's NORMALISED frustum-plane coefficients in fp32 (see Pre32 below): they depend on the camera only, so every sweep of every
-        // hypothesis reads them back with scalar loads instead of re-deriving them (six conversions, four divisions, eight products per wave and sweep)
-        const double* Kf = Kmat + (long long)f * 9;
-        float* cf = camf_all + (long long)f * 8;
-        const float fx = (float)Kf[0], cx = (float)Kf[2], wcx = (float)((W - 1.0) - Kf[2]), fy = (float)Kf[4], cy = (float)Kf[5], hcy = (float)((H - 1.0) - Kf[5]);
-        const float iL = 1.0f / (fabsf(fx) + fabsf(cx)), iR = 1.0f / (fabsf(fx) + fabsf(wcx));
-        const float iT = 1.0f / (fabsf(fy) + fabsf(cy)), iB = 1.0f / (fabsf(fy) + fabsf(hcy));
-        cf[0] = fx * iL; cf[1] = cx * iL; cf[2] = fx * iR; cf[3] = wcx * iR;
-        cf[4] = fy * iT; cf[5] = cy * iT; cf[6] = fy * iB; cf[7] = hcy * iB;
-    }
-}
-
-// ----------------------------------------------------------------------------------------------
-// MULTI-WORKGROUP frame preparation (round 6).  prepare_kernel runs one 1024-thread workgroup per frame: 32 of 256 compute units for 0.26 ms at
-// the head of every solve.  The same five steps as five launches, G workgroups per frame each (same keys, same total order, same records and
-// boxes, bit for bit -- tests compare the paths):
-//   prep_bounds_kernel   partial ground-plane bounds + label counts per slice; clears the frame's flag
-//   prep_hist_kernel     keys of the slice (stored), bucket counts of the slice (LDS atomics) -> [frame][slice][bucket]
-//   prep_scatter_kernel  bucket offsets = exclusive scan of the summed counts (every workgroup, into LDS); a slice's keys go to
-//                        offset[bucket] + (counts of the slices before it) + an LDS cursor: no global atomics
-//   prep_rank_kernel     one thread per key: rank inside its bucket by counting -> sorted keys
-//   prep_records_kernel  one wavefront per cluster: gathers its 64 records, writes them and reduces the box FROM ITS REGISTERS
-// A frame with a bucket above 4096 keys is flagged by the scatter step, skipped by the last two and prepared by prepare_kernel (launched
-// behind them with `only_flagged`).
-constexpr int PREP_NBK = 2048;        // buckets: the top 11 key bits (label + 32 x 32 grid of the Hilbert curve)
-constexpr int PREP_G = 8;             // workgroups per frame of the slice kernels (PREP_NBK % PREP_G == 0)
-constexpr int PREP_CPW = 4;           // clusters per wavefront of prep_records_kernel (their keys, then their gathers, in flight together; parked in lanes 0..3, finished lane-parallel)
-struct PrepWs { float* partial; int* cntg; int* bases; int* flag; };      // [F][G][8] | [F][G][NBK] bucket counts per slice | [F][NBK + 1] | [F]
-
-// bounds, scale and label counts of a frame from its G partial results (same min / max / sums whatever the slicing: exact operations)
-struct PrepFrame { float mnx, mnz, scale; int n1, n0; };
-__device__ __forceinline__ PrepFrame prep_frame(const float* __restrict__ partial, int f) {
-    float mnx = __builtin_inff(), mxx = -__builtin_inff(), mnz = __builtin_inff(), mxz = -__builtin_inff();
-    int n1 = 0, n0 = 0;
-    for (int g = 0; g < PREP_G; ++g) {
-        const float* q = partial + ((long long)f * PREP_G + g) * 8;
-        mnx = fminf(mnx, q[0]); mxx = fmaxf(mxx, q[1]); mnz = fminf(mnz, q[2]); mxz = fmaxf(mxz, q[3]);
-        n1 += __builtin_bit_cast(int, q[4]); n0 += __builtin_bit_cast(int, q[5]);
-    }
-    const float ext = fmaxf(mxx - mnx, mxz - mnz);
-    PrepFrame r;
-    r.mnx = mnx; r.mnz = mnz; r.scale = (ext > 0.0f && ext < __builtin_inff()) ? 1023.0f / ext : 0.0f; r.n1 = n1; r.n0 = n0;
-    return r;
-}
-__device__ __forceinline__ void prep_slice(int N, int g, int& lo, int& hi) {
-    const int S = ((N + PREP_G - 1) / PREP_G + 255) & ~255;
-    lo = min(g * S, N); hi = min(lo + S, N);
-}
-
-template <typename PT>
-__global__ __launch_bounds__(256) void prep_bounds_kernel(const PT* __restrict__ points, const int* __restrict__ labels, int N, PrepWs w) {
-    __shared__ float s_f[4][4];
-    __shared__ int s_i[2][4];
-    const int f = blockIdx.x / PREP_G, g = blockIdx.x % PREP_G, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const PT* px = points + (long long)f * 3 * N;
-    const PT* pz = px + 2 * (long long)N;
-    const int* lab = labels + (long long)f * N;
-    if (g == 0 && tid == 0) w.flag[f] = 0;
-    int lo, hi;
-    prep_slice(N, g, lo, hi);
-    float mnx = __builtin_inff(), mxx = -__builtin_inff(), mnz = __builtin_inff(), mxz = -__builtin_inff();
-    int c1 = 0, c0 = 0;
-    for (int n = lo + tid; n < hi; n += 256) {
-        const int l = lab[n];
-        if (l == 0 || l == 1) {
-            const float x = (float)px[n], z = (float)pz[n];
-            mnx = fminf(mnx, x); mxx = fmaxf(mxx, x); mnz = fminf(mnz, z); mxz = fmaxf(mxz, z);
-            c1 += l == 1; c0 += l == 0;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        mnx = fminf(mnx, __shfl_xor(mnx, o)); mxx = fmaxf(mxx, __shfl_xor(mxx, o));
-        mnz = fminf(mnz, __shfl_xor(mnz, o)); mxz = fmaxf(mxz, __shfl_xor(mxz, o));
-        c1 += __shfl_xor(c1, o); c0 += __shfl_xor(c0, o);
-    }
-    if (lane == 0) { s_f[0][wave] = mnx; s_f[1][wave] = mxx; s_f[2][wave] = mnz; s_f[3][wave] = mxz; s_i[0][wave] = c1; s_i[1][wave] = c0; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int v = 1; v < 4; ++v) {
-            mnx = fminf(mnx, s_f[0][v]); mxx = fmaxf(mxx, s_f[1][v]); mnz = fminf(mnz, s_f[2][v]); mxz = fmaxf(mxz, s_f[3][v]);
-            c1 += s_i[0][v]; c0 += s_i[1][v];
-        }
-        float* q = w.partial + ((long long)f * PREP_G + g) * 8;
-        q[0] = mnx; q[1] = mxx; q[2] = mnz; q[3] = mxz; q[4] = __builtin_bit_cast(float, c1); q[5] = __builtin_bit_cast(float, c0);
-    }
-}
-
-// the sort key of point n (prepare_kernel's key_of: the same expressions, the same bits)
-template <typename PT>
-__device__ __forceinline__ unsigned long long prep_key(const PT* px, const PT* pz, const int* lab, int n, const PrepFrame& fr) {
-    const int l = lab[n];
-    const float qx = fminf(fmaxf(((float)px[n] - fr.mnx) * fr.scale, 0.0f), 1023.0f);
-    const float qz = fminf(fmaxf(((float)pz[n] - fr.mnz) * fr.scale, 0.0f), 1023.0f);
-    const unsigned m = hilbert10((unsigned)qx, (unsigned)qz);
-    const unsigned long long k = ((unsigned long long)((l == 1 ? 0u : 1u << 20) | m) << 32) | (unsigned)n;
-    return (l == 0 || l == 1) ? k : ~0ull;
-}
-
-template <typename PT>
-__global__ __launch_bounds__(256) void prep_hist_kernel(const PT* __restrict__ points, const int* __restrict__ labels, int N, int P,
-                                                        unsigned long long* __restrict__ keys_all, PrepWs w) {
-    __shared__ int cnt[PREP_NBK];
-    const int f = blockIdx.x / PREP_G, g = blockIdx.x % PREP_G, tid = threadIdx.x;
-    const PT* px = points + (long long)f * 3 * N;
-    const PT* pz = px + 2 * (long long)N;
-    const int* lab = labels + (long long)f * N;
-    unsigned long long* raw = keys_all + (long long)f * 2 * P + P;         // the second key buffer holds the unsorted keys until the ranking
-    const PrepFrame fr = prep_frame(w.partial, f);
-    for (int i = tid; i < PREP_NBK; i += 256) cnt[i] = 0;
-    __syncthreads();
-    int lo, hi;
-    prep_slice(N, g, lo, hi);
-    for (int n = lo + tid; n < hi; n += 256) {
-        const unsigned long long k = prep_key(px, pz, lab, n, fr);
-        raw[n] = k;
-        if (k != ~0ull) atomicAdd(&cnt[(int)(k >> 42)], 1);
-    }
-    __syncthreads();
-    for (int i = tid; i < PREP_NBK; i += 256) w.cntg[((long long)f * PREP_G + g) * PREP_NBK + i] = cnt[i];
-}
-
-__global__ __launch_bounds__(1024) void prep_scatter_kernel(int N, int P, unsigned long long* __restrict__ keys_all, PrepWs w) {
-    __shared__ int cur[PREP_NBK];           // where the slice's next key of a bucket goes
-    __shared__ int s_w[16];
-    const int f = blockIdx.x / PREP_G, g = blockIdx.x % PREP_G, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    unsigned long long* keys = keys_all + (long long)f * 2 * P;
-    const unsigned long long* raw = keys + P;
-    {   // exclusive scan of the 2048 summed counts: two buckets per thread, wave scan, 16 wave totals (prepare_kernel's scan)
-        const int* cg = w.cntg + (long long)f * PREP_G * PREP_NBK;
-        int a0 = 0, a1 = 0, before0 = 0, before1 = 0;       // totals of the two buckets; the keys of the slices before this one
-#pragma unroll
-        for (int q = 0; q < PREP_G; ++q) {
-            const int c0 = cg[q * PREP_NBK + 2 * tid], c1 = cg[q * PREP_NBK + 2 * tid + 1];
-            a0 += c0; a1 += c1;
-            before0 += q < g ? c0 : 0; before1 += q < g ? c1 : 0;
-        }
-        int v = a0 + a1;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(v, o); if (lane >= o) v += u; }
-        if (lane == 63) s_w[wave] = v;
-        __syncthreads();
-        int woff = 0;
-        for (int q = 0; q < wave; ++q) woff += s_w[q];
-        const int excl = woff + v - (a0 + a1);
-        cur[2 * tid] = excl + before0; cur[2 * tid + 1] = excl + a0 + before1;
-        if (g == 0) {
-            int* bases = w.bases + (long long)f * (PREP_NBK + 1);
-            bases[2 * tid] = excl; bases[2 * tid + 1] = excl + a0;
-            if (tid == 1023) bases[PREP_NBK] = excl + a0 + a1;
-        }
-        if (a0 > 4096 || a1 > 4096) w.flag[f] = 1;            // a degenerate scene: the frame goes to prepare_kernel's bitonic network
-    }
-    __syncthreads();
-    int lo, hi;
-    prep_slice(N, g, lo, hi);
-    for (int n = lo + tid; n < hi; n += 1024) {
-        const unsigned long long k = raw[n];
-        if (k != ~0ull) keys[atomicAdd(&cur[(int)(k >> 42)], 1)] = k;
-    }
-}
-
-__global__ __launch_bounds__(256) void prep_rank_kernel(int P, unsigned long long* __restrict__ keys_all, PrepWs w) {
-    const int f = blockIdx.y;
-    if (w.flag[f]) return;
-    const int* bases = w.bases + (long long)f * (PREP_NBK + 1);
-    const unsigned long long* keys = keys_all + (long long)f * 2 * P;
-    unsigned long long* keys2 = keys_all + (long long)f * 2 * P + P;
-    const int nv = bases[PREP_NBK];
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= nv) return;
-    // rank inside the bucket by counting (#{j : key_j < key}; the keys are unique): neighbouring threads sit in the same bucket and read the
-    // same addresses (broadcast)
-    const unsigned long long k = keys[p];
-    const int bk = (int)(k >> 42), b0 = bases[bk], c = bases[bk + 1] - b0;
-    int rank = 0;
-    for (int j = 0; j < c; j += 8) {            // eight loads in flight (clamped; the duplicates do not count)
-        unsigned long long q[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) q[u] = keys[b0 + min(j + u, c - 1)];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) rank += (j + u < c && q[u] < k) ? 1 : 0;
-    }
-    keys2[b0 + rank] = k;
-}
-
-// Records in sorted order (every label block cluster-aligned and padded with copies of its last record) and the cluster boxes: one wavefront
-// per cluster holds the cluster's 64 records in its lanes -- written out and reduced from registers; PREP_CPW clusters per wavefront, their
-// reduced values parked in lanes 0 .. PREP_CPW - 1, which then finish their own boxes (prepare_kernel steps 4 and 5, the same operations).
-template <typename PT>
-__global__ __launch_bounds__(256) void prep_records_kernel(const PT* __restrict__ points, const int* __restrict__ labels, int N, int P, int NCMAX,
-                                                           const unsigned long long* __restrict__ keys_all, Rec<PT>* __restrict__ packed,
-                                                           Box* __restrict__ boxes_all, int* __restrict__ counts, const double* __restrict__ Kmat,
-                                                           double H, double W, float* __restrict__ camf_all, PrepWs w) {
-    const int f = blockIdx.y;
-    if (w.flag[f]) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const PT* px = points + (long long)f * 3 * N;
-    const PT* py = px + N;
-    const PT* pz = px + 2 * (long long)N;
-    const int* lab = labels + (long long)f * N;
-    const unsigned long long* skeys = keys_all + (long long)f * 2 * P + P;
-    Rec<PT>* out = packed + (long long)f * (N + 2 * CL);
-    Box* boxes = boxes_all + (long long)f * NCMAX;
-    const PrepFrame fr = prep_frame(w.partial, f);
-    const int n1 = fr.n1, n0 = fr.n0;
-    const int nc1 = (n1 + CL - 1) / CL, nc0 = (n0 + CL - 1) / CL, nct = nc1 + nc0;
-    if (blockIdx.x == 0 && tid == 0) {
-        counts[4 * f] = n1; counts[4 * f + 1] = n0; counts[4 * f + 2] = nc1; counts[4 * f + 3] = nc0;
-        const double* Kf = Kmat + (long long)f * 9;
-        float* cf = camf_all + (long long)f * 8;
-        const float fx = (float)Kf[0], cx = (float)Kf[2], wcx = (float)((W - 1.0) - Kf[2]), fy = (float)Kf[4], cy = (float)Kf[5], hcy = (float)((H - 1.0) - Kf[5]);
-        const float iL = 1.0f / (fabsf(fx) + fabsf(cx)), iR = 1.0f / (fabsf(fx) + fabsf(wcx));
-        const float iT = 1.0f / (fabsf(fy) + fabsf(cy)), iB = 1.0f / (fabsf(fy) + fabsf(hcy));
-        cf[0] = fx * iL; cf[1] = cx * iL; cf[2] = fx * iR; cf[3] = wcx * iR;
-        cf[4] = fy * iT; cf[5] = cy * iT; cf[6] = fy * iB; cf[7] = hcy * iB;
-    }
-    const int c_first = (blockIdx.x * 4 + wave) * PREP_CPW;
-    if (c_first >= nct) return;              // wave-uniform
-    double mlo[3] = {0, 0, 0}, mhi[3] = {0, 0, 0};
-    float mrxz = 0.0f, mr3 = 0.0f;
-    bool mnan = false;
-    // the PREP_CPW clusters' keys, then their gathers, are requested together (a cluster alone is a chain of two dependent round trips)
-    int nn_all[PREP_CPW];
-#pragma unroll
-    for (int tt = 0; tt < PREP_CPW; ++tt) {
-        const int c = min(c_first + tt, nct - 1);
-        const int i = c * CL + lane;
-        const int rank = c < nc1 ? min(i, n1 - 1) : n1 + min(i - nc1 * CL, n0 - 1);       // position in the sorted key list (padding: the block's last record)
-        nn_all[tt] = (int)(unsigned)(skeys[rank] & 0xffffffffull);
-    }
-    Rec<PT> r_all[PREP_CPW];
-#pragma unroll
-    for (int tt = 0; tt < PREP_CPW; ++tt) { r_all[tt].x = px[nn_all[tt]]; r_all[tt].y = py[nn_all[tt]]; r_all[tt].z = pz[nn_all[tt]]; r_all[tt].lab = lab[nn_all[tt]]; }
-#pragma unroll
-    for (int tt = 0; tt < PREP_CPW; ++tt) {
-        if (c_first + tt >= nct) break;          // wave-uniform
-        const int c = c_first + tt;
-        const int i = c * CL + lane;
-        const bool first = c < nc1;
-        const Rec<PT> r = r_all[tt];
-        out[i] = r;
-        const int end = first ? n1 : nc1 * CL + n0;
-        const bool valid = i < end;
-        const double x = valid ? (double)r.x : 0.0, y = valid ? (double)r.y : 0.0, z = valid ? (double)r.z : 0.0;
-        double lo[3] = {valid ? x : __builtin_inf(), valid ? y : __builtin_inf(), valid ? z : __builtin_inf()};
-        double hi[3] = {valid ? x : -__builtin_inf(), valid ? y : -__builtin_inf(), valid ? z : -__builtin_inf()};
-        double rxz = valid ? x * x + z * z : 0.0, r3 = valid ? x * x + y * y + z * z : 0.0;
-        float frxz, fr3;
-        if (sizeof(PT) == 4) {
-            float l0 = (float)lo[0], l1 = (float)lo[1], l2 = (float)lo[2], h0 = (float)hi[0], h1 = (float)hi[1], h2 = (float)hi[2];
-            float pad0 = __builtin_inff(), pad1 = 0.0f;
-            frxz = (float)(sqrt(rxz) * (1.0 + 1e-6)) + 1e-30f; fr3 = (float)(sqrt(r3) * (1.0 + 1e-6)) + 1e-30f;
-            wave_min4_f32(l0, l1, l2, pad0);
-            wave_max4_f32(h0, h1, h2, pad1);
-            float pad2 = 0.0f, pad3 = 0.0f;
-            wave_max4_f32(frxz, fr3, pad2, pad3);
-            lo[0] = l0; lo[1] = l1; lo[2] = l2; hi[0] = h0; hi[1] = h1; hi[2] = h2;
-        } else {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-                for (int a = 0; a < 3; ++a) { lo[a] = fmin(lo[a], __shfl_xor(lo[a], o)); hi[a] = fmax(hi[a], __shfl_xor(hi[a], o)); }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) { rxz = fmax(rxz, __shfl_xor(rxz, o)); r3 = fmax(r3, __shfl_xor(r3, o)); }
-            frxz = (float)(sqrt(rxz) * (1.0 + 1e-6)) + 1e-30f; fr3 = (float)(sqrt(r3) * (1.0 + 1e-6)) + 1e-30f;
-        }
-        const bool nan_any = __any(valid && !(x == x && y == y && z == z)) != 0;
-        if (lane == tt) {
-#pragma unroll
-            for (int a = 0; a < 3; ++a) { mlo[a] = lo[a]; mhi[a] = hi[a]; }
-            mrxz = frxz; mr3 = fr3; mnan = nan_any;
-        }
-    }
-    const int c = c_first + lane;
-    if (lane < PREP_CPW && c < nct) {
-        Box bx;
-        float* bc = &bx.cx;
-        float* bh = &bx.hx;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const double cd = 0.5 * (mlo[a] + mhi[a]);
-            const float cf = (float)cd;
-            const double hd = fmax(mhi[a] - (double)cf, (double)cf - mlo[a]);
-            bc[a] = cf;
-            bh[a] = (float)(hd * (1.0 + 1e-6)) + 1e-30f;
-        }
-        if (mnan) bx.hx = __builtin_nanf("");
-        bx.rxz = mrxz;
-        bx.r3 = mr3;
-        boxes[c] = bx;
     }
 }
 
@@ -1155,60 +513,22 @@ __device__ __forceinline__ int cluster_status(const Box& bx, const Pre32& q, con
     return decided ? (inside ? 2 : 0) : (neg ? (lrs > kGuardLrMin ? 5 : 3) : 1);      // lrs NaN -> 3
 }
 
-// Wave-wide minima of FOUR non-negative floats (or +inf) at once, by DPP (no LDS round trip): four joins inside rows of 16 lanes, then
-// row_bcast15 / row_bcast31 carry the row results into lane 63, which is read back as a scalar.  Non-negative floats order like their bit
-// patterns, so the joins are v_min_u32 with the DPP modifier ON the instruction -- written as one asm block because hipcc expands
-// fminf(v, dpp(v)) into mov + mov_dpp + canonicalise + min (24 instructions per value instead of 6).  The four values are interleaved: three
-// independent instructions separate a value's consecutive joins, which covers the two wait states a DPP read needs after a VALU write.
+// Wave-wide minima of FOUR non-negative floats (or +inf) at once, on the DPP ladder of solver_prep.h (no LDS round trip; 6 instructions per
+// value instead of the 24 hipcc makes of fminf(v, dpp(v))).  Non-negative floats order like their bit patterns, so the joins are v_min_u32.
 __device__ __forceinline__ void wave_min4_nonneg(float& a, float& b, float& c, float& d) {
-#define DI2P_MIN4(CTRL)                                \
-    "v_min_u32_dpp %0, %0, %0 " CTRL "\n\t"           \
-    "v_min_u32_dpp %1, %1, %1 " CTRL "\n\t"           \
-    "v_min_u32_dpp %2, %2, %2 " CTRL "\n\t"           \
-    "v_min_u32_dpp %3, %3, %3 " CTRL "\n\t"
-    asm volatile("s_nop 1\n\t"
-                 DI2P_MIN4("quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf")
-                 DI2P_MIN4("quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf")
-                 DI2P_MIN4("row_half_mirror row_mask:0xf bank_mask:0xf")
-                 DI2P_MIN4("row_mirror row_mask:0xf bank_mask:0xf")
-                 DI2P_MIN4("row_bcast:15 row_mask:0xa bank_mask:0xf")
-                 DI2P_MIN4("row_bcast:31 row_mask:0xc bank_mask:0xf")
-                 : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
-#undef DI2P_MIN4
-    a = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, a), 63));
-    b = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, b), 63));
-    c = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, c), 63));
-    d = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, d), 63));
+    asm volatile(DI2P_DPP_LADDER(DI2P_DPP_J4, "v_min_u32_dpp", "") : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
+    a = wave_lane63(a); b = wave_lane63(b); c = wave_lane63(c); d = wave_lane63(d);
 }
 
 // The same for TWO values and for ONE (batches of the classification walk smaller than four): fewer independent instructions separate a value's
 // consecutive joins, so the DPP read-after-write wait states are filled with s_nop.
 __device__ __forceinline__ void wave_min2_nonneg(float& a, float& b) {
-#define DI2P_MIN2(CTRL) "v_min_u32_dpp %0, %0, %0 " CTRL "\n\t" "v_min_u32_dpp %1, %1, %1 " CTRL "\n\t" "s_nop 0\n\t"
-    asm volatile("s_nop 1\n\t"
-                 DI2P_MIN2("quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf")
-                 DI2P_MIN2("quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf")
-                 DI2P_MIN2("row_half_mirror row_mask:0xf bank_mask:0xf")
-                 DI2P_MIN2("row_mirror row_mask:0xf bank_mask:0xf")
-                 DI2P_MIN2("row_bcast:15 row_mask:0xa bank_mask:0xf")
-                 DI2P_MIN2("row_bcast:31 row_mask:0xc bank_mask:0xf")
-                 : "+v"(a), "+v"(b));
-#undef DI2P_MIN2
-    a = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, a), 63));
-    b = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, b), 63));
+    asm volatile(DI2P_DPP_LADDER(DI2P_DPP_J2, "v_min_u32_dpp", "s_nop 0\n\t") : "+v"(a), "+v"(b));
+    a = wave_lane63(a); b = wave_lane63(b);
 }
 __device__ __forceinline__ void wave_min1_nonneg(float& a) {
-#define DI2P_MIN1(CTRL) "v_min_u32_dpp %0, %0, %0 " CTRL "\n\t" "s_nop 1\n\t"
-    asm volatile("s_nop 1\n\t"
-                 DI2P_MIN1("quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf")
-                 DI2P_MIN1("quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf")
-                 DI2P_MIN1("row_half_mirror row_mask:0xf bank_mask:0xf")
-                 DI2P_MIN1("row_mirror row_mask:0xf bank_mask:0xf")
-                 DI2P_MIN1("row_bcast:15 row_mask:0xa bank_mask:0xf")
-                 DI2P_MIN1("row_bcast:31 row_mask:0xc bank_mask:0xf")
-                 : "+v"(a));
-#undef DI2P_MIN1
-    a = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, a), 63));
+    asm volatile(DI2P_DPP_LADDER(DI2P_DPP_J1, "v_min_u32_dpp", "s_nop 1\n\t") : "+v"(a));
+    a = wave_lane63(a);
 }
 template <int N> __device__ __forceinline__ void wave_min_nonneg(float* v) {
     static_assert(N == 1 || N == 2 || N == 4, "batch sizes of the cluster walk");
@@ -1916,9 +1236,15 @@ struct LMState {
 //   [0] finish_iteration  [1] begin: fetch + scaled matrix  [2] Cholesky solve  [3] model change  [4] begin: step, projection, stores
 //   [5] decide without the fit  [6] interpolating fit  [7] trial_next_decide
 __shared__ long long g_lmclk[8];
-#define DI2P_LMCLK(i, t0) g_lmclk[i] += clock64() - (t0)
+#define DI2P_LMSTAMP(t) long long t = clock64()                         // start a stamp
+#define DI2P_LMRESTAMP(t) t = clock64()                                 // restart it
+#define DI2P_LMCLK(i, t0) g_lmclk[i] += clock64() - (t0)                // add the time since a stamp to sub-stage i ...
+#define DI2P_LMADD(field, t0) field += (int)(clock64() - (t0))          // ... or to a field of the LM state
 #else
+#define DI2P_LMSTAMP(t) ((void)0)
+#define DI2P_LMRESTAMP(t) ((void)0)
 #define DI2P_LMCLK(i, t0) ((void)0)
+#define DI2P_LMADD(field, t0) ((void)0)
 #endif
 template <int N> __device__ __forceinline__ void pin_regs(double* v) {
 #pragma unroll
@@ -1929,9 +1255,7 @@ template <int NP>
 __device__ __forceinline__ void lm_begin_iteration(LMState<NP>& st) {
     constexpr int NT = Tri<NP>::N;
     const double kMinDiag = 1e-6, kMaxDiag = 1e32, kMinRadius = 1e-32, kGradTol = 1e-10;
-#ifdef DI2P_SOLVER_LMPROF
-    long long tb0 = clock64();
-#endif
+    DI2P_LMSTAMP(tb0);
     double S[NP], A[NT], g[NP], diag[NP], sc[3];
 #pragma unroll
     for (int a = 0; a < NP; ++a) { S[a] = st.S[a]; g[a] = st.g[a]; diag[a] = st.diag[a]; }
@@ -1959,16 +1283,12 @@ __device__ __forceinline__ void lm_begin_iteration(LMState<NP>& st) {
         }
 #pragma unroll
         for (int a = 0; a < NP; ++a) { M[a * (a + 1) / 2 + a] += lm_div(diag[a], radius); ds[a] = -(S[a] * g[a]); }
-#ifdef DI2P_SOLVER_LMPROF
         DI2P_LMCLK(1, tb0);
-        const long long tc0 = clock64();
-#endif
+        DI2P_LMSTAMP(tc0);
         bool valid = chol_solve_inplace<NP>(M, ds);
-#ifdef DI2P_SOLVER_LMPROF
-        st.n_resweep += (int)(clock64() - tc0);
+        DI2P_LMADD(st.n_resweep, tc0);
         DI2P_LMCLK(2, tc0);
-        const long long tm0 = clock64();
-#endif
+        DI2P_LMSTAMP(tm0);
         double model_change = 0.0;
         if (valid) {
             double q = 0.0, l = 0.0;
@@ -1981,16 +1301,12 @@ __device__ __forceinline__ void lm_begin_iteration(LMState<NP>& st) {
             model_change = -(l + 0.5 * q);
             valid = model_change > 0.0;
         }
-#ifdef DI2P_SOLVER_LMPROF
         DI2P_LMCLK(3, tm0);
-        const long long tp0 = clock64();
-#endif
+        DI2P_LMSTAMP(tp0);
         if (!valid) {
             if (++invalid_run >= 5) { write_back(); st.done = 1; return; }
             radius /= decrease; decrease *= 2.0; reuse_diag = 1;
-#ifdef DI2P_SOLVER_LMPROF
-            tb0 = clock64();
-#endif
+            DI2P_LMRESTAMP(tb0);
             continue;
         }
         invalid_run = 0;
@@ -2013,9 +1329,7 @@ __device__ __forceinline__ void lm_begin_iteration(LMState<NP>& st) {
         for (int a = 0; a < NP; ++a) { st.delta[a] = delta[a]; st.xe[a] = xe[a]; }
         st.gd = gd; st.dmax = dmax; st.t = 1.0; st.ls_it = 0;
         st.phase = PH_TRIAL; st.want_j = 2; st.prev_vok = 0; st.prev_gok = 0;
-#ifdef DI2P_SOLVER_LMPROF
         DI2P_LMCLK(4, tp0);
-#endif
         return;   // needs a sweep at xe
     }
 }
@@ -2077,15 +1391,11 @@ template <int NP>
 __device__ __forceinline__ void lm_apply(LMState<NP>& st, int action, double fe, const double* ge, const double* Ae) {
     bool begin = action == ACT_BEGIN;
     if (action == ACT_FINISH_CUR || action == ACT_FINISH_FIRST) {
-#ifdef DI2P_SOLVER_LMPROF
-        const long long tf0 = clock64();
-#endif
+        DI2P_LMSTAMP(tf0);
         const bool first = action == ACT_FINISH_FIRST;
         if (first) plus_proj<NP>(st.x, st.delta, 1.0, st.lb, st.ub, st.xe);     // delta stays unscaled: back to the first trial point
         begin = lm_finish_iteration<NP>(st, first ? st.f1 : fe, first ? st.g1 : ge, first ? st.A1 : Ae);
-#ifdef DI2P_SOLVER_LMPROF
         DI2P_LMCLK(0, tf0);
-#endif
     }
     if (begin) lm_begin_iteration<NP>(st);
 }
@@ -2149,14 +1459,10 @@ __device__ __forceinline__ int lm_decide(LMState<NP>& st, bool ok, double fe, co
     }
     st.prev_t = cur.x; st.prev_f = cur.value; st.prev_g = cur.gradient; st.prev_vok = cur.value_ok; st.prev_gok = cur.grad_ok;
     double p[6];
-#ifdef DI2P_SOLVER_LMPROF
-    const long long tfit0 = clock64();
+    DI2P_LMSTAMP(tfit0);
     const bool fitted = interpolating_fit(st.cost, st.gd, cur, prev, p);
     DI2P_LMCLK(6, tfit0);
     if (fitted) {
-#else
-    if (interpolating_fit(st.cost, st.gd, cur, prev, p)) {
-#endif
         // the minimiser of the interpolant over [1e-3, 0.6] x t is found by the whole wavefront (lm_poly_wave), then lm_trial_next_decide
 #pragma unroll
         for (int j = 0; j < 6; ++j) st.poly[j] = p[j];
@@ -2306,13 +1612,9 @@ __global__ __launch_bounds__(WPH * 64, MINW) void solve_kernel(const SolveArgs<P
         int action = ACT_NONE;
         if (lm_wave_here && lm_lane == 0) {
             const bool ok = sh.comb[NV - 1] == 0.0 && isfinite(sh.comb[0]);
-#ifdef DI2P_SOLVER_LMPROF
-            const long long td0_ = clock64();
-#endif
+            DI2P_LMSTAMP(td0_);
             action = lm_decide<NP>(st, ok, sh.comb[0], sh.comb + 1, sh.comb + 1 + NP);
-#ifdef DI2P_SOLVER_LMPROF
             DI2P_LMCLK(5, td0_);
-#endif
         }
         const long long t2c = PROFILE ? clock64() : 0;
         asm volatile("" ::: "memory");          // the interpolant is read back from LDS by all 64 lanes (not forwarded from lane 0's registers)
@@ -2329,26 +1631,18 @@ __global__ __launch_bounds__(WPH * 64, MINW) void solve_kernel(const SolveArgs<P
         // loads with lm_decide's) they were spilled -- three scratch reloads with a full wait on the lane everybody waits for, four times per sweep
         asm volatile("" ::: "memory");
         if (lm_wave_here && lm_lane == 0) {
-#ifdef DI2P_SOLVER_LMPROF
-            const long long ttn0 = clock64();
-#endif
+            DI2P_LMSTAMP(ttn0);
             if (action == ACT_TRIAL_NEXT) action = lm_trial_next_decide<NP>(st);
-#ifdef DI2P_SOLVER_LMPROF
             DI2P_LMCLK(7, ttn0);
-#endif
             lm_apply<NP>(st, action, sh.comb[0], sh.comb + 1, sh.comb + 1 + NP);
             // the iterate of the NEXT sweep enters the ring of the classification cache (slot = its sweep number % RING)
             const int slot = (st.nsweep - s_base) & (RING - 1);
             double xn[NP];
 #pragma unroll
             for (int i = 0; i < NP; ++i) { xn[i] = st.xe[i]; sh.ring[slot][i] = xn[i]; }
-#ifdef DI2P_SOLVER_LMPROF
-            const long long tr0 = clock64();
-#endif
+            DI2P_LMSTAMP(tr0);
             if (NP == 4 && !st.done) { Rot<NP> r0; make_rot<NP>(xn, r0); sh.rot_cs[0] = r0.R[0]; sh.rot_cs[1] = r0.R[2]; }
-#ifdef DI2P_SOLVER_LMPROF
-            st.pad_ += (int)(clock64() - tr0);
-#endif
+            DI2P_LMADD(st.pad_, tr0);
         }
         const long long t3 = PROFILE ? clock64() : 0;
         c_comb += t2b - t2; c_decide += t2c - t2b; c_poly += t2d - t2c; c_apply += t3 - t2d;
@@ -2662,26 +1956,32 @@ int launch_solve(const PT* points, const int* labels, const double* K, const dou
 
 }  // namespace
 
+// the body of the two solve entry points; `who`: the entry point's name for its error strings (DI2P_CHECK_ARG / DI2P_RETURN_LAUNCH take __func__)
+template <typename PT>
+static int solve_batched_entry(const char* who, const PT* points, const int32_t* labels, const double* K, const double* init_y, const double* init_T,
+                               const double* yaw0, double H, double W, const double* lb_host, const double* ub_host, int max_iter, int is_2d,
+                               int F, int R, int N, double* params, double* cost, int32_t* iters, int32_t* sweeps, void* workspace, void* stream) {
+    const bool ptrs = points && labels && K && init_y && init_T && lb_host && ub_host && params && cost && iters && workspace;
+    if (!ptrs || !(F >= 0 && R >= 0 && N >= 0 && max_iter >= 0)) { di2p_set_error("%s: %s", who, ptrs ? "bad size" : "null pointer"); return -1; }
+    if (F == 0 || R == 0) return 0;
+    launch_solve<PT>(points, labels, K, init_y, init_T, yaw0, H, W, lb_host, ub_host, max_iter, is_2d, F, R, N, params, cost, iters, sweeps, workspace, (hipStream_t)stream);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { di2p_set_error("%s: launch failed: %s", who, hipGetErrorString(e)); return (int)e; }
+    return 0;
+}
+
 extern "C" int di2p_solve_batched(const double* points, const int32_t* labels, const double* K, const double* init_y,
                                   const double* init_T, const double* yaw0, double H, double W, const double* lb_host,
                                   const double* ub_host, int max_iter, int is_2d, int F, int R, int N, double* params,
                                   double* cost, int32_t* iters, int32_t* sweeps, void* workspace, void* stream) {
-    DI2P_CHECK_ARG(points && labels && K && init_y && init_T && lb_host && ub_host && params && cost && iters && workspace, "null pointer");
-    DI2P_CHECK_ARG(F >= 0 && R >= 0 && N >= 0 && max_iter >= 0, "bad size");
-    if (F == 0 || R == 0) return 0;
-    launch_solve<double>(points, labels, K, init_y, init_T, yaw0, H, W, lb_host, ub_host, max_iter, is_2d, F, R, N, params, cost, iters, sweeps, workspace, (hipStream_t)stream);
-    DI2P_RETURN_LAUNCH();
+    return solve_batched_entry(__func__, points, labels, K, init_y, init_T, yaw0, H, W, lb_host, ub_host, max_iter, is_2d, F, R, N, params, cost, iters, sweeps, workspace, stream);
 }
 
 extern "C" int di2p_solve_batched_f32(const float* points, const int32_t* labels, const double* K, const double* init_y,
                                       const double* init_T, const double* yaw0, double H, double W, const double* lb_host,
                                       const double* ub_host, int max_iter, int is_2d, int F, int R, int N, double* params,
                                       double* cost, int32_t* iters, int32_t* sweeps, void* workspace, void* stream) {
-    DI2P_CHECK_ARG(points && labels && K && init_y && init_T && lb_host && ub_host && params && cost && iters && workspace, "null pointer");
-    DI2P_CHECK_ARG(F >= 0 && R >= 0 && N >= 0 && max_iter >= 0, "bad size");
-    if (F == 0 || R == 0) return 0;
-    launch_solve<float>(points, labels, K, init_y, init_T, yaw0, H, W, lb_host, ub_host, max_iter, is_2d, F, R, N, params, cost, iters, sweeps, workspace, (hipStream_t)stream);
-    DI2P_RETURN_LAUNCH();
+    return solve_batched_entry(__func__, points, labels, K, init_y, init_T, yaw0, H, W, lb_host, ub_host, max_iter, is_2d, F, R, N, params, cost, iters, sweeps, workspace, stream);
 }
 
 extern "C" int di2p_select_best(const double* params, const double* cost, const int32_t* has_inside, int is_2d, int F, int R,

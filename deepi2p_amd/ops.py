@@ -833,10 +833,12 @@ def initial_guess(points64, labels):
     return yaw0, labels_out, has_inside
 
 
-def solve_batched(points, labels, K, init_y, init_T, H, W, lb, ub, max_iter, is_2d, yaw0=None, sweeps=None):
+def solve_batched(points, labels, K, init_y, init_T, H, W, lb, ub, max_iter, is_2d, yaw0=None, sweeps=None, workspace=None):
     """points f64|f32 [F,3,N], labels i32[F,N], K f64[F,3,3], init_y f64[F,R], init_T f64[F,R,3]
-    -> params f64[F,R,np], cost f64[F,R], iters i32[F,R]."""
-    require_cuda(points, labels, K, init_y, init_T, yaw0)
+    -> params f64[F,R,np], cost f64[F,R], iters i32[F,R].
+    workspace: caller-owned uint8 tensor of at least di2p_solve_workspace_bytes(F, R, N) bytes on the points' device, used instead of
+    the internal allocation (the C API takes it from the caller anyway; tests read the prepared frames back from it)."""
+    require_cuda(points, labels, K, init_y, init_T, yaw0, workspace)
     _chk(labels, _i32, "labels")
     _chk(K, _f64, "K")
     _chk(init_y, _f64, "init_y")
@@ -850,7 +852,16 @@ def solve_batched(points, labels, K, init_y, init_T, H, W, lb, ub, max_iter, is_
     name = "di2p_solve_batched" if points.dtype == _f64 else "di2p_solve_batched_f32"
     if points.dtype not in (_f64, _f32):
         raise RuntimeError("points must be float64 or float32")
-    ws = torch.empty((_lib.load().di2p_solve_workspace_bytes(F, R, N),), dtype=torch.uint8, device=points.device)
+    need = _lib.load().di2p_solve_workspace_bytes(F, R, N)
+    if workspace is None:
+        ws = torch.empty((need,), dtype=torch.uint8, device=points.device)
+    else:
+        ws = workspace
+        _chk(ws, torch.uint8, "workspace")
+        if ws.device != points.device:
+            raise RuntimeError("workspace must be on the points' device")
+        if ws.numel() < need:
+            raise RuntimeError("workspace has %d bytes, di2p_solve_workspace_bytes(%d, %d, %d) = %d" % (ws.numel(), F, R, N, need))
     call(name, ptr(points), ptr(labels), ptr(K), ptr(init_y), ptr(init_T), ptr(yaw0), float(H), float(W), _dbl3(lb),
          _dbl3(ub), int(max_iter), int(bool(is_2d)), F, R, N, ptr(params), ptr(cost), ptr(iters), ptr(sweeps), ptr(ws), stream())
     return params, cost, iters

@@ -339,7 +339,7 @@ def test_solver_matches_oracle_other_cameras(dev, seed, is_2d, N, HW, flip):
 def test_frame_preparation_sort_paths_agree(dev, scene, N):
     """Frame preparation sorts the records by (label, Hilbert cell, index).  The shipped path is a counting sort into (label, cell) buckets
     followed by a ranking of every key inside its bucket, ONE THREAD PER KEY -- round 6: as five launches of several workgroups per frame
-    (solver.hip prep_*_kernel), round 4: one workgroup per frame (prepare_kernel step 3a, knob solver_prep_single); a frame with a bucket above
+    (solver_prep.h prep_*_kernel), round 4: one workgroup per frame (solver_prep.h prepare_kernel step 3a, knob solver_prep_single); a frame with a bucket above
     4096 keys goes to the bitonic network instead.  Either way the order must be the SAME as the bitonic network's (knob solver_prep_bitonic):
     params, costs, iteration and sweep counts bit-identical.  Scenes: a scan (small buckets), patchy (dense patches: large buckets), collapsed
     (a far outlier stretches the grid so that everything shares a few cells: the fallback), duplicates (equal coordinates, unique keys by
@@ -375,3 +375,125 @@ def test_frame_preparation_sort_paths_agree(dev, scene, N):
     with _lib.option("solver_prep_single", 1):   # the round-4 single-workgroup kernel (counting sort + ranking)
         c = run()
     assert a == c
+
+
+# ---- the PREPARED data of the three frame-preparation paths -----------------------------------------------------------------------------
+def _hilbert10(x, y):
+    """solver_prep.h hilbert10 on uint32 arrays"""
+    x, y = x.astype(np.uint32).copy(), y.astype(np.uint32).copy()
+    d = np.zeros_like(x)
+    s = np.uint32(512)
+    while s > 0:
+        rx, ry = ((x & s) != 0).astype(np.uint32), ((y & s) != 0).astype(np.uint32)
+        d += s * s * ((np.uint32(3) * rx) ^ ry)
+        flip = (ry == 0) & (rx == 1)
+        x, y = np.where(flip, s - 1 - x, x), np.where(flip, s - 1 - y, y)
+        x, y = np.where(ry == 0, y, x), np.where(ry == 0, x, y)
+        s >>= np.uint32(1)
+    return d
+
+
+def _largest_bucket(pts, lab):
+    """Occupancy of the fullest of the 2048 (label, 32 x 32 Hilbert grid) buckets, from the key rule (solver_prep.h prep_frame_of / prep_key):
+    above 4096 the multi-workgroup path flags the frame and hands it to prepare_kernel's bitonic network."""
+    valid = (lab == 0) | (lab == 1)
+    x, z = pts[0].astype(np.float32), pts[2].astype(np.float32)
+    mnx, mnz = x[valid].min(), z[valid].min()
+    ext = np.float32(max(x[valid].max() - mnx, z[valid].max() - mnz))
+    scale = np.float32(1023.0) / ext if 0 < ext < np.inf else np.float32(0)
+    qx, qz = np.clip((x - mnx) * scale, 0, 1023).astype(np.uint32), np.clip((z - mnz) * scale, 0, 1023).astype(np.uint32)
+    bucket = ((lab != 1).astype(np.uint32) << 10) | (_hilbert10(qx, qz) >> 10)
+    return int(np.bincount(bucket[valid], minlength=2048).max())
+
+
+def _prep_case(name):
+    """-> pts f32[F,3,N] (exactly representable in either point type), labels i32[F,N], K f64[F,3,3], yaw / T of R = 2 hypotheses per frame"""
+    frames = []
+    if name == "mixed":            # F = 3, N = 4352 (68 clusters): a scan | one bucket above 4096 keys (flagged: the fallback) | one just under
+        N = 4352
+        for i, m in enumerate((0, 4130, 4040)):
+            f, rng = _frame(950 + i, N)
+            pts, lab = f["pc"].astype(np.float32).copy(), f["labels"].astype(np.int32).copy()
+            pts[0, :m] = 11.0 + rng.uniform(0, 1.0, m); pts[2, :m] = 21.0 + rng.uniform(0, 1.0, m)       # a 1 m patch of equally labelled points
+            lab[:m] = 1
+            frames.append((pts, lab, f, rng))
+    else:                          # F = 2, N = 130: labels 0 / 1 / 2 with partial clusters in both label blocks and a NaN | no label-1 point at all
+        N = 130
+        for i in range(2):
+            f, rng = _frame(960 + i, N)
+            pts, lab = f["pc"].astype(np.float32).copy(), f["labels"].astype(np.int32).copy()
+            lab[::9] = 2
+            if i == 0:
+                lab[1:40] = 1; lab[40:90] = 0
+                pts[0, 3] = np.nan
+            else:
+                lab[lab == 1] = 0
+            frames.append((pts, lab, f, rng))
+    R = 2
+    ys = np.stack([rng.normal(f["yaw_gt"], 0.2, R) for _, _, f, rng in frames])
+    Ts = np.stack([np.stack((np.zeros(R), np.zeros(R), rng.uniform(-5, 5, R)), axis=1) for _, _, f, rng in frames])
+    return (np.stack([p for p, _, _, _ in frames]), np.stack([l for _, l, _, _ in frames]), np.stack([f["K"] for _, _, f, _ in frames]), ys, Ts)
+
+
+def _prepared_regions(dev, case, dtype, knob=None):
+    """Solves `case` into a zero-filled caller-owned workspace and returns its three leading regions as bytes: counts i32[F][4], the records of
+    every frame and the cluster boxes.  The offsets are those of solver.hip solve_ws_layout (every region start rounded up to 256 bytes; the
+    record region is sized for 32-byte records whatever the point type, the frame stride is N + 128 records of the type's own size)."""
+    from deepi2p_amd import _lib, ops
+    pts, lab, K, ys, Ts = case
+    F, _, N = pts.shape
+    R = ys.shape[1]
+    up = lambda v: (v + 255) & ~255
+    rec = 16 if dtype == torch.float32 else 32
+    ncmax = (N + 63) // 64 + 2
+    off_recs = up(F * 4 * 4)
+    off_boxes = up(off_recs + F * (N + 128) * 32)
+    ws = torch.zeros((_lib.load().di2p_solve_workspace_bytes(F, R, N),), dtype=torch.uint8, device=dev)
+    args = (torch.from_numpy(pts).to(dev).to(dtype), torch.from_numpy(lab).to(dev), torch.from_numpy(K).to(dev), torch.from_numpy(ys).to(dev),
+            torch.from_numpy(Ts).to(dev), H, W, LB, UB, 2, True)
+    if knob:
+        with _lib.option(knob, 1):
+            ops.solve_batched(*args, workspace=ws)
+    else:
+        ops.solve_batched(*args, workspace=ws)
+    w = ws.cpu().numpy()
+    return {"counts": w[:F * 16].tobytes(), "records": w[off_recs:off_recs + F * (N + 128) * rec].tobytes(),
+            "boxes": w[off_boxes:off_boxes + F * ncmax * 32].tobytes()}
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64], ids=["f32", "f64"])
+@pytest.mark.parametrize("name", ["mixed", "ragged_nan"])
+def test_prepared_frames_identical_on_every_path(dev, name, dtype):
+    """The PREPARED data -- counts, sorted and padded records, cluster boxes, read back from a caller-owned workspace -- is byte-identical on the
+    three frame-preparation paths (multi-workgroup; solver_prep_single; solver_prep_bitonic), for both point types, in ONE call whose frames
+    take different paths: `mixed` is a batch of a plain scan, a frame with a bucket above 4096 keys (the multi-workgroup path flags it and
+    prepare_kernel prepares it behind its unflagged neighbours) and a frame just under the limit; `ragged_nan` has partial clusters in both label
+    blocks, ignored labels, a frame without a label-1 point, and a NaN coordinate (its box's hx is NaN on every path)."""
+    case = _prep_case(name)
+    pts, lab = case[0], case[1]
+    F, _, N = pts.shape
+    if name == "mixed":            # which path a frame takes, from the key rule alone (no GPU needed)
+        occ = [_largest_bucket(pts[f], lab[f]) for f in range(F)]
+        assert occ[1] > 4096 and occ[0] <= 4096 and occ[2] <= 4096, occ
+    a = _prepared_regions(dev, case, dtype)
+    counts = np.frombuffer(a["counts"], np.int32).reshape(F, 4)
+    np.testing.assert_array_equal(counts[:, 0], (lab == 1).sum(1))
+    np.testing.assert_array_equal(counts[:, 1], (lab == 0).sum(1))
+    np.testing.assert_array_equal(counts[:, 2:], (counts[:, :2] + 63) // 64)
+    if name == "mixed":
+        assert counts[1, 0] >= 4130
+    else:
+        assert counts[0, 0] % 64 and counts[0, 1] % 64 and counts[1, 0] == 0 and (lab[0] == 2).any()
+    b = _prepared_regions(dev, case, dtype, "solver_prep_single")
+    c = _prepared_regions(dev, case, dtype, "solver_prep_bitonic")
+    for region in ("counts", "records", "boxes"):
+        assert a[region] == b[region], "%s: multi-workgroup vs solver_prep_single" % region
+        assert a[region] == c[region], "%s: multi-workgroup vs solver_prep_bitonic" % region
+    if name == "ragged_nan":       # the NaN point's cluster: hx (word 3 of the box) is NaN, the bytes compared above
+        ft = np.float32 if dtype == torch.float32 else np.float64
+        recs = np.frombuffer(a["records"], ft).reshape(F, N + 128, 4)
+        (i,) = np.nonzero(np.isnan(recs[0, :, 0]))
+        assert i.size == 1 and i[0] < counts[0, 0]
+        boxes = np.frombuffer(a["boxes"], np.float32).reshape(F, (N + 63) // 64 + 2, 8)
+        assert np.isnan(boxes[0, i[0] // 64, 3]) and not np.isnan(boxes[0, i[0] // 64, :3]).any()
+        assert np.isnan(boxes).sum() == 1
