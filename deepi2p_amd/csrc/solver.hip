@@ -1423,7 +1423,9 @@ __device__ __forceinline__ int lm_decide(LMState<NP>& st, bool ok, double fe, co
     ++st.nsweep;
     if (st.phase == PH_INIT) {
         st.cost = fe;
-        if (!ok) { st.done = 1; return ACT_NONE; }
+        // evaluation failure at the start: the sums that exist leave out the record that failed (a label-0 record on a frustum plane is flagged
+        // and skipped), so a finite fe is NOT the cost of this pose -- report NaN, as the reference's final evaluation does; never the argmin
+        if (!ok) { st.cost = __builtin_nan(""); st.done = 1; return ACT_NONE; }
 #pragma unroll
         for (int a = 0; a < NP; ++a) { st.g[a] = ge[a]; st.S[a] = 1.0 / (1.0 + sqrt(Ae[a * (a + 1) / 2 + a])); }
 #pragma unroll
@@ -1602,8 +1604,10 @@ __global__ __launch_bounds__(WPH * 64, MINW) void solve_kernel(const SolveArgs<P
             // lane (no divergent branch; lanes > 0 feed it their harmless sums); a non-finite / non-positive product gives NaN, caught below
             const double cost = 0.5 * (ln_pos(i == 0 ? prod : 1.0) + (double)ex * 0.69314718055994530942);
             double t = i == 0 ? cost : sum;
-            // a non-finite Jacobian entry or residual (evaluation failure in the reference) makes a sum non-finite: one vote per sweep
-            const bool nonfinite = __any(lm_lane < NV - 1 && !isfinite(t)) != 0;
+            // a non-finite Jacobian entry or residual (evaluation failure in the reference) makes the cost or a GRADIENT sum non-finite (every
+            // entry of an active row enters J^T r): one vote per sweep.  The normal equations are not in the vote: J^T J can overflow with
+            // every entry finite, which the reference evaluates successfully and then rejects as an invalid step (lm_begin_iteration).
+            const bool nonfinite = __any(lm_lane < 1 + NP && !isfinite(t)) != 0;
             if (lm_lane == NV - 1 && nonfinite) t = 1.0;
             if (lm_lane < NV) sh.comb[lm_lane] = t;
         }

@@ -324,6 +324,8 @@ int di2p_channel_max(const float* x, float* y, int B, int C, int N, void* stream
  *   init_T f64[F,R,3], lb/ub f64[3] HOST arrays, is_2d: 4 params [ry,tx,ty,tz] else 6
  *   [angle-axis, t].  Outputs: params f64[F,R,np], cost f64[F,R], iters i32[F,R], sweeps i32[F,R] (optional).
  *   If yaw0 != NULL it is added to init_y per frame (restart noise drawn before yaw0 is known).
+ *   A hypothesis whose (box-projected) start cannot be evaluated -- a non-finite residual or Jacobian entry -- returns that start with
+ *   iters 0 and cost NaN, which di2p_select_best never selects.
  *   workspace: di2p_solve_workspace_bytes(F, R, N) bytes of scratch (sorted point records, cluster boxes, sort keys,
  *   parked Levenberg-Marquardt states of the two-tier launch).
  * di2p_select_best: argmin cost over R per frame (ties -> lowest r; frames with has_inside==0 get

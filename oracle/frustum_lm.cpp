@@ -258,8 +258,10 @@ inline int real_roots_in(const double* q, int deg, double a, double b, double* r
 }
 
 // LineSearch::InterpolatingPolynomialMinimizingStepSize for CUBIC: lowerbound = (0, f0, g0) always valid.
-inline double interpolating_step(double f0, double g0, const Sample& cur, const Sample& prev, double min_step, double max_step) {
-    if (!cur.value_ok) return std::min(std::max(cur.x * 0.5, min_step), max_step);
+// *bisected (may be NULL) is set when the fit is not used and the step is the clamped bisection instead.
+inline double interpolating_step(double f0, double g0, const Sample& cur, const Sample& prev, double min_step, double max_step, bool* bisected) {
+    if (bisected) *bisected = false;
+    if (!cur.value_ok) { if (bisected) *bisected = true; return std::min(std::max(cur.x * 0.5, min_step), max_step); }
     // polynomial p(u) = f0 + g0 xc u + u^2 r(u), u = x / xc; r has one coefficient per remaining constraint
     const double xc = cur.x, G0 = g0 * xc;
     double M[4][5];
@@ -304,7 +306,7 @@ inline double interpolating_step(double f0, double g0, const Sample& cur, const 
     double p[6] = {f0, G0, 0, 0, 0, 0};
     const int deg = m + 1;
     for (int j = 0; j < m; ++j) p[j + 2] = rc[j];
-    for (int j = 0; j <= deg; ++j) if (!std::isfinite(p[j])) return std::min(std::max(cur.x * 0.5, min_step), max_step);
+    for (int j = 0; j <= deg; ++j) if (!std::isfinite(p[j])) { if (bisected) *bisected = true; return std::min(std::max(cur.x * 0.5, min_step), max_step); }
     // MinimizePolynomial over u in [umin, umax]
     const double umin = min_step / xc, umax = max_step / xc;
     double best_u = 0.5 * (umin + umax), best_v = poly_eval(p, deg, best_u);
@@ -322,10 +324,31 @@ inline double interpolating_step(double f0, double g0, const Sample& cur, const 
     return best_u * xc;
 }
 
+// Which branches a solve took (tests/solver_lm_cases.py declares them per case).  Counting only: no influence on any iterate.
+struct LmStats {
+    int trial_evals;        // sample_at calls: cost + gradient evaluations at line-search trial points
+    int ls_extra;           // ... of them beyond the first trial of their iteration
+    int ls_late_accept;     // Armijo satisfied at a trial other than the first
+    int ls_giveup;          // searches abandoned at 20 trials
+    int ls_min_step;        // searches stopped by tn * dmax < 1e-9
+    int ls_bisect;          // interpolation steps that fell back to the clamped bisection
+    int rejected;           // steps with rel <= min_relative_decrease
+    int invalid;            // Cholesky failure or model_change <= 0
+    int on_bound;           // the final iterate has a translation component on lb / ub
+};
+constexpr int kLmStatsWords = (int)(sizeof(LmStats) / sizeof(int));
+
 enum Term { T_MAX_ITER = 0, T_GRADIENT = 1, T_PARAMETER = 2, T_FUNCTION = 3, T_RADIUS = 4, T_INVALID = 5, T_EVAL_FAIL = 6 };
 
 template <int NP>
-void minimize(const Problem<NP>& P, double* x, int max_iter, int* iters_out, int* term_out, int* n_eval_out) {
+void minimize(const Problem<NP>& P, double* x, int max_iter, int* iters_out, int* term_out, int* n_eval_out, LmStats* stats_out) {
+    LmStats stats;
+    std::memset(&stats, 0, sizeof(stats));
+    auto finish_stats = [&]() {
+        if (!stats_out) return;
+        for (int i = NP - 3; i < NP; ++i) if (x[i] == P.lb[i] || x[i] == P.ub[i]) stats.on_bound = 1;
+        *stats_out = stats;
+    };
     const double kMinDiag = 1e-6, kMaxDiag = 1e32, kMaxRadius = 1e16, kMinRadius = 1e-32;
     const double kMinRelDec = 1e-3, kFuncTol = 1e-6, kGradTol = 1e-10, kParamTol = 1e-8;
     double zero[NP] = {0}, tmp[NP];
@@ -334,7 +357,7 @@ void minimize(const Problem<NP>& P, double* x, int max_iter, int* iters_out, int
     double cost, g[NP], A[NP * NP];
     int n_eval = 1;
     int iter = 0, term = T_MAX_ITER;
-    if (!P.eval(x, &cost, g, A, nullptr)) { *iters_out = 0; *term_out = T_EVAL_FAIL; *n_eval_out = n_eval; return; }
+    if (!P.eval(x, &cost, g, A, nullptr)) { *iters_out = 0; *term_out = T_EVAL_FAIL; *n_eval_out = n_eval; finish_stats(); return; }
     double S[NP];                                                        // Jacobi scaling, fixed at iteration 0
     for (int i = 0; i < NP; ++i) S[i] = 1.0 / (1.0 + std::sqrt(A[i * NP + i]));
     auto grad_max_norm = [&](const double* xx, const double* gg) {       // projected gradient, inf-norm
@@ -369,6 +392,7 @@ void minimize(const Problem<NP>& P, double* x, int max_iter, int* iters_out, int
             valid = model_change > 0.0;
         }
         if (!valid) {
+            ++stats.invalid;
             if (++invalid_run >= 5) { term = T_INVALID; break; }
             radius /= decrease; decrease *= 2.0; reuse_diag = true;
             continue;
@@ -386,7 +410,7 @@ void minimize(const Problem<NP>& P, double* x, int max_iter, int* iters_out, int
                 double d2[NP], xc2[NP], gt[NP], At[NP * NP];
                 for (int a = 0; a < NP; ++a) d2[a] = tt * delta[a];
                 P.plus(x, d2, xc2);
-                ++n_eval;
+                ++n_eval; ++stats.trial_evals;
                 if (!P.eval(xc2, &sm.value, gt, At, nullptr)) return sm;     // non-finite cost OR Jacobian: invalid sample
                 sm.value_ok = true;
                 double gdir = 0.0;
@@ -400,12 +424,16 @@ void minimize(const Problem<NP>& P, double* x, int max_iter, int* iters_out, int
             int ls_it = 0; bool success = false;
             for (;;) {
                 if (cur.value_ok && cur.value <= cost + 1e-4 * gd * cur.x) { success = true; break; }
-                if (++ls_it >= 20) break;
-                const double tn = interpolating_step(cost, gd, cur, prev, 1e-3 * cur.x, 0.6 * cur.x);
-                if (tn * dmax < 1e-9) break;
+                if (++ls_it >= 20) { ++stats.ls_giveup; break; }
+                bool bisected;
+                const double tn = interpolating_step(cost, gd, cur, prev, 1e-3 * cur.x, 0.6 * cur.x, &bisected);
+                if (bisected) ++stats.ls_bisect;
+                if (tn * dmax < 1e-9) { ++stats.ls_min_step; break; }
                 prev = cur;
                 cur = sample_at(tn);
+                ++stats.ls_extra;
             }
+            if (success && ls_it > 0) ++stats.ls_late_accept;
             if (success && cur.x != 1.0) for (int a = 0; a < NP; ++a) delta[a] *= cur.x;
         }
         double xc[NP], cand_cost;
@@ -426,10 +454,12 @@ void minimize(const Problem<NP>& P, double* x, int max_iter, int* iters_out, int
             radius = std::min(kMaxRadius, radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * rel - 1.0, 3)));
             decrease = 2.0; reuse_diag = false;
         } else {
+            ++stats.rejected;
             radius /= decrease; decrease *= 2.0; reuse_diag = true;
         }
     }
     *iters_out = iter; *term_out = term; *n_eval_out = n_eval;
+    finish_stats();
 }
 
 void angle_axis_to_R(const double w[3], double R[9]) {     // ceres::AngleAxisToRotationMatrix, row-major out
@@ -447,7 +477,7 @@ void angle_axis_to_R(const double w[3], double R[9]) {     // ceres::AngleAxisTo
 template <int NP>
 int solve_impl(const double* pts, const int* labels, int N, const double K[9], double init_y, const double init_T[3],
                double H, double W, const double lb[3], const double ub[3], int max_iter,
-               double P_out[16], double* final_cost, double* residuals, int* n_res, int* iters, int* term, double* params_out) {
+               double P_out[16], double* final_cost, double* residuals, int* n_res, int* iters, int* term, double* params_out, LmStats* stats) {
     Problem<NP> P;
     P.pts = pts; P.labels = labels; P.N = N;
     P.k = Camera{K[0], K[4], K[2], K[5], H - 1.0, W - 1.0};          // registration.cpp:21-22,79-82
@@ -458,7 +488,7 @@ int solve_impl(const double* pts, const int* labels, int N, const double K[9], d
     if (NP == 4) { x[0] = init_y; } else { x[0] = 0.0; x[1] = init_y; x[2] = 0.0; }   // :34-50
     for (int i = 0; i < 3; ++i) x[toff + i] = init_T[i];
     int it = 0, tm = 0, ne = 0;
-    minimize<NP>(P, x, max_iter, &it, &tm, &ne);
+    minimize<NP>(P, x, max_iter, &it, &tm, &ne, stats);
     std::vector<double> res;
     double c = 0.0;
     P.eval(x, &c, nullptr, nullptr, residuals ? &res : nullptr);       // Problem::Evaluate (:150-155)
@@ -482,14 +512,26 @@ int solve_impl(const double* pts, const int* labels, int N, const double K[9], d
 
 extern "C" {
 
+// One solvePGivenK call, also reporting the branches it took: stats (may be NULL) receives the oracle_lm_stats_words() ints of LmStats.
+int oracle_solve_p_given_k_stats(const double* points, const int* labels, int N, const double* K, double init_y_angle,
+                                 const double* init_T, double H, double W, const double* lb, const double* ub, int max_iter,
+                                 int is_2d, double* P_out, double* final_cost, double* residuals, int* n_res, int* iters,
+                                 int* term, double* params_out, int* stats) {
+    LmStats* sp = reinterpret_cast<LmStats*>(stats);
+    if (is_2d) return solve_impl<4>(points, labels, N, K, init_y_angle, init_T, H, W, lb, ub, max_iter, P_out, final_cost, residuals, n_res, iters, term, params_out, sp);
+    return solve_impl<6>(points, labels, N, K, init_y_angle, init_T, H, W, lb, ub, max_iter, P_out, final_cost, residuals, n_res, iters, term, params_out, sp);
+}
+
+int oracle_lm_stats_words() { return kLmStatsWords; }
+
 // One solvePGivenK call.  points: 3 x N row-major f64; labels i32[N]; K row-major 3x3.
 // residuals may be NULL; otherwise must hold 3*N_in + N_out doubles.  Returns #cost evaluations.
 int oracle_solve_p_given_k(const double* points, const int* labels, int N, const double* K, double init_y_angle,
                            const double* init_T, double H, double W, const double* lb, const double* ub, int max_iter,
                            int is_2d, double* P_out, double* final_cost, double* residuals, int* n_res, int* iters,
                            int* term, double* params_out) {
-    if (is_2d) return solve_impl<4>(points, labels, N, K, init_y_angle, init_T, H, W, lb, ub, max_iter, P_out, final_cost, residuals, n_res, iters, term, params_out);
-    return solve_impl<6>(points, labels, N, K, init_y_angle, init_T, H, W, lb, ub, max_iter, P_out, final_cost, residuals, n_res, iters, term, params_out);
+    return oracle_solve_p_given_k_stats(points, labels, N, K, init_y_angle, init_T, H, W, lb, ub, max_iter, is_2d, P_out, final_cost,
+                                        residuals, n_res, iters, term, params_out, nullptr);
 }
 
 // Diagnostics: the same solve, also returning the points every cost + gradient evaluation was made at (trace: cap x (4|6) doubles).
@@ -510,20 +552,30 @@ int oracle_solve_trace(const double* points, const int* labels, int N, const dou
 
 // R independent restarts of one frame spread over nthreads std::threads (mirrors the reference's
 // waves of OS processes, evaluation/registration_lsq.py:142-186).  init_T: R x 3.
-void oracle_solve_restarts(const double* points, const int* labels, int N, const double* K, int R,
-                           const double* init_y_angles, const double* init_Ts, double H, double W, const double* lb,
-                           const double* ub, int max_iter, int is_2d, int nthreads, double* P_out /*R x 16*/,
-                           double* costs /*R*/, int* iters /*R*/, int* terms /*R*/, double* params /*R x (4|6)*/) {
+// stats (may be NULL): R x oracle_lm_stats_words() ints, the LmStats of every restart.
+void oracle_solve_restarts_stats(const double* points, const int* labels, int N, const double* K, int R,
+                                 const double* init_y_angles, const double* init_Ts, double H, double W, const double* lb,
+                                 const double* ub, int max_iter, int is_2d, int nthreads, double* P_out /*R x 16*/,
+                                 double* costs /*R*/, int* iters /*R*/, int* terms /*R*/, double* params /*R x (4|6)*/, int* stats) {
     const int np = is_2d ? 4 : 6;
     auto work = [&](int t) {
         for (int r = t; r < R; r += nthreads)
-            oracle_solve_p_given_k(points, labels, N, K, init_y_angles[r], init_Ts + 3 * r, H, W, lb, ub, max_iter, is_2d,
-                                   P_out + 16 * r, costs + r, nullptr, nullptr, iters + r, terms + r, params + np * r);
+            oracle_solve_p_given_k_stats(points, labels, N, K, init_y_angles[r], init_Ts + 3 * r, H, W, lb, ub, max_iter, is_2d,
+                                         P_out + 16 * r, costs + r, nullptr, nullptr, iters + r, terms + r, params + np * r,
+                                         stats ? stats + kLmStatsWords * r : nullptr);
     };
     if (nthreads <= 1) { work(0); return; }
     std::vector<std::thread> th;
     for (int t = 0; t < nthreads; ++t) th.emplace_back(work, t);
     for (auto& t : th) t.join();
+}
+
+void oracle_solve_restarts(const double* points, const int* labels, int N, const double* K, int R,
+                           const double* init_y_angles, const double* init_Ts, double H, double W, const double* lb,
+                           const double* ub, int max_iter, int is_2d, int nthreads, double* P_out /*R x 16*/,
+                           double* costs /*R*/, int* iters /*R*/, int* terms /*R*/, double* params /*R x (4|6)*/) {
+    oracle_solve_restarts_stats(points, labels, N, K, R, init_y_angles, init_Ts, H, W, lb, ub, max_iter, is_2d, nthreads, P_out, costs, iters,
+                                terms, params, nullptr);
 }
 
 // Residuals (UNcorrected), Jacobian (row-major n_res x np, may be NULL), corrected cost at given params.

@@ -97,6 +97,32 @@ def test_solver_matches_oracle_per_hypothesis(dev, is_2d, N, R):
     assert np.all(par_g[:, toff:] >= np.array(LB) - 1e-12) and np.all(par_g[:, toff:] <= np.array(UB) + 1e-12)
 
 
+@pytest.mark.parametrize("is_2d,N,R", [(True, 4096, 24), (False, 2048, 12)])
+def test_solver_f32_matches_oracle_per_hypothesis(dev, is_2d, N, R):
+    """The same two rows through the float32 record path (di2p_solve_batched_f32: what the pipeline and the benchmark run), the oracle fed the
+    points rounded to float32: same statement as above, hypothesis by hypothesis."""
+    from deepi2p_amd import ops
+    f, rng = _frame(3 if is_2d else 4, N)
+    pts, lab = f["pc"].astype(np.float64), f["labels"]
+    _, y0, pcf, labf = flm.get_initial_guess(pts, lab)
+    ys, Ts = flm.draw_restarts(rng, R, y0, 10 * math.pi / 180, 10)
+    pc32 = np.ascontiguousarray(pcf.astype(np.float32))
+    Po, co, it_o, term_o, par_o = flm.solve_restarts(pc32.astype(np.float64), labf, f["K"], ys, Ts, H, W, LB, UB, 500, is_2d, nthreads=8)
+    params, cost, iters = ops.solve_batched(torch.from_numpy(pc32).to(dev).unsqueeze(0), torch.from_numpy(np.ascontiguousarray(labf.astype(np.int32))).to(dev).unsqueeze(0),
+                                            torch.from_numpy(np.ascontiguousarray(f["K"])).to(dev).view(1, 3, 3), torch.from_numpy(np.ascontiguousarray(ys)).to(dev).view(1, R),
+                                            torch.from_numpy(np.ascontiguousarray(Ts)).to(dev).view(1, R, 3), H, W, LB, UB, 500, is_2d)
+    _, P, _ = ops.select_best(params.view(R, 1, -1), cost.view(R, 1), is_2d)
+    Pg, cg, par_g, it_g = P.cpu().numpy(), cost.view(-1).cpu().numpy(), params[0].cpu().numpy(), iters.view(-1).cpu().numpy()
+    ok = _agreement(par_o, par_g, is_2d)
+    _check_forks(("per_hypothesis_f32", is_2d, N, R), ok)
+    np.testing.assert_allclose(cg[ok], co[ok], rtol=1e-6)
+    assert abs(cg.min() - co.min()) <= 1e-6 * co.min()
+    np.testing.assert_allclose(Pg[ok], Po[ok], atol=2e-3)
+    np.testing.assert_array_equal(it_g[ok], it_o[ok])
+    toff = 1 if is_2d else 3
+    assert np.all(par_g[:, toff:] >= np.array(LB) - 1e-12) and np.all(par_g[:, toff:] <= np.array(UB) + 1e-12)
+
+
 @pytest.mark.parametrize("is_2d,use_f32", [(True, True), (True, False), (False, False)])
 def test_cluster_culling_is_exact(dev, is_2d, use_f32):
     """The frustum-plane test of whole 64-point clusters must never change a result: with DI2P_SOLVER_NOCULL=1 every
