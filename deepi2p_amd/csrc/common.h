@@ -42,7 +42,7 @@ static inline int di2p_cdiv(long long a, long long b) { return (int)((a + b - 1)
     X(SOLVER_NOPREFILTER, "solver_noprefilter", "DI2P_SOLVER_NOPREFILTER", 0)     /* 1: skip the fp32 pre-filter of the per-point classification (bit-identical by construction) */ \
     X(SOLVER_TIER_SWEEPS, "solver_tier_sweeps", "DI2P_SOLVER_TIER_SWEEPS", 0)     /* sweeps after which a hypothesis is handed to the wide (16-wave) tail kernel; 0 = never */ \
     X(WINO_COB, "wino_cob", "DI2P_WINO_COB", 0)                                   /* 32 / 64: force the output-channel block of the Winograd convolution (0: by grid size) */ \
-    X(CONV_NOWINOGRAD, "conv_nowinograd", "DI2P_CONV_NOWINOGRAD", 0)              /* 1: the host layer runs 3x3 stride-1 convolutions on the direct implicit-GEMM kernel (read by networks.py) */ \
+    X(CONV_NOWINOGRAD, "conv_nowinograd", "DI2P_CONV_NOWINOGRAD", 0)              /* 1: the inference network runs 3x3 stride-1 convolutions on the direct implicit-GEMM kernel, not on Winograd (read by ops.conv_route; the training step does not read it) */ \
     X(WINO_KC, "wino_kc", "DI2P_WINO_KC", 0)                                      /* 8 / 4: input channels per K-step of the Winograd convolution (0: 4 up to 256 input channels, else 8) */ \
     X(CONV_NOSTEM, "conv_nostem", "DI2P_CONV_NOSTEM", 0)                          /* 1: the host layer runs the 7x7 stem on the generic implicit-GEMM kernel (read by networks.py) */ \
     X(WINO_REG, "wino_reg", "DI2P_WINO_REG", 0)                                   /* Winograd kernel: 0 automatic, 1 LDS-panel kernel, 2 register-resident (4 waves), 3 register-resident (2 waves) */ \
@@ -53,7 +53,7 @@ static inline int di2p_cdiv(long long a, long long b) { return (int)((a + b - 1)
     X(PW_NOCHAIN, "pw_nochain", "DI2P_PW_NOCHAIN", 0)                             /* 1: the host layer runs the narrow PointNet chains as separate launches instead of di2p_point_chain (bit-identical; read by ops.py) */ \
     X(HEAD_REG, "head_reg", "DI2P_HEAD_REG", 0)                                   /* 1: di2p_point_head runs the wave-autonomous kernel (one persistent 8-wave workgroup per compute unit: faster alone, slower beside other streams' kernels) instead of the LDS-tile kernel (bit-identical) */ \
     X(CONV_S2SCALAR, "conv_s2scalar", "DI2P_CONV_S2SCALAR", 0)                    /* 1: stride-2 convolutions stage their operand with four dword loads per row (rounds 1-3) instead of aligned 8-float windows (bit-identical) */ \
-    X(CONV_X3, "conv_x3", "DI2P_CONV_X3", 31)                                     /* bit mask of the 3x3 layers the host layer runs on di2p_conv3x3_x3 where it supports their shape (bf16 MFMA, exact three-way splits): bit s-1 = stride-1 layers of ResNet stage s, bit 4 = the stride-2 layers with their 1x1 downsample branch; 0: Winograd / direct fp32-MFMA kernels only (read by networks.py) */ \
+    X(CONV_X3, "conv_x3", "DI2P_CONV_X3", 31)                                     /* bit mask of the 3x3 layers the host layer runs on di2p_conv3x3_x3 where it supports their shape (bf16 MFMA, exact three-way splits): bit s-1 = stride-1 layers of ResNet stage s, bit 4 = the stride-2 layers with their 1x1 downsample branch; 0: Winograd / direct fp32-MFMA kernels only (read by ops.conv_route, for inference and training alike) */ \
     X(CONV_X3_CFG, "conv_x3_cfg", "DI2P_CONV_X3_CFG", -1)                         /* >= 0: force tile configuration 0..3 of di2p_conv3x3_x3 where the call passes cfg = -1 (default -1: cheapest by a cost model) */ \
     X(HEAD_X3, "head_x3", "DI2P_HEAD_X3", 1)                                      /* 1 (default): the host layer runs the coarse per-point head on di2p_point_head_x3 (bf16 MFMA, exact three-way splits, wave-autonomous); 0: di2p_point_head (fp32 MFMA, LDS tile; bit-identical to the three separate launches) (read by networks.py) */ \
     X(HEAD_X3_TAB, "head_x3_tab", "DI2P_HEAD_X3_TAB", 1)                          /* 1 (default): di2p_point_head_x3 keeps the frame's two node tables in LDS, one workgroup of eight waves (two per SIMD, 256 registers) per compute unit; 2: the same with four waves (one per SIMD, 512 registers); 0: gathers the tables from memory (no LDS: shares its compute units) */ \

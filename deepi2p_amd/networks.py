@@ -287,6 +287,23 @@ class PCEncoder(_PackedModule):
 
 
 # ------------------------------------------------------------------ image encoder
+def _block_conv3x3(blk, n, x, stride, residual=None):
+    """Layer conv<n> (+ folded BatchNorm + residual + ReLU) of a packed BasicBlock on the kernel ops.conv_route names, from the operand _pack derived
+    for that kernel.  -> (y, None); a stride-2 layer on the bf16x3 kernel comes with the block's 1x1 downsample branch out of the same
+    launch: (y, identity)."""
+    Wt, sc, sh, _ = blk["c" + n]
+    Cout = Wt.shape[1]
+    kernel, cfg = ops.conv_route(x.shape, (Cout, x.shape[1], 3, 3), stride, 1)
+    if kernel == "x3" and stride == 2:
+        _, sd_, shd, _ = blk["ds"]
+        return ops.conv3x3_x3(x, blk["X" + n], Cout, sc, sh, 2, True, downsample=(blk["Xd"], sd_, shd), cfg=cfg)
+    if kernel == "x3":
+        return ops.conv3x3_x3(x, blk["X" + n], Cout, sc, sh, 1, True, residual=residual, cfg=cfg), None
+    if kernel == "winograd":
+        return ops.conv3x3_winograd(x, blk["U" + n], sc, sh, True, residual=residual), None
+    return ops.conv2d(x, Wt, sc, sh, 3, 3, stride, 1, True, residual=residual, tap_major=True), None       # (every 3x3 layer has Cin % 16 == 0)
+
+
 class ImageEncoder(_PackedModule):
     LAYERS = (3, 4, 6, 3)
 
@@ -351,38 +368,14 @@ class ImageEncoder(_PackedModule):
                 x = ops.conv2d(x, Wt, sc, sh, 7, 7, 2, 3, True)
             x = ops.maxpool3x3s2(x)
         stage_out = {}
-        wino = not _lib.get_option("conv_nowinograd")
-        # bit s-1: the stride-1 layers of stage s, bit 4: the stride-2 layers (+ their 1x1 downsample branch) on di2p_conv3x3_x3
-        x3_mask = _lib.get_option("conv_x3")
         for blk in p["blocks"]:
-            identity = x
-            Wt, sc, sh, _ = blk["c1"]
-            Cout, stride = Wt.shape[1], blk["stride"]
-            x3_bit = 16 if stride == 2 else 1 << (blk["stage"] - 1)
-            y = None
-            if (x3_mask & x3_bit) and "X1" in blk and (stride == 1 or "Xd" in blk) and ops.conv3x3_x3_supported(x.shape, Cout, stride):
-                if stride == 2:
-                    Wd, sd_, shd, _ = blk["ds"]
-                    y, identity = ops.conv3x3_x3(x, blk["X1"], Cout, sc, sh, 2, True, downsample=(blk["Xd"], sd_, shd))
-                else:
-                    y = ops.conv3x3_x3(x, blk["X1"], Cout, sc, sh, 1, True)
-            if y is None:
-                wino_ok = wino and x.shape[3] % 2 == 0 and x.shape[3] >= 4       # the kernel wants an even width (else: direct kernel)
-                if wino_ok and "U1" in blk:
-                    y = ops.conv3x3_winograd(x, blk["U1"], sc, sh, True)
-                else:
-                    y = ops.conv2d(x, Wt, sc, sh, 3, 3, stride, 1, True, tap_major=True)
+            y, identity = _block_conv3x3(blk, "1", x, blk["stride"])
+            if identity is None:
+                identity = x
                 if "ds" in blk:
                     Wd, sd_, shd, _ = blk["ds"]
-                    identity = ops.conv2d(x, Wd, sd_, shd, 1, 1, stride, 0, False, tap_major=True)
-            Wt, sc, sh, _ = blk["c2"]
-            x3_bit = 1 << (blk["stage"] - 1)
-            if (x3_mask & x3_bit) and "X2" in blk and ops.conv3x3_x3_supported(y.shape, Cout, 1):
-                x = ops.conv3x3_x3(y, blk["X2"], Cout, sc, sh, 1, True, residual=identity)
-            elif wino and "U2" in blk and y.shape[3] % 2 == 0 and y.shape[3] >= 4:
-                x = ops.conv3x3_winograd(y, blk["U2"], sc, sh, True, residual=identity)
-            else:
-                x = ops.conv2d(y, Wt, sc, sh, 3, 3, 1, 1, True, residual=identity, tap_major=True)
+                    identity = ops.conv2d(x, Wd, sd_, shd, 1, 1, blk["stride"], 0, False, tap_major=True)
+            x, _ = _block_conv3x3(blk, "2", y, 1, identity)
             if blk["last_of_stage"]:
                 stage_out[blk["stage"]] = x
         return stage_out[3], stage_out[4], ops.global_avgpool(stage_out[4])

@@ -22,6 +22,12 @@ def _chk(t, dtype, name):
         raise RuntimeError("%s must be %s, got %s" % (name, dtype, t.dtype))
 
 
+def _work(name, macs):
+    """Add `macs` multiply-accumulates to the executed-work counter of entry point `name` (_lib.WORK; bench.py switches it on)."""
+    if _lib.WORK is not None:
+        _lib.WORK[name] = _lib.WORK.get(name, 0) + macs
+
+
 # ------------------------------------------------------------------------------------ native ops
 def index_max(data, index, K, return_values=False, mask=None):
     """data f32[B,C,N], index i32[B,N] -> max_idx i32[B,C,K] (and masked max values if asked)."""
@@ -418,15 +424,13 @@ def pointwise_gemm(srcs, Wt, M, N, scale=None, shift=None, batch_bias=None, relu
         Y = torch.empty((B, Nout, M) if transpose_out else (B, M, Nout), dtype=_f32, device=Wt.device)
         y_ptr = ptr(Y)
     if Wp is not None:
-        if _lib.WORK is not None:
-            _lib.WORK["di2p_pointwise_gemm_x3"] = _lib.WORK.get("di2p_pointwise_gemm_x3", 0) + B * M * K * N
+        _work("di2p_pointwise_gemm_x3", B * M * K * N)
         if from_planes:
             call("di2p_pointwise_gemm_x3p", ptr(srcs[0].t), ptr(Wp), y_ptr, B, M, K, N, ctypes.byref(e), stream())
         else:
             call("di2p_pointwise_gemm_x3", arr, len(srcs), ptr(Wp), y_ptr, B, M, K, N, ctypes.byref(e), stream())
         return (Y, Ymax) if Ymax is not None else Y
-    if _lib.WORK is not None:
-        _lib.WORK["di2p_pointwise_gemm"] = _lib.WORK.get("di2p_pointwise_gemm", 0) + B * M * K * N
+    _work("di2p_pointwise_gemm", B * M * K * N)
     call("di2p_pointwise_gemm", arr, len(srcs), ptr(Wt), ptr(Y), B, M, K, N, ctypes.byref(e), stream())
     return (Y, Ymax) if Ymax is not None else Y
 
@@ -445,8 +449,7 @@ def point_head(srcs, layer0, layer1, layer2, N, batch_bias=None, gathered=None):
     e.relu, e.group_max, e.transpose_out = int(bool(act0)), 1, 0
     _fill_gathered(e, gathered, B, M, N)
     out = torch.empty((B, P, N), dtype=_f32, device=Wt0.device)
-    if _lib.WORK is not None:
-        _lib.WORK["di2p_point_head"] = _lib.WORK.get("di2p_point_head", 0) + B * N * (Wt0.shape[0] * M + M * M + M * P)
+    _work("di2p_point_head", B * N * (Wt0.shape[0] * M + M * M + M * P))
     call("di2p_point_head", _fill_srcs(srcs), len(srcs), ptr(Wt0), Wt0.shape[0], ctypes.byref(e), ptr(Wt1), ptr(sc1), ptr(sh1),
          int(bool(act1)), ptr(Wt2), ptr(sc2), ptr(sh2), int(bool(act2)), ptr(out), B, M, P, N, stream())
     return out
@@ -500,8 +503,7 @@ def point_head_x3(src0, src1, packed, gathered, N):
     h.relu0, h.relu1, h.relu2, h.P = int(bool(packed["relu0"])), int(bool(packed["relu1"])), int(bool(packed["relu2"])), P
     h.W2t, h.scale2, h.shift2 = ptr(packed["W2t"]), ptr(packed["sc2"]), ptr(packed["sh2"])
     out = torch.empty((B, P, N), dtype=_f32, device=src0.device)
-    if _lib.WORK is not None:
-        _lib.WORK["di2p_point_head_x3"] = _lib.WORK.get("di2p_point_head_x3", 0) + B * N * ((src0.shape[1] + src1.shape[1]) * 128 + 128 * 128 + 128 * P)
+    _work("di2p_point_head_x3", B * N * ((src0.shape[1] + src1.shape[1]) * 128 + 128 * 128 + 128 * P))
     call("di2p_point_head_x3", ctypes.byref(h), ptr(out), B, N, stream())
     return out
 
@@ -553,8 +555,7 @@ def point_head_labels(y0, packed, N, scores_out=None):
     coarse = torch.empty((B, N), dtype=_i32, device=y0.device)
     fine = torch.empty((B, N), dtype=_i32, device=y0.device)
     h.scores, h.coarse, h.fine = ptr(scores_out), ptr(coarse), ptr(fine)
-    if _lib.WORK is not None:
-        _lib.WORK["di2p_point_head_labels_x3"] = _lib.WORK.get("di2p_point_head_labels_x3", 0) + B * N * 256 * (256 + P)
+    _work("di2p_point_head_labels_x3", B * N * 256 * (256 + P))
     call("di2p_point_head_labels_x3", ctypes.byref(h), B, N, stream())
     return coarse, fine
 
@@ -586,8 +587,7 @@ def point_chain(srcs, layers, N, batch_bias=None, gathered=None):
     e.relu, e.group_max, e.transpose_out = int(bool(act0)), 1, 0
     _fill_gathered(e, gathered, B, M, N)
     out = torch.empty((B, M, N), dtype=_f32, device=Wt0.device)
-    if _lib.WORK is not None:
-        _lib.WORK["di2p_point_chain"] = _lib.WORK.get("di2p_point_chain", 0) + B * N * (Wt0.shape[0] * M + (len(layers) - 1) * M * M)
+    _work("di2p_point_chain", B * N * (Wt0.shape[0] * M + (len(layers) - 1) * M * M))
     call("di2p_point_chain", _fill_srcs(srcs), len(srcs), ptr(Wt0), Wt0.shape[0], ctypes.byref(e), ptr(Wt1), ptr(sc1), ptr(sh1),
          int(bool(act1)), ptr(Wt2), ptr(sc2), ptr(sh2), int(bool(act2)), ptr(out), B, M, N, stream())
     return out
@@ -623,12 +623,66 @@ def attention_pool(feat, score):
     return out
 
 
-def conv2d(x, Wt, scale, shift, KH, KW, stride, pad, relu, residual=None, tap_major=False):
-    require_cuda(x, Wt, scale, shift, residual)
+def _conv_operands(who, x, Cout, KH, KW, stride, pad, scale, shift, residual):
+    """The operand checks the convolution wrappers share -- the kernels read through raw pointers, so a short scale / shift or a smaller
+    residual would be read out of bounds: x f32[B,Cin,H,W], scale / shift f32 with at least Cout values, residual (if any) f32 of exactly
+    the output shape.  -> (B, Cin, H, W, OH, OW); the caller checks its weight operand against Cin."""
+    _chk(x, _f32, who + " input")
+    if x.dim() != 4:
+        raise RuntimeError("%s takes x f32[B,Cin,H,W]" % who)
     B, Cin, H, W = x.shape
-    Cout = Wt.shape[1]
-    OH = (H + 2 * pad - KH) // stride + 1
-    OW = (W + 2 * pad - KW) // stride + 1
+    OH, OW = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
+    for name, v in (("scale", scale), ("shift", shift)):
+        if v is None or v.dtype != _f32:
+            raise RuntimeError("%s %s must be %s, got %s" % (who, name, _f32, None if v is None else v.dtype))
+        if v.numel() < Cout:
+            raise RuntimeError("%s: %s holds %d values, needs %d" % (who, name, v.numel(), Cout))
+    if residual is not None:
+        _chk(residual, _f32, who + " residual")
+        if residual.shape != (B, Cout, OH, OW):
+            raise RuntimeError("%s: residual must be f32%s, got %s" % (who, (B, Cout, OH, OW), tuple(residual.shape)))
+    return B, Cin, H, W, OH, OW
+
+
+def conv_route(x_shape, w_shape, stride, pad, training=False):
+    """Which kernel runs the convolution layer x f32[B,Cin,H,W] * W f32[Cout,Cin,KH,KW]: -> (kernel, cfg), THE statement of the rule for the
+    inference network (networks.ImageEncoder), the training step and its input gradient (train_net._Conv2d; the gradient of a stride-1 "same"
+    layer is the route of dY with Cin and Cout swapped) and the tests.  A function of the shapes and the library knobs only (host code).
+      "x3"         conv3x3_x3 (bf16x3): 3x3 / pad 1, Cin % 16 == 0, the layer's bit of the knob `conv_x3` (bit 4: stride 2; else bit 0..3 for
+                   Cout 64 / 128 / 256 / 512 and beyond -- ResNet stage 1..4) and a kernel instance for the shape.  cfg: the tile configuration
+                   to pass (-1: the library's choice, which the knob `conv_x3_cfg` overrides).  Inference: stride 2 too (the caller fuses the
+                   block's 1x1 downsample branch into the launch).  Training: stride 1, from 16 frames on every such layer, below (the
+                   reference's batch of 8) only Cout >= 256 -- the workgroup tiles are sized for whole rounds of the chip at 32 frames; at 8
+                   frames the Winograd kernel's smaller tiles win on the two large-image stages (tools/bench_conv_x3.py, B=8: 30.8 / 38.7 us
+                   against 29.2 / 42.7) and lose on the small-image ones (48.2 / 73.2 against 29.2 / 46.0 us with the smallest tile
+                   configuration, cfg = 3, which the route then names where it runs the shape and the knob forces none)
+      "winograd"   conv3x3_winograd: 3x3 / stride 1 / pad 1, Cin % 16 == 0, Cout % 32 == 0, an even width of at least 4.  The knob
+                   `conv_nowinograd` takes it away from INFERENCE only: the training step has never read that knob
+      "direct_tap" conv2d on the tap-major matrix (16-byte staged): any other layer with Cin % 16 == 0
+      "direct"     conv2d on the plain matrix: the rest (the 7x7 stem in training)
+    cfg is None for every kernel but "x3"."""
+    B, Cin, H, W = x_shape
+    Cout, _, KH, KW = w_shape
+    if KH == KW == 3 and pad == 1 and Cin % 16 == 0 and stride in (1, 2):
+        bit = 4 if stride == 2 else max(0, min(3, int(Cout).bit_length() - 7))
+        wanted = not training or (stride == 1 and (B >= 16 or Cout >= 256))
+        if wanted and _lib.get_option("conv_x3") >> bit & 1 and conv3x3_x3_supported(x_shape, Cout, stride):
+            small = training and B < 16 and _lib.get_option("conv_x3_cfg") < 0 and conv3x3_x3_supported(x_shape, Cout, stride, cfg=3)
+            return "x3", 3 if small else -1
+        if stride == 1 and Cout % 32 == 0 and W % 2 == 0 and W >= 4 and (training or not _lib.get_option("conv_nowinograd")):
+            return "winograd", None
+    return ("direct_tap" if Cin % 16 == 0 else "direct"), None
+
+
+def conv2d(x, Wt, scale, shift, KH, KW, stride, pad, relu, residual=None, tap_major=False):
+    """y = relu?(scale * conv(x) + shift + residual) on the implicit-GEMM kernels (di2p_conv2d); Wt f32[KH*KW*Cin, Cout], rows ordered
+    (ci,kh,kw) or, tap_major, (kh,kw,ci)."""
+    require_cuda(x, Wt, scale, shift, residual)
+    _chk(Wt, _f32, "conv2d Wt")
+    Cout = Wt.shape[-1]
+    B, Cin, H, W, OH, OW = _conv_operands("conv2d", x, Cout, KH, KW, stride, pad, scale, shift, residual)
+    if tuple(Wt.shape) != (KH * KW * Cin, Cout):
+        raise RuntimeError("conv2d: Wt must be f32[KH*KW*Cin, Cout] = [%d, %d], got %s" % (KH * KW * Cin, Cout, tuple(Wt.shape)))
     y = torch.empty((B, Cout, OH, OW), dtype=_f32, device=x.device)
     args = (ptr(x), ptr(Wt), ptr(scale), ptr(shift), ptr(residual), ptr(y), B, Cin, H, W, Cout, KH, KW,
             stride, pad, int(bool(relu)), int(bool(tap_major)))
@@ -644,8 +698,8 @@ def conv2d(x, Wt, scale, shift, KH, KW, stride, pad, relu, residual=None, tap_ma
 def conv3x3_x3_supported(x_shape, Cout, stride, cfg=-1):
     """True if di2p_conv3x3_x3 has a kernel instance for this layer shape (x_shape = (B, Cin, H, W)) in tile configuration cfg (0..3;
     -1: the knob conv_x3_cfg, by default the cheapest)."""
-    B, Cin, H, W = (int(v) for v in x_shape)
-    return bool(_lib.load().di2p_conv3x3_x3_supported(B, Cin, H, W, int(Cout), int(stride), int(cfg)))
+    B, Cin, H, W = x_shape
+    return bool(_lib.load().di2p_conv3x3_x3_supported(int(B), int(Cin), int(H), int(W), int(Cout), int(stride), int(cfg)))
 
 
 CONV_X3_PLAN_FIELDS = ("cfg", "instance", "instances", "fallback", "dbuf", "plan_items", "instance_items", "pwt", "tiles_per_frame", "n_mt",
@@ -670,23 +724,11 @@ def conv3x3_x3(x, Wp, Cout, scale, shift, stride, relu, residual=None, downsampl
     downsample = (Wp_ds, scale_ds, shift_ds) -- the BasicBlock's 1x1 / stride-2 branch of the same input (resnet.py:160-164) -- and
     returns (y, y_ds).  cfg: the tile configuration, as for conv3x3_x3_supported."""
     require_cuda(x, Wp, scale, shift, residual)
-    _chk(x, _f32, "conv3x3_x3 input")
-    if x.dim() != 4:
-        raise RuntimeError("conv3x3_x3 takes x f32[B,Cin,H,W]")
-    B, Cin, H, W = x.shape
-    OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
-    # the kernel reads the operands through raw pointers: a pack made for another layer shape or a smaller residual would be read out of bounds
+    B, Cin, H, W, OH, OW = _conv_operands("conv3x3_x3", x, Cout, 3, 3, stride, 1, scale, shift, residual)
+    # a pack made for another layer shape would be read out of bounds like a short scale or a smaller residual
     packed_bytes = _lib.load().di2p_bf16x3_packed_bytes
     if Wp.numel() * Wp.element_size() != packed_bytes(9 * Cin, int(Cout)):
         raise RuntimeError("conv3x3_x3: Wp is not bf16x3_pack of a [9*%d, %d] matrix (%d bytes, expected %d)" % (Cin, Cout, Wp.numel() * Wp.element_size(), packed_bytes(9 * Cin, int(Cout))))
-    for name, v in (("scale", scale), ("shift", shift)):
-        _chk(v, _f32, "conv3x3_x3 " + name)
-        if v.numel() < Cout:
-            raise RuntimeError("conv3x3_x3: %s holds %d values, needs %d" % (name, v.numel(), Cout))
-    if residual is not None:
-        _chk(residual, _f32, "conv3x3_x3 residual")
-        if tuple(residual.shape) != (B, Cout, OH, OW):
-            raise RuntimeError("conv3x3_x3: residual must be f32%s, got %s" % ((B, Cout, OH, OW), tuple(residual.shape)))
     y = torch.empty((B, Cout, OH, OW), dtype=_f32, device=x.device)
     Wd = sd = hd = yd = None
     if downsample is not None:
@@ -698,8 +740,7 @@ def conv3x3_x3(x, Wp, Cout, scale, shift, stride, relu, residual=None, downsampl
         if sd.numel() < Cout or hd.numel() < Cout:
             raise RuntimeError("conv3x3_x3: downsample scale / shift need %d values" % Cout)
         yd = torch.empty((B, Cout, OH, OW), dtype=_f32, device=x.device)
-    if _lib.WORK is not None:
-        _lib.WORK["di2p_conv3x3_x3"] = _lib.WORK.get("di2p_conv3x3_x3", 0) + B * Cout * Cin * (9 + (1 if downsample is not None else 0)) * OH * OW
+    _work("di2p_conv3x3_x3", B * Cout * Cin * (9 + (1 if downsample is not None else 0)) * OH * OW)
     call("di2p_conv3x3_x3", ptr(x), ptr(Wp), ptr(scale), ptr(shift), ptr(residual), ptr(y), B, Cin, H, W, Cout, int(stride), int(bool(relu)),
          ptr(Wd), ptr(sd), ptr(hd), ptr(yd), int(cfg), stream())
     return (y, yd) if downsample is not None else y
@@ -754,8 +795,7 @@ def stem_x3(x, Wp, scale, shift):
     if Wp.numel() * Wp.element_size() != _lib.load().di2p_stem_x3_packed_bytes() or scale.numel() < 64 or shift.numel() < 64:
         raise RuntimeError("stem_x3: Wp must be stem_x3_weights(...) and scale / shift hold 64 values")
     y = torch.empty((B, 64, H // 4, W // 4), dtype=_f32, device=x.device)
-    if _lib.WORK is not None:
-        _lib.WORK["di2p_stem_x3"] = _lib.WORK.get("di2p_stem_x3", 0) + B * 64 * 147 * (H // 2) * (W // 2)
+    _work("di2p_stem_x3", B * 64 * 147 * (H // 2) * (W // 2))
     call("di2p_stem_x3", ptr(x), ptr(Wp), ptr(scale), ptr(shift), ptr(y), B, H, W, stream())
     return y
 
@@ -788,13 +828,13 @@ def winograd_weights_dgrad(weight):
 def conv3x3_winograd(x, U, scale, shift, relu, residual=None):
     """3x3 / stride 1 / pad 1 convolution via Winograd F(2x2,3x3): y = relu?(scale * conv(x) + shift + residual)."""
     require_cuda(x, U, scale, shift, residual)
-    B, Cin, H, W = x.shape
-    Cout = U.shape[2]
-    if U.shape[0] != 16 or U.shape[1] != Cin:
-        raise RuntimeError("U must be f32[16, Cin, Cout]")
+    _chk(U, _f32, "conv3x3_winograd U")
+    Cout = U.shape[-1]
+    B, Cin, H, W, _, _ = _conv_operands("conv3x3_winograd", x, Cout, 3, 3, 1, 1, scale, shift, residual)
+    if tuple(U.shape) != (16, Cin, Cout):
+        raise RuntimeError("U must be f32[16, Cin, Cout] = [16, %d, %d], got %s" % (Cin, Cout, tuple(U.shape)))
     y = torch.empty((B, Cout, H, W), dtype=_f32, device=x.device)
-    if _lib.WORK is not None:
-        _lib.WORK["di2p_conv3x3_winograd"] = _lib.WORK.get("di2p_conv3x3_winograd", 0) + B * Cout * Cin * 16 * ((H + 1) // 2) * ((W + 1) // 2)
+    _work("di2p_conv3x3_winograd", B * Cout * Cin * 16 * ((H + 1) // 2) * ((W + 1) // 2))
     call("di2p_conv3x3_winograd", ptr(x), ptr(U), ptr(scale), ptr(shift), ptr(residual), ptr(y), B, Cin, H, W, Cout, int(bool(relu)), stream())
     return y
 

@@ -15,7 +15,7 @@ floats: output and every input / parameter gradient against torch.autograd of th
   determinism  every replay runs twice: bit-identical outputs and gradients
   coverage     the kernel path of each case from the library's own predicates; the recorded step must reach every path listed in REQUIRED
   knobs        rc_tile64, bn_unfused, pw_x3, conv_x3, conv_x3_cfg, conv_dgrad_dense on the same recorded cases; the stride-1 3x3 layers of
-               stages 1 and 2 at batch 16 (where _use_conv_x3 takes every stage)
+               stages 1 and 2 at batch 16 (where ops.conv_route takes every stage)
 
 Run with -s for the per-case table and the coverage manifest.
 """
@@ -287,45 +287,29 @@ def _rc_path(rows, cols, R):
     return "rc_gemm128" if vec and rows >= 128 and cols >= 128 and _lib.get_option("rc_tile64") == 0 else "rc_gemm 64-tile"
 
 
-def _x3_cfg_note(xshape, Cout):
+def _conv_path(xs, ws, stride, pad, what):
+    """The kernel ops.conv_route names for the training step's convolution of xs with a filter bank ws (what = "fwd" / "dgrad"), as a label."""
     from deepi2p_amd import _lib, ops
-    if _lib.get_option("conv_x3_cfg") >= 0:
-        return "cfg %d" % _lib.get_option("conv_x3_cfg")
-    if xshape[0] < 16:
-        with _lib.option("conv_x3_cfg", 3):
-            if ops.conv3x3_x3_supported(xshape, Cout, 1):
-                return "cfg 3"
-    return "cfg auto"
-
-
-def _conv_fwd_path(tn, xs, ws, stride, pad):
-    Cout, Cin, KH, KW = ws
-    if (KH, KW, stride, pad) == (3, 3, 1, 1) and Cin % 16 == 0 and tn._use_conv_x3(xs, Cout):
-        return "x3 conv fwd", _x3_cfg_note(xs, Cout)
-    if (KH, KW, stride, pad) == (3, 3, 1, 1) and Cin % 16 == 0 and Cout % 32 == 0 and xs[3] % 2 == 0 and xs[3] >= 4:
-        return "winograd conv fwd", None
-    if Cin % 16 == 0:
-        return "tap-major direct conv fwd", None
-    return "stem conv fwd, not tap-major", None
+    kernel, cfg = ops.conv_route(xs, ws, stride, pad, training=True)
+    if kernel == "x3":
+        knob = _lib.get_option("conv_x3_cfg")
+        return "x3 conv %s [cfg %s]" % (what, knob if knob >= 0 else cfg if cfg >= 0 else "auto")
+    if kernel == "winograd":
+        return "winograd conv " + what
+    p = "tap-major direct conv fwd" if kernel == "direct_tap" else "stem conv fwd, not tap-major"
+    return "dgrad as " + p if what == "dgrad" else p
 
 
 def _paths(case):
-    """The kernels a case runs under the current knobs (train_net's dispatch restated with its own predicates)."""
+    """The kernels a case runs under the current knobs (the convolutions: by ops.conv_route, the rule train_net itself runs)."""
     from deepi2p_amd import _lib, train_net as tn
     op, sp = case["op"], case["spec"]
     if op == "_Conv2d":
         xs, ws, stride, pad = sp[0][1], sp[1][1], sp[2][1], sp[3][1]
         Cout, Cin, KH, KW = ws
-        p, note = _conv_fwd_path(tn, xs, ws, stride, pad)
-        paths = [p + (" [%s]" % note if note else "")]
+        paths = [_conv_path(xs, ws, stride, pad, "fwd")]
         if stride == 1 and KH == KW and 2 * pad == KH - 1:
-            dys = (xs[0], Cout, xs[2], xs[3])
-            if (KH, pad) == (3, 1) and Cout % 16 == 0 and Cin % 32 == 0 and xs[3] % 2 == 0 and xs[3] >= 4 and not tn._use_conv_x3(dys, Cin):
-                paths.append("winograd conv dgrad")
-            elif (KH, pad) == (3, 1) and Cout % 16 == 0 and tn._use_conv_x3(dys, Cin):
-                paths.append("x3 conv dgrad [%s]" % _x3_cfg_note(dys, Cin))
-            else:
-                paths.append("dgrad as " + _conv_fwd_path(tn, dys, (Cin, Cout, KH, KW), 1, pad)[0])
+            paths.append(_conv_path((xs[0], Cout, xs[2], xs[3]), (Cin, Cout, KH, KW), 1, pad, "dgrad"))
         elif stride == 2 and _lib.get_option("conv_dgrad_dense") == 0:
             paths.append("s2 parity dgrad")
         else:
@@ -504,7 +488,7 @@ def test_knob_conv_x3_off(step):
 
 
 def _batch16_cases():
-    """The stride-1 3x3 layers of stages 1 and 2 at batch 16: from 16 frames on _use_conv_x3 takes every stage (forward and input gradient)."""
+    """The stride-1 3x3 layers of stages 1 and 2 at batch 16: from 16 frames on ops.conv_route takes every stage (forward and input gradient)."""
     cases = []
     for i, (C, H, W) in enumerate(((64, 40, 128), (128, 20, 64))):
         cases.append(dict(op="_Conv2d", spec=[("f", (16, C, H, W)), ("f", (C, C, 3, 3)), ("v", 1), ("v", 1)], seed=900 + i, count=1,
@@ -527,7 +511,7 @@ def test_batch16_stage1_stage2_on_x3(step):
 def test_knob_conv_x3_cfg(step, cfg):
     """Each tile configuration of di2p_conv3x3_x3 on the x3 layers it supports.  A configuration that cannot run a shape (0 and 1 take 32-pixel
     segments: not the 16-pixel rows of the 512-channel stage; 1 to 3 do not fit the batch-16 stage-1 patch, 2 and 3 not the stage-2 one) leaves
-    that layer on the Winograd kernel through _use_conv_x3 -- still held to the bar."""
+    that layer on the Winograd kernel through ops.conv_route -- still held to the bar."""
     from deepi2p_amd import _lib
     cases = _x3_conv_cases(step) + _B16
     with _lib.option("conv_x3_cfg", cfg):
