@@ -355,12 +355,29 @@ inline bool rc_vec_ok(const float* base, long long ld, long long batch_stride, i
     return ((uintptr_t)base & 15) == 0 && ld % 4 == 0 && batch_stride % 4 == 0 && R % 4 == 0 && R >= 32;
 }
 
+// The one routing decision of the family: tile, stager pair and chunk plan of a launch.  kind: 0 = a plainly strided pair (di2p_bmm_rc), 1 = the
+// convolution weight gradient (A strided, B im2col), 2 = the gather backward (A strided, B selection).  a_vec / b_vec: rc_vec_ok of the operand
+// (meaningless, and ignored, for an operand that is not plainly strided).  rc_launch runs what this returns; di2p_rc_route reports it.
+enum { RC_KIND_STRIDED = 0, RC_KIND_WGRAD = 1, RC_KIND_GATHER = 2 };
+struct RcRoute { int tile; bool a_vec, b_vec; RcPlan pl; };
+RcRoute rc_route(int kind, int Z, int rows, int cols, int R, bool a_vec, bool b_vec) {
+    RcRoute rt;
+    rt.a_vec = kind == RC_KIND_STRIDED ? a_vec && b_vec : kind == RC_KIND_WGRAD ? a_vec : false;      // a strided pair takes 16-byte stagers together or not at all
+    rt.b_vec = kind == RC_KIND_STRIDED && a_vec && b_vec;
+    rt.tile = rt.a_vec && rt.b_vec && rc_big(rows, cols) ? RC2_BM : RC_BM;
+    rt.pl = rc_plan(Z, rows, cols, R, rt.tile);
+    return rt;
+}
+
 template <class LA, class LB>
 int rc_launch(const char* who, LA la, LB lb, int Z, int rows, int cols, int R, float alpha, bool reduce_z, float* out, void* ws, long long ws_bytes,
               hipStream_t st, bool a_vec = false, bool b_vec = false) {
-    bool big = false;
-    if constexpr (std::is_same<LA, RcStrided>::value && std::is_same<LB, RcStrided>::value) big = a_vec && b_vec && rc_big(rows, cols);
-    const RcPlan pl = rc_plan(Z, rows, cols, R, big ? RC2_BM : RC_BM);
+    constexpr bool a_strided = std::is_same<LA, RcStrided>::value, b_strided = std::is_same<LB, RcStrided>::value;
+    constexpr int kind = a_strided && b_strided ? RC_KIND_STRIDED : a_strided && std::is_same<LB, RcIm2col>::value ? RC_KIND_WGRAD : RC_KIND_GATHER;
+    const RcRoute rt = rc_route(kind, Z, rows, cols, R, a_vec, b_vec);
+    const bool big = rt.tile == RC2_BM;
+    const RcPlan pl = rt.pl;
+    a_vec = rt.a_vec; b_vec = rt.b_vec;
     if (!ws || ws_bytes < pl.bytes) { di2p_set_error("%s: workspace too small (%lld bytes needed)", who, pl.bytes); return -1; }
     if ((long long)Z * pl.chunks > 65535) { di2p_set_error("%s: too many reduction chunks", who); return -1; }
     const dim3 grid(di2p_cdiv(cols, big ? RC2_BM : RC_BM), di2p_cdiv(rows, big ? RC2_BM : RC_BM), Z * pl.chunks);
@@ -907,6 +924,15 @@ extern "C" int di2p_bmm_rc(const float* A, long long lda, long long a_batch_stri
                      rc_vec_ok(A, lda, a_batch_stride, R), rc_vec_ok(Bm, ldb, b_batch_stride, R));
 }
 
+extern "C" int di2p_rc_vec_ok(const float* base, long long ld, long long batch_stride, int R) { return rc_vec_ok(base, ld, batch_stride, R) ? 1 : 0; }
+
+extern "C" int di2p_rc_route(int kind, int Z, int rows, int cols, int R, int a_vec, int b_vec, int32_t* out) {
+    DI2P_CHECK_ARG(out && kind >= RC_KIND_STRIDED && kind <= RC_KIND_GATHER && Z >= 1 && rows >= 1 && cols >= 1 && R >= 1, "bad args");
+    const RcRoute rt = rc_route(kind, Z, rows, cols, R, a_vec != 0, b_vec != 0);
+    out[0] = rt.tile; out[1] = rt.a_vec; out[2] = rt.b_vec; out[3] = rt.pl.rch; out[4] = rt.pl.chunks;
+    return 0;
+}
+
 extern "C" int di2p_bmm_km(const float* A, int lda, long long a_batch_stride, const float* Bm, int ldb, long long b_batch_stride, float* out, int Z,
                            int rows, int cols, int K, float alpha, void* stream) {
     DI2P_CHECK_ARG(A && Bm && out && Z >= 1 && rows >= 1 && cols >= 1 && K >= 1 && Z <= 65535, "bad args");
@@ -936,7 +962,7 @@ extern "C" int di2p_gather_backward(const float* dy, const int32_t* idx, const f
 extern "C" long long di2p_conv2d_wgrad_workspace_bytes(int B, int Cin, int H, int W, int Cout, int KH, int KW, int stride, int pad) {
     if (B < 1 || Cin < 1 || Cout < 1 || KH < 1 || KW < 1 || stride < 1) return 0;
     const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
-    if (OH < 1 || OW < 1) return 0;
+    if (H + 2 * pad < KH || W + 2 * pad < KW || OH < 1 || OW < 1) return 0;
     return rc_plan(B, Cout, Cin * KH * KW, OH * OW).bytes;
 }
 
@@ -944,7 +970,7 @@ extern "C" int di2p_conv2d_wgrad(const float* x, const float* dy, float* dW, int
                                  void* workspace, long long workspace_bytes, void* stream) {
     DI2P_CHECK_ARG(x && dy && dW && B >= 1 && Cin >= 1 && Cout >= 1 && KH >= 1 && KW >= 1 && stride >= 1 && pad >= 0, "bad args");
     const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
-    DI2P_CHECK_ARG(OH >= 1 && OW >= 1, "empty output");
+    DI2P_CHECK_ARG(H + 2 * pad >= KH && W + 2 * pad >= KW && OH >= 1 && OW >= 1, "empty output");          // (the division truncates toward zero: a filter that does not fit gives 1 at stride > 1)
     RcStrided la{}; la.base = dy; la.ld = (long long)OH * OW; la.batch_stride = (long long)Cout * OH * OW; la.n = Cout;
     RcIm2col lb{}; lb.base = x; lb.Cin = Cin; lb.H = H; lb.W = W; lb.OW = OW; lb.KH = KH; lb.KW = KW; lb.stride = stride; lb.pad = pad; lb.ncols = Cin * KH * KW;
     return rc_launch(__func__, la, lb, B, Cout, Cin * KH * KW, OH * OW, 1.0f, true, dW, workspace, workspace_bytes, (hipStream_t)stream,
@@ -955,7 +981,7 @@ extern "C" int di2p_conv2d_dgrad(const float* dy, const float* Wgt, float* dx, i
                                  void* stream) {
     DI2P_CHECK_ARG(dy && Wgt && dx && B >= 1 && B <= 65535 && Cin >= 1 && Cout >= 1 && KH >= 1 && KW >= 1 && stride >= 1 && pad >= 0, "bad args");
     const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
-    DI2P_CHECK_ARG(OH >= 1 && OW >= 1, "empty output");
+    DI2P_CHECK_ARG(H + 2 * pad >= KH && W + 2 * pad >= KW && OH >= 1 && OW >= 1, "empty output");          // (the division truncates toward zero: a filter that does not fit gives 1 at stride > 1)
     if (stride == 2 && B <= 16383 && !di2p_opt(DI2P_OPT_CONV_DGRAD_DENSE)) {          // one parity class of input pixels per workgroup: 1/4 of the matrix work
         const int ncol = ((H + 1) / 2) * ((W + 1) / 2);
         hipLaunchKernelGGL(conv_dgrad_s2_kernel, dim3(di2p_cdiv(ncol, KmCfg::BN), di2p_cdiv(Cin, KmCfg::BM), B * 4), dim3(KmCfg::THREADS),

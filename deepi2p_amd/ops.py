@@ -718,6 +718,25 @@ def conv3x3_x3_plan(x_shape, Cout, stride, cfg=-1):
     return dict(zip(CONV_X3_PLAN_FIELDS, (int(v) for v in out)))
 
 
+RC_KINDS = ("strided", "wgrad", "gather")
+RC_ROUTE_FIELDS = ("tile", "a_stager", "b_stager", "rch", "chunks")
+
+
+def rc_vec_ok(ptr, ld, batch_stride, R):
+    """True if the reduction GEMMs of the training step may read this strided operand with 16-byte loads (di2p_rc_vec_ok; host code)."""
+    return bool(_lib.load().di2p_rc_vec_ok(ptr, int(ld), int(batch_stride), int(R)))
+
+
+def rc_route(kind, Z, rows, cols, R, a_vec=False, b_vec=False):
+    """What a reduction GEMM of the training step would launch (di2p_rc_route: the launcher's own routing function; host code, no GPU
+    needed): a dict of RC_ROUTE_FIELDS -- tile (64 / 128), the stagers of A and B (0 scalar, 1 16-byte), reduction indices per chunk and
+    chunks.  kind: "strided" (di2p_bmm_rc), "wgrad" (di2p_conv2d_wgrad: rows = Cout, cols = Cin*KH*KW, R = OH*OW), "gather"
+    (di2p_gather_backward: rows = C, cols = M, R = J); a_vec / b_vec: rc_vec_ok of the strided operands."""
+    out = (ctypes.c_int32 * len(RC_ROUTE_FIELDS))()
+    _lib.call("di2p_rc_route", RC_KINDS.index(kind), int(Z), int(rows), int(cols), int(R), int(bool(a_vec)), int(bool(b_vec)), out)
+    return dict(zip(RC_ROUTE_FIELDS, (int(v) for v in out)))
+
+
 def conv3x3_x3(x, Wp, Cout, scale, shift, stride, relu, residual=None, downsample=None, cfg=-1):
     """3x3 / pad 1 convolution on the bf16 matrix instructions with exact three-way fp32 splits (di2p_conv3x3_x3):
     y = relu?(scale * conv(x) + shift + residual).  Wp = bf16x3_pack(tap-major Wt[9 Cin, Cout]).  stride 2 takes

@@ -506,6 +506,12 @@ int di2p_adam_step(float* params, const float* grads, float* exp_avg, float* exp
  * di2p_bmm_rc: out[z][row][col] = alpha * sum_r A[z][row*lda + r] * B[z][col*ldb + r]  (both operands contiguous along the reduction:
  *   d W[M][K] = sum_{b,n} dY[b][m][n] X[b][k][n] with reduce_z = 1; attention d feat with reduce_z = 0).  Deterministic chunked reduction;
  *   workspace: di2p_bmm_rc_workspace_bytes(Z, rows, cols, R).
+ * di2p_rc_route / di2p_rc_vec_ok (additive; detect by symbol): which kernel instance and chunk plan a call of this family runs -- host code,
+ *   the launcher's own routing function, launches nothing (for tests and tools).  kind 0 = di2p_bmm_rc, 1 = di2p_conv2d_wgrad (rows = Cout,
+ *   cols = Cin*KH*KW, R = OH*OW, Z = B), 2 = di2p_gather_backward (rows = C, cols = M, R = J, Z = B); a_vec / b_vec = di2p_rc_vec_ok of the
+ *   strided operand(s) (1: 16-byte aligned base, ld % 4 == 0, batch_stride % 4 == 0, R % 4 == 0, R >= 32; honours the knob "rc_tile64").
+ *   out[0..4] = tile (64 or 128), A stager, B stager (0 scalar, 1 16-byte), reduction indices per chunk, chunks; the workspace the call
+ *   needs is Z * chunks * rows * cols * 4 bytes.
  * di2p_bmm_km: out[z][row][col] = alpha * sum_k A[z][k*lda + row] * B[z][k*ldb + col]  (attention d score).
  * di2p_gather_backward: d feats[b,c,m] = sum_j dy[b,c,j] * sum_k w[b,j,k] * [idx[b,j,k] == m]; k = 1 (torch.gather along the point axis,
  *   weights NULL = 1) or k = 3 (upsample_by_interpolation, networks_united.py:90-103).  workspace: di2p_gather_backward_workspace_bytes.
@@ -525,6 +531,8 @@ int di2p_channel_sum(const float* x, float* out, int B, int C, int N, void* work
 long long di2p_bmm_rc_workspace_bytes(int Z, int rows, int cols, int R);
 int di2p_bmm_rc(const float* A, long long lda, long long a_batch_stride, const float* Bm, long long ldb, long long b_batch_stride, float* out,
                 int Z, int rows, int cols, int R, float alpha, int reduce_z, void* workspace, long long workspace_bytes, void* stream);
+int di2p_rc_vec_ok(const float* base, long long ld, long long batch_stride, int R);
+int di2p_rc_route(int kind, int Z, int rows, int cols, int R, int a_vec, int b_vec, int32_t* out);
 int di2p_bmm_km(const float* A, int lda, long long a_batch_stride, const float* Bm, int ldb, long long b_batch_stride, float* out, int Z,
                 int rows, int cols, int K, float alpha, void* stream);
 long long di2p_gather_backward_workspace_bytes(int B, int C, int J, int M);
