@@ -160,16 +160,11 @@ __global__ __launch_bounds__(256, 1) void conv3x3_x3_kernel(const CxArgs a) {
 #pragma unroll
             for (int p = 0; p < 3; ++p) af[slot][i][p] = __builtin_amdgcn_raw_buffer_load_b128(wr, a_off[i], so + p * 16, 0);
     };
+    // The accumulators are never filled with zeros: the first product into each (tap 0, resp. the centre tap, of the first chunk) takes the
+    // constant zero as its C operand.  Besides the fill itself this keeps constants out of the accumulators' loop PHIs: hipcc breaks a
+    // vector PHI with a constant among its inputs into one PHI per register, the chunk loop then carried 4-register accumulators as single
+    // registers and rotated them through v_accvgpr moves on every chunk (DESIGN, "conv3x3_x3: accumulator copies").
     acc_t acc[TM][TN], accs[SA ? TM : 1][SA ? TN : 1];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < M::NACC; ++r) {
-                acc[i][j][r] = 0.0f;
-                if constexpr (SA) accs[i][j][r] = 0.0f;
-            }
     // fused downsample branch: own descriptor, offsets, accumulators
     acc_t acc_ds[DS ? TM : 1][DS ? TN : 1];
     u32x4_t af_ds[DS ? TM : 1][3];
@@ -178,13 +173,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_x3_kernel(const CxArgs a) {
     if constexpr (DS) {
         wr_ds = __builtin_amdgcn_make_buffer_rsrc((void*)a.Wp_ds, 0, (int)min((long long)(a.Cin / 8) * a.Mp_ds * 48, 0x7fffffffll), 0x00020000);
 #pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            a_off_ds[i] = (cl * a.Mp_ds + mt * MT + (wm * TM + i) * MF + nl) * 48;
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < M::NACC; ++r) acc_ds[i][j][r] = 0.0f;
-        }
+        for (int i = 0; i < TM; ++i) a_off_ds[i] = (cl * a.Mp_ds + mt * MT + (wm * TM + i) * MF + nl) * 48;
     }
     auto a_load_ds = [&](int c) {
         if constexpr (DS) {
@@ -208,24 +197,28 @@ __global__ __launch_bounds__(256, 1) void conv3x3_x3_kernel(const CxArgs a) {
 #pragma unroll
             for (int j = 0; j < TN; ++j) bf[set][j][p] = lds[bcur[j] + toff + p];
     };
-    // one tap of one chunk: six products per tile, smallest terms first; consecutive matrix instructions write different accumulators
-    auto tap_mma = [&](int slot, int set, int tap) __attribute__((always_inline)) {
-#define DI2P_CX_PROD(ACC, QA, QB)                                                                                                       \
+    // one tap of one chunk: six products per tile, smallest terms first; consecutive matrix instructions write different accumulators.
+    // `first`: the first chunk, whose first product into an accumulator starts it from the constant zero (an inline operand)
+    auto tap_mma = [&](int slot, int set, int tap, bool first) __attribute__((always_inline)) {
+        const bool z = first && tap == 0;
+#define DI2P_CX_PROD(ACC, QA, QB, Z)                                                                                                    \
     _Pragma("unroll") for (int i = 0; i < TM; ++i) _Pragma("unroll") for (int j = 0; j < TN; ++j)                                       \
-        ACC[i][j] = bf16x3::mma(af[slot][i][QA], bf[set][j][QB], ACC[i][j]);
+        ACC[i][j] = bf16x3::mma(af[slot][i][QA], bf[set][j][QB], (Z) ? acc_t{} : ACC[i][j]);
         if constexpr (SA) {
-            DI2P_CX_PROD(accs, 2, 0) DI2P_CX_PROD(accs, 1, 1) DI2P_CX_PROD(accs, 0, 2) DI2P_CX_PROD(accs, 1, 0) DI2P_CX_PROD(accs, 0, 1)
+            DI2P_CX_PROD(accs, 2, 0, z) DI2P_CX_PROD(accs, 1, 1, false) DI2P_CX_PROD(accs, 0, 2, false) DI2P_CX_PROD(accs, 1, 0, false)
+            DI2P_CX_PROD(accs, 0, 1, false) DI2P_CX_PROD(acc, 0, 0, z)
         } else {
-            DI2P_CX_PROD(acc, 2, 0) DI2P_CX_PROD(acc, 1, 1) DI2P_CX_PROD(acc, 0, 2) DI2P_CX_PROD(acc, 1, 0) DI2P_CX_PROD(acc, 0, 1)
+            DI2P_CX_PROD(acc, 2, 0, z) DI2P_CX_PROD(acc, 1, 1, false) DI2P_CX_PROD(acc, 0, 2, false) DI2P_CX_PROD(acc, 1, 0, false)
+            DI2P_CX_PROD(acc, 0, 1, false) DI2P_CX_PROD(acc, 0, 0, false)
         }
-        DI2P_CX_PROD(acc, 0, 0)
 #undef DI2P_CX_PROD
         if constexpr (DS) {
             if (tap == 4) {
-#define DI2P_CX_PROD(QA, QB)                                                                                                            \
+#define DI2P_CX_PROD(QA, QB, Z)                                                                                                         \
     _Pragma("unroll") for (int i = 0; i < TM; ++i) _Pragma("unroll") for (int j = 0; j < TN; ++j)                                       \
-        acc_ds[i][j] = bf16x3::mma(af_ds[i][QA], bf[set][j][QB], acc_ds[i][j]);
-                DI2P_CX_PROD(2, 0) DI2P_CX_PROD(1, 1) DI2P_CX_PROD(0, 2) DI2P_CX_PROD(1, 0) DI2P_CX_PROD(0, 1) DI2P_CX_PROD(0, 0)
+        acc_ds[i][j] = bf16x3::mma(af_ds[i][QA], bf[set][j][QB], (Z) ? acc_t{} : acc_ds[i][j]);
+                DI2P_CX_PROD(2, 0, first) DI2P_CX_PROD(1, 1, false) DI2P_CX_PROD(0, 2, false) DI2P_CX_PROD(1, 0, false) DI2P_CX_PROD(0, 1, false)
+                DI2P_CX_PROD(0, 0, false)
 #undef DI2P_CX_PROD
             }
         }
@@ -236,8 +229,8 @@ __global__ __launch_bounds__(256, 1) void conv3x3_x3_kernel(const CxArgs a) {
     // memory into the next ring slot, then the B fragments from LDS into the other register set ; a few vector instructions of the split
     // of one staged item }, then that item's LDS stores and last the eight loads of the item that is fetched in this tap (behind the
     // A requests: the wait for A at the next tap then leaves them in flight; they are first used three taps later).
-    auto chunk = [&](int c, auto stage_tag) __attribute__((always_inline)) {
-        constexpr bool STAGE = decltype(stage_tag)::value;
+    auto chunk = [&](int c, auto stage_tag, auto first_tag) __attribute__((always_inline)) {
+        constexpr bool STAGE = decltype(stage_tag)::value, FIRST = decltype(first_tag)::value;
         const int buf = DBUF ? (c & 1) : 0;
 #pragma unroll
         for (int j = 0; j < TN; ++j) bcur[j] = bbase[j] + buf * BUF;
@@ -253,10 +246,10 @@ __global__ __launch_bounds__(256, 1) void conv3x3_x3_kernel(const CxArgs a) {
             if (tap < 8) b_read((tap + 1) & 1, tap + 1);
             if (tap < 7) a_load((tap + 2) % 3, tap + 2, c);
             else a_load((tap + 2) % 3, tap - 7, min(c + 1, NC - 1));
-            tap_mma(tap % 3, tap & 1, tap);
+            tap_mma(tap % 3, tap & 1, tap, FIRST);
             const bool stores = STAGE && DBUF && tap >= 3 && tap - 3 < ITEMS, loads = STAGE && tap < ITEMS;
             if (stores) stage_store(tap - 3, buf ^ 1);
-            if (loads) stage_load(tap, c + 1);
+            if (loads) stage_load(tap, min(c + 1, NC - 1));      // past the end (a layer of one chunk): this chunk again
 #pragma unroll
             for (int i = 0; i < NM; ++i) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                    // one matrix instruction
@@ -285,26 +278,30 @@ __global__ __launch_bounds__(256, 1) void conv3x3_x3_kernel(const CxArgs a) {
     a_load(1, 1, 0);
     __syncthreads();
     CX_STAMP(0);
-    for (int c = 0; c + 1 < NC; ++c) chunk(c, std::true_type{});
-    chunk(NC - 1, std::false_type{});
+    // The first chunk starts the accumulators (from zero), the last one stages no patch; the chunks between them are the loop.  A layer of
+    // one chunk runs the first alone, which then stages its own patch once more and nobody reads it (no such layer in the network; a
+    // fourth copy of the chunk for it cost every instance registers).
+    chunk(0, std::true_type{}, std::true_type{});
+    for (int c = 1; c + 1 < NC; ++c) chunk(c, std::true_type{}, std::false_type{});
+    if (NC > 1) chunk(NC - 1, std::false_type{}, std::false_type{});
 
     // ---- epilogue
-    if constexpr (SA) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) acc[i][j] += accs[i][j];
-    }
     // Every load of the epilogue (folded BatchNorm rows, residual) is requested before the first result is formed, and nothing in it
     // branches: hipcc otherwise waits for each residual value (and the store before it) in turn -- eighty memory round trips per wave.
     // Buffer addressing drops what must not be written (segments past the frame, channels past Cout): their offset is out of range.
+    // An accumulator register is read once, where its output is formed; with SMALL the small products' set is added in that read
+    // (acc + accs first, then scale, shift, residual, ReLU).
     auto store = [&](const acc_t (&ac)[TM][TN], const float* scale, const float* shift, const float* res, float* y, bool relu,
-                     auto res_tag) __attribute__((always_inline)) {
-        constexpr bool RES = decltype(res_tag)::value;
+                     auto res_tag, auto small_tag) __attribute__((always_inline)) {
+        constexpr bool RES = decltype(res_tag)::value, SMALL = decltype(small_tag)::value;
         constexpr int OOB = 0x40000000;
         const int bytes = a.Cout * OHW * 4;
         const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc((void*)(y + (long long)b * a.Cout * OHW), 0, bytes, 0x00020000);
         const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc((void*)((RES ? res : y) + (long long)b * a.Cout * OHW), 0, bytes, 0x00020000);
+        // the folded BatchNorm rows through descriptors of their own: a channel past Cout is out of range and loads as zero (its outputs
+        // are dropped below).  The whole offset is the instruction's vector offset: the scalar offset is not range-checked
+        const __amdgpu_buffer_rsrc_t scr = __builtin_amdgcn_make_buffer_rsrc((void*)scale, 0, a.Cout * 4, 0x00020000);
+        const __amdgpu_buffer_rsrc_t shr = __builtin_amdgcn_make_buffer_rsrc((void*)shift, 0, a.Cout * 4, 0x00020000);
         int so[TN];
 #pragma unroll
         for (int j = 0; j < TN; ++j) so[j] = sval[j] ? ooff[j] * 4 : OOB;
@@ -314,8 +311,9 @@ __global__ __launch_bounds__(256, 1) void conv3x3_x3_kernel(const CxArgs a) {
         for (int i = 0; i < TM; ++i)
 #pragma unroll
             for (int r = 0; r < M::NACC; ++r) {
-                const int co = mt * MT + (wm * TM + i) * MF + M::row(r, cl), cc = min(co, a.Cout - 1);
-                sc[i][r] = scale[cc]; sh[i][r] = shift[cc];
+                const int co = mt * MT + (wm * TM + i) * MF + M::row(r, cl);
+                sc[i][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(scr, co * 4, 0, 0));
+                sh[i][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(shr, co * 4, 0, 0));
                 co_off[i][r] = co < a.Cout ? co * OHW * 4 : OOB;
                 if constexpr (RES) {
 #pragma unroll
@@ -323,21 +321,35 @@ __global__ __launch_bounds__(256, 1) void conv3x3_x3_kernel(const CxArgs a) {
                         rv[i][j][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rr, (int)((unsigned)co_off[i][r] + (unsigned)so[j]), 0, 0));
                 }
             }
+        __builtin_amdgcn_sched_barrier(0);      // the requests stay ahead of the results: moved among them, the accumulators were read early and spilled
+        // An accumulator register is read where its output is formed, by a statement of THIS branch (with / without a residual: two
+        // texts).  Written as plain element reads they are the same in both branches, and hipcc hoists them above the branch: every
+        // accumulator read before the first request, the values spilled.  The matrix instructions are long done (a barrier and all the
+        // requests above lie between); the idle states make that a property of these lines.
+        asm volatile("s_nop 15\n\ts_nop 3");
+        auto acc_read = [&](float e) __attribute__((always_inline)) {
+            float u;
+            if constexpr (RES) asm volatile("v_accvgpr_read_b32 %0, %1 ; residual" : "=v"(u) : "a"(e));
+            else asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(u) : "a"(e));
+            return u;
+        };
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
             for (int r = 0; r < M::NACC; ++r)
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
-                    float v = ac[i][j][r] * sc[i][r] + sh[i][r];
+                    float u = acc_read(ac[i][j][r]);
+                    if constexpr (SMALL) u += acc_read(accs[i][j][r]);
+                    float v = u * sc[i][r] + sh[i][r];
                     if constexpr (RES) v += rv[i][j][r];
                     v = relu ? fmaxf(v, 0.0f) : v;
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), yr, (int)((unsigned)co_off[i][r] + (unsigned)so[j]), 0, 0);
                 }
     };
-    if (a.residual) store(acc, a.scale, a.shift, a.residual, a.y, a.relu != 0, std::true_type{});
-    else store(acc, a.scale, a.shift, a.residual, a.y, a.relu != 0, std::false_type{});
-    if constexpr (DS) store(acc_ds, a.scale_ds, a.shift_ds, nullptr, a.y_ds, false, std::false_type{});
+    if (a.residual) store(acc, a.scale, a.shift, a.residual, a.y, a.relu != 0, std::true_type{}, std::bool_constant<SA>{});
+    else store(acc, a.scale, a.shift, a.residual, a.y, a.relu != 0, std::false_type{}, std::bool_constant<SA>{});
+    if constexpr (DS) store(acc_ds, a.scale_ds, a.shift_ds, nullptr, a.y_ds, false, std::false_type{}, std::false_type{});
 #if DI2P_CX_CLK
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     CX_STAMP(3);
