@@ -1,7 +1,7 @@
 // Philox4x32-10 (Salmon et al., SC'11; Random123 constants) and the 53-bit uniform every draw of the library is made from.  One
 // definition, so that a stream keeps its bits wherever it is drawn.  The fourth counter word is the stream tag:
 //   0, 1 restart list   2 random choice   3 dropout keep-mask   4 per-frame sample draws   5 point / intensity / normal jitter
-//   6 point shuffle (range filter of the Oxford loader)
+//   6 point shuffle (range filter of the Oxford loader)   7 synthetic-world scan: dropout, range and intensity noise (world.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,6 +1,6 @@
 // Batches that are ragged on two levels (batch entry -> units -> rows): what the count / prefix / write split of submap.hip (sub-map ->
-// profiles -> rows) and sweeps.hip (frame -> sweeps -> rows) has in common.  Included by those two files only; everything is in the
-// anonymous namespace, so each of them gets its own offsets_kernel.  Integer code throughout.
+// profiles -> rows) and sweeps.hip (frame -> sweeps -> rows) has in common.  Included by those two files (and by world.hip, for wave_prefix
+// and the workspace helpers); everything is in the anonymous namespace, so each of them gets its own offsets_kernel.  Integer code throughout.
 //   check_offsets2   (device, wave-wide) the acceptance of one entry's offsets on both levels
 //   wave_prefix      (device, wave-wide) chunked exclusive prefix over a range of int counts, 64-bit lanes, clamped at 2^31 - 1
 //   offsets_kernel   one wave: exclusive prefix over the entries' totals, the final status

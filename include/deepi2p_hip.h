@@ -767,6 +767,33 @@ int di2p_sweep_accumulate(const float* rows, const int32_t* sweep_offsets, const
                           int P_cap, int cols, int cap, int max_frame_points, float box_x, float box_y, int32_t* kept, int32_t* out_offsets,
                           float* out_points, int32_t* status, void* workspace, void* stream);
 
+/* ---- (additive, ABI 9; detect by symbol) synthetic worlds (csrc/world.hip) ---------------------------------------------------------------------
+ * One analytic scene per frame, ray-cast for the camera and for an HDL-64-like LiDAR through one trace function (deepi2p_amd/world.py fixes
+ * the formulas; tests/world_oracle.py restates them in numpy).  prims f64[B,P,16], P <= 32 (checked), count i32[B] (clamped to [0, P] on the
+ * device; 0: all sky, no return).  A row: type (0 ground, 1 box, 2 vertical cylinder); ground z0 | box lo xyz, hi xyz | cylinder cx, cy,
+ * radius, z0, z1 in slots 1-6; albedo r g b in [0, 1] (7-9); LiDAR reflectance (10); texture cell size > 0 (11); 12-15 unused.
+ * di2p_world_trace: origin f64[B,3], dirs f64[B,R,3] -> t f64[B,R] (inf on a miss), prim i32[B,R] (-1 on a miss): the nearest hit, ties to
+ *   the lowest index; fp64, no fused multiply-add; slab test with 1 / d (NaN products skipped), smaller cylinder root, ground for d.z < 0.
+ * di2p_world_render_camera: pixel (u, v) casts cam_to_world[b] . ((u - cx) / fx, (v - cy) / fy, 1) from cam_to_world[b]'s translation
+ *   (K_raw f64[B,3,3], cam_to_world f64[B,4,4] used as given) -> image u8[B,H0,W0,3] (4-byte aligned; dword stores, correct for any H0, W0),
+ *   and where not NULL depth f32[B,H0,W0] (t, 0 on a miss) and prim i32[B,H0,W0].  max_range: the distance at which the fade ends.
+ * di2p_world_render_scan, four launches, no allocation, no synchronisation: ray r = beam * azimuths + azimuth has the sensor-frame direction
+ *   (cE cA, cE sA, sE) from elevation f64[beams,2] and azimuth f64[B,azimuths,2] (cos, sin), cast from pose f64[B,4,4] (sensor to world).  Kept
+ *   iff t < max_range and u >= dropout (before the noise); t += range_sigma g, intensity = clip(reflectance + intensity_sigma g', 0, 1); u, g,
+ *   g' from Philox counter (r, frame0 + b, 0 | 1 | 2, 7), seed = *seed_dev if seed_dev else seed.  -> out_points f32[B * beams * azimuths, 4]
+ *   rows (x, y, z, intensity) in the sensor frame, the kept rays in ray order, frame after frame; out_offsets i32[B+1]; out_count i32[B].
+ *   Rows past out_offsets[B] are not written.  workspace: di2p_world_workspace_bytes(B, beams * azimuths) bytes (0 for bad sizes), 256-byte
+ *   aligned.  B <= 65535 and B * R < 2^31 everywhere. */
+long long di2p_world_workspace_bytes(int B, int R);
+int di2p_world_trace(const double* prims, const int32_t* count, int B, int P, const double* origin, const double* dirs, int R, double* t,
+                     int32_t* prim, void* stream);
+int di2p_world_render_camera(const double* prims, const int32_t* count, int B, int P, const double* K_raw, const double* cam_to_world, int H0,
+                             int W0, double max_range, uint8_t* image, float* depth, int32_t* prim, void* stream);
+int di2p_world_render_scan(const double* prims, const int32_t* count, int B, int P, const double* elevation, const double* azimuth,
+                           const double* pose, int beams, int azimuths, double max_range, double dropout, double range_sigma,
+                           double intensity_sigma, unsigned long long seed, const unsigned long long* seed_dev, int frame0, float* out_points,
+                           int32_t* out_offsets, int32_t* out_count, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
