@@ -131,6 +131,11 @@ _SIGS = {
     "di2p_bmm_rc": [c_void_p, c_ll, c_ll, c_void_p, c_ll, c_ll, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_ll, c_void_p],
     "di2p_rc_vec_ok": [c_void_p, c_ll, c_ll, c_int],
     "di2p_rc_route": [c_int] * 7 + [ctypes.POINTER(ctypes.c_int32)],
+    "di2p_pointwise_route": [c_int] * 6 + [ctypes.POINTER(ctypes.c_int32)],
+    "di2p_conv2d_route": [c_int] * 12 + [c_ll, ctypes.POINTER(ctypes.c_int32)],
+    "di2p_winograd_route": [c_int] * 5 + [ctypes.POINTER(ctypes.c_int32)],
+    "di2p_point_chain_route": [c_int] * 6 + [ctypes.POINTER(ctypes.c_int32)],
+    "di2p_point_head_route": [c_int] * 8 + [ctypes.POINTER(ctypes.c_int32)],
     "di2p_bmm_km": [c_void_p, c_int, c_ll, c_void_p, c_int, c_ll, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p],
     "di2p_gather_backward": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_ll, c_void_p],
     "di2p_conv2d_wgrad": [c_void_p] * 3 + [c_int] * 9 + [c_void_p, c_ll, c_void_p],

@@ -466,18 +466,13 @@ __global__ __launch_bounds__(Cfg::THREADS) void conv2d_stem_kernel(const float* 
 template <class Cfg>
 void launch_conv_vec(const float* x, const float* Wt, const float* scale, const float* shift, const float* residual, float* y,
                      int Cin, int H, int W, int Cout, int OH, int OW, int KH, int KW, int stride, int pad, int Ntot, int relu,
-                     float* part, int splits, hipStream_t st) {
+                     float* part, int splits, int variant, int depth, hipStream_t st) {
     const dim3 grid(di2p_cdiv(Ntot, Cfg::BN), di2p_cdiv(Cout, Cfg::BM), splits), block(Cfg::THREADS);
     const size_t lds = Cfg::LDS_FLOATS * sizeof(float);
-    // depth-2 register prefetch (bit-identical results; +1..10 % per layer, most on the stride-2 layers); conv_depth1 = 1 selects
-    // the depth-1 engine (tests compare the two)
-    const bool depth1 = di2p_opt(DI2P_OPT_CONV_DEPTH1) != 0;
+    const bool depth1 = depth == 1;
 #define DI2P_CONV_VEC_LAUNCH(S, D) hipLaunchKernelGGL((conv2d_vec_kernel<Cfg, S, D>), grid, block, lds, st, x, Wt, scale, shift, residual, y, Cin, H, W, Cout, OH, OW, KH, KW, pad, Ntot, relu, part, splits)
-    // stride 2: aligned 8-float windows where the shape allows (W == 2 OW, whole 8-column groups, padded 3x3 or plain 1x1); conv_s2scalar = 1: never
-    const bool window = stride == 2 && W == 2 * OW && W % 8 == 0 && ((pad == 1 && KW == 3) || (pad == 0 && KW == 1)) &&
-                        ((uintptr_t)x & 15) == 0 && !di2p_opt(DI2P_OPT_CONV_S2SCALAR);
-    if (stride == 1) { if (depth1) DI2P_CONV_VEC_LAUNCH(1, 1); else DI2P_CONV_VEC_LAUNCH(1, 2); }
-    else if (window) { if (depth1) DI2P_CONV_VEC_LAUNCH(22, 1); else DI2P_CONV_VEC_LAUNCH(22, 2); }
+    if (variant == 1) { if (depth1) DI2P_CONV_VEC_LAUNCH(1, 1); else DI2P_CONV_VEC_LAUNCH(1, 2); }
+    else if (variant == 22) { if (depth1) DI2P_CONV_VEC_LAUNCH(22, 1); else DI2P_CONV_VEC_LAUNCH(22, 2); }
     else { if (depth1) DI2P_CONV_VEC_LAUNCH(2, 1); else DI2P_CONV_VEC_LAUNCH(2, 2); }
 #undef DI2P_CONV_VEC_LAUNCH
     if (splits > 1) {
@@ -596,21 +591,20 @@ int conv_splits(int Cin, int Cout, int KH, int KW, int OW, long long opix, int t
     return per_frame * 2 >= limit * 3 / 2 ? 2 : 3;
 }
 
-int conv2d_impl(const float* x, const float* Wt, const float* scale, const float* shift, const float* residual,
-                float* y, int B, int Cin, int H, int W, int Cout, int KH, int KW, int stride, int pad, int relu,
-                int tap_major, void* workspace, long long workspace_bytes, void* stream) {
-    DI2P_CHECK_ARG(x && Wt && scale && shift && y, "null pointer");
-    DI2P_CHECK_ARG(B >= 0 && Cin >= 1 && H >= 1 && W >= 1 && Cout >= 1 && KH >= 1 && KW >= 1 && stride >= 1 && pad >= 0, "bad size");
-    if (B == 0) return 0;
-    const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
-    DI2P_CHECK_ARG(OH >= 1 && OW >= 1, "empty output");
-    DI2P_CHECK_ARG(!tap_major || Cin % 16 == 0, "tap-major weights need Cin % 16 == 0");
-    DI2P_CHECK_ARG((long long)Cin * H * W < (1ll << 31), "per-image extent must fit 31 bits");
-    const long long Ntot_ll = (long long)B * OH * OW;
-    DI2P_CHECK_ARG(Ntot_ll < (1ll << 31), "too many output pixels");
-    const int Ntot = (int)Ntot_ll;
-    hipStream_t st = (hipStream_t)stream;
-#define DI2P_CONV(CFG) launch_conv<CFG>(x, Wt, scale, shift, residual, y, Cin, H, W, Cout, OH, OW, KH, KW, stride, pad, Ntot, relu, tap_major, st)
+// Output extent of one axis; 0 where the filter does not fit the padded input (C's truncating division would give 1 at stride > 1).
+inline int conv_out(int in, int k, int stride, int pad) { return in + 2 * pad < k ? 0 : (in + 2 * pad - k) / stride + 1; }
+
+// The one routing decision of di2p_conv2d / di2p_conv2d_ws: kernel, tile, stride variant, prefetch depth and split count of a launch.
+// conv2d_impl runs what this returns; di2p_conv2d_route reports it.  x_aligned / wt_aligned: 16-byte aligned x / Wt; workspace_bytes: the
+// usable workspace (0: none, or misaligned).
+enum { CONV_K_SCALAR = 0, CONV_K_VEC = 1, CONV_K_STEMROW = 2 };
+struct ConvRoute { int kernel, bm, bn, bk, variant, depth, splits; };
+ConvRoute conv_route(int B, int Cin, int H, int W, int Cout, int KH, int KW, int stride, int pad, int tap_major, bool x_aligned,
+                     bool wt_aligned, long long workspace_bytes) {
+    const int OH = conv_out(H, KH, stride, pad), OW = conv_out(W, KW, stride, pad);
+    const long long Ntot = (long long)B * OH * OW;
+    ConvRoute rt{};
+    rt.splits = 1; rt.depth = 1;
     // tile choice: K-step 32 when a tap holds whole 32-channel groups (halves barriers, doubles the prefetch
     // distance); the largest tile that still yields >= ~2 workgroups per CU.
     const bool k32 = tap_major && Cin % 32 == 0;
@@ -623,25 +617,61 @@ int conv2d_impl(const float* x, const float* Wt, const float* scale, const float
     else if (Cout >= 128 && nb128x64 >= 512) choice = 2;
     else choice = 0;
     // the 7x7/2 stem (weights in their own order): row-decoding vector stager
-    if (!tap_major && KH == 7 && KW == 7 && stride == 2 && OW % 4 == 0 && Cout % 4 == 0 && ((uintptr_t)Wt & 15) == 0) {
-        using CfgS = TileCfg<2, 2, 1, 2, 32>;      // 64 x 128, B_PASSES = 4 (one mask per pass)
+    if (!tap_major && KH == 7 && KW == 7 && stride == 2 && OW % 4 == 0 && Cout % 4 == 0 && wt_aligned) {
+        rt.kernel = CONV_K_STEMROW; rt.bm = 64; rt.bn = 128; rt.bk = 32;      // B_PASSES = 4 (one mask per pass)
+        return rt;
+    }
+    // vector stager: tap-major weights, 32-channel taps, whole 4-pixel groups per output row, 16-byte aligned weights
+    const bool vec = k32 && OW % 4 == 0 && Cout % 4 == 0 && wt_aligned &&
+                     ((stride == 1 && pad <= 1 && KW <= 2 * pad + 1 && W >= 4) || stride == 2);
+    if (vec) choice = Cout <= 64 ? 1 : 0;   // measured: 64x64 tiles (more, smaller workgroups) win for Cout >= 128
+    if (vec) {
+        rt.splits = conv_splits(Cin, Cout, KH, KW, OW, (long long)OH * OW, tap_major);
+        if (rt.splits > 1 && workspace_bytes < (long long)rt.splits * Cout * Ntot * (long long)sizeof(float)) rt.splits = 1;
+        if (rt.splits > 1) choice = 0;
+        // stride 2: aligned 8-float windows where the shape allows (W == 2 OW, whole 8-column groups, padded 3x3 or plain 1x1); conv_s2scalar = 1: never
+        const bool window = stride == 2 && W == 2 * OW && W % 8 == 0 && ((pad == 1 && KW == 3) || (pad == 0 && KW == 1)) && x_aligned &&
+                            !di2p_opt(DI2P_OPT_CONV_S2SCALAR);
+        rt.variant = stride == 1 ? 1 : window ? 22 : 2;
+        // depth-2 register prefetch (bit-identical results; +1..10 % per layer, most on the stride-2 layers); conv_depth1 = 1 selects
+        // the depth-1 engine (tests compare the two)
+        rt.depth = di2p_opt(DI2P_OPT_CONV_DEPTH1) != 0 ? 1 : 2;
+    }
+    rt.kernel = vec ? CONV_K_VEC : CONV_K_SCALAR;
+    rt.bm = choice >= 2 ? 128 : 64; rt.bn = choice & 1 ? 128 : 64; rt.bk = k32 ? 32 : 16;
+    return rt;
+}
+
+int conv2d_impl(const float* x, const float* Wt, const float* scale, const float* shift, const float* residual,
+                float* y, int B, int Cin, int H, int W, int Cout, int KH, int KW, int stride, int pad, int relu,
+                int tap_major, void* workspace, long long workspace_bytes, void* stream) {
+    DI2P_CHECK_ARG(x && Wt && scale && shift && y, "null pointer");
+    DI2P_CHECK_ARG(B >= 0 && Cin >= 1 && H >= 1 && W >= 1 && Cout >= 1 && KH >= 1 && KW >= 1 && stride >= 1 && pad >= 0, "bad size");
+    if (B == 0) return 0;
+    const int OH = conv_out(H, KH, stride, pad), OW = conv_out(W, KW, stride, pad);
+    DI2P_CHECK_ARG(OH >= 1 && OW >= 1, "empty output");
+    DI2P_CHECK_ARG(!tap_major || Cin % 16 == 0, "tap-major weights need Cin % 16 == 0");
+    DI2P_CHECK_ARG((long long)Cin * H * W < (1ll << 31), "per-image extent must fit 31 bits");
+    const long long Ntot_ll = (long long)B * OH * OW;
+    DI2P_CHECK_ARG(Ntot_ll < (1ll << 31), "too many output pixels");
+    const int Ntot = (int)Ntot_ll;
+    hipStream_t st = (hipStream_t)stream;
+    const ConvRoute rt = conv_route(B, Cin, H, W, Cout, KH, KW, stride, pad, tap_major, ((uintptr_t)x & 15) == 0, ((uintptr_t)Wt & 15) == 0,
+                                    workspace && ((uintptr_t)workspace & 15) == 0 ? workspace_bytes : 0);
+#define DI2P_CONV(CFG) launch_conv<CFG>(x, Wt, scale, shift, residual, y, Cin, H, W, Cout, OH, OW, KH, KW, stride, pad, Ntot, relu, tap_major, st)
+    if (rt.kernel == CONV_K_STEMROW) {
+        using CfgS = TileCfg<2, 2, 1, 2, 32>;      // 64 x 128
         const dim3 grid(di2p_cdiv(Ntot, CfgS::BN), di2p_cdiv(Cout, CfgS::BM));
         hipLaunchKernelGGL(conv2d_stem_kernel<CfgS>, grid, dim3(CfgS::THREADS), CfgS::LDS_FLOATS * sizeof(float), st, x, Wt, scale, shift,
                            residual, y, Cin, H, W, Cout, OH, OW, pad, Ntot, relu);
         DI2P_RETURN_LAUNCH();
     }
-    // vector stager: tap-major weights, 32-channel taps, whole 4-pixel groups per output row, 16-byte aligned weights
-    const bool vec = k32 && OW % 4 == 0 && Cout % 4 == 0 && ((uintptr_t)Wt & 15) == 0 &&
-                     ((stride == 1 && pad <= 1 && KW <= 2 * pad + 1 && W >= 4) || stride == 2);
-    if (vec) choice = Cout <= 64 ? 1 : 0;   // measured: 64x64 tiles (more, smaller workgroups) win for Cout >= 128
-    int splits = vec ? conv_splits(Cin, Cout, KH, KW, OW, (long long)OH * OW, tap_major) : 1;
-    if (splits > 1 && (!workspace || workspace_bytes < (long long)splits * Cout * Ntot * (long long)sizeof(float) || ((uintptr_t)workspace & 15))) splits = 1;
-    if (splits > 1) choice = 0;
+    const int choice = (rt.bm == 128 ? 2 : 0) + (rt.bn == 128 ? 1 : 0);   // 0: 64x64  1: 64x128  2: 128x64  3: 128x128
     float* part = (float*)workspace;
-#define DI2P_CONVV(CFG) launch_conv_vec<CFG>(x, Wt, scale, shift, residual, y, Cin, H, W, Cout, OH, OW, KH, KW, stride, pad, Ntot, relu, part, splits, st)
-    if (vec) {
+#define DI2P_CONVV(CFG) launch_conv_vec<CFG>(x, Wt, scale, shift, residual, y, Cin, H, W, Cout, OH, OW, KH, KW, stride, pad, Ntot, relu, part, rt.splits, rt.variant, rt.depth, st)
+    if (rt.kernel == CONV_K_VEC) {
         if (choice == 1) DI2P_CONVV(CfgC64x128k32); else DI2P_CONVV(CfgC64x64k32);
-    } else if (k32) {
+    } else if (rt.bk == 32) {
         switch (choice) { case 3: DI2P_CONV(CfgC128x128k32); break; case 2: DI2P_CONV(CfgC128x64k32); break;
                           case 1: DI2P_CONV(CfgC64x128k32); break; default: DI2P_CONV(CfgC64x64k32); }
     } else {
@@ -653,6 +683,21 @@ int conv2d_impl(const float* x, const float* Wt, const float* scale, const float
     DI2P_RETURN_LAUNCH();
 }
 }  // namespace
+
+// What di2p_conv2d / di2p_conv2d_ws would launch (host code: nothing is launched): conv2d_impl's own conv_route.  x_aligned / wt_aligned: x / Wt
+// 16-byte aligned; workspace_bytes: size of a 16-byte aligned workspace, 0 for none (di2p_conv2d).
+// out[0..6] = kernel (0 scalar stager, 1 16-byte stager, 2 the 7x7/2 row-decoding stager), tile rows, tile columns, K-step, stride variant
+// (0: n/a, 1, 2, 22 = stride 2 with aligned-window loads), prefetch depth, K-slices actually used.
+extern "C" int di2p_conv2d_route(int B, int Cin, int H, int W, int Cout, int KH, int KW, int stride, int pad, int tap_major, int x_aligned,
+                                 int wt_aligned, long long workspace_bytes, int32_t* out) {
+    DI2P_CHECK_ARG(out && B >= 1 && Cin >= 1 && H >= 1 && W >= 1 && Cout >= 1 && KH >= 1 && KW >= 1 && stride >= 1 && pad >= 0, "bad size");
+    DI2P_CHECK_ARG(conv_out(H, KH, stride, pad) >= 1 && conv_out(W, KW, stride, pad) >= 1, "empty output");
+    DI2P_CHECK_ARG(!tap_major || Cin % 16 == 0, "tap-major weights need Cin % 16 == 0");
+    DI2P_CHECK_ARG((long long)B * conv_out(H, KH, stride, pad) * conv_out(W, KW, stride, pad) < (1ll << 31), "too many output pixels");
+    const ConvRoute rt = conv_route(B, Cin, H, W, Cout, KH, KW, stride, pad, tap_major, x_aligned != 0, wt_aligned != 0, workspace_bytes);
+    out[0] = rt.kernel; out[1] = rt.bm; out[2] = rt.bn; out[3] = rt.bk; out[4] = rt.variant; out[5] = rt.depth; out[6] = rt.splits;
+    return 0;
+}
 
 extern "C" int di2p_conv2d(const float* x, const float* Wt, const float* scale, const float* shift, const float* residual,
                            float* y, int B, int Cin, int H, int W, int Cout, int KH, int KW, int stride, int pad, int relu,
@@ -670,7 +715,7 @@ extern "C" int di2p_conv2d_ws(const float* x, const float* Wt, const float* scal
 extern "C" long long di2p_conv2d_workspace_bytes(int B, int Cin, int H, int W, int Cout, int KH, int KW, int stride, int pad,
                                                  int tap_major) {
     if (B <= 0 || Cin < 1 || H < 1 || W < 1 || Cout < 1 || KH < 1 || KW < 1 || stride < 1 || pad < 0) return 0;
-    const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
+    const int OH = conv_out(H, KH, stride, pad), OW = conv_out(W, KW, stride, pad);
     if (OH < 1 || OW < 1) return 0;
     const bool shape_ok = (stride == 1 && pad <= 1 && KW <= 2 * pad + 1 && W >= 4) || stride == 2;
     const long long Ntot = (long long)B * OH * OW;

@@ -903,9 +903,8 @@ void launch_pw(const SrcDev& s, const float* Wt, float* Y, int B, int M, int K, 
 }
 
 template <class Cfg>
-void launch_pw_vec(bool dense, const SrcDev& s, const float* Wt, float* Y, int B, int M, int K, int N, const EpiDev& e, hipStream_t st) {
+void launch_pw_vec(bool dense, bool d2, const SrcDev& s, const float* Wt, float* Y, int B, int M, int K, int N, const EpiDev& e, hipStream_t st) {
     const dim3 grid(di2p_cdiv(N, Cfg::BN), di2p_cdiv(M, Cfg::BM), B);
-    const bool d2 = di2p_opt(DI2P_OPT_CONV_DEPTH1) == 0 && K > 2 * Cfg::BK;      // depth-2 prefetch pays from three K-steps on
     if (dense && d2)
         hipLaunchKernelGGL((pointwise_gemm_vec_kernel<Cfg, true, true>), grid, dim3(Cfg::THREADS), Cfg::LDS_FLOATS * sizeof(float), st, s, Wt, Y, M, K, N, e);
     else if (dense)
@@ -1282,6 +1281,68 @@ using Cfg64x128 = TileCfg<2, 2, 1, 2>;
 using Cfg32x128 = TileCfg<1, 4, 1, 1>;
 using Cfg64x64 = TileCfg<2, 2, 1, 1>;
 
+// The one routing decision of di2p_pointwise_gemm: stager, tile, loader and prefetch depth of a launch.  The entry point runs what this returns;
+// di2p_pointwise_route reports it.
+//   16-byte stager (vec): weights 16-byte addressable, whole 4-column groups, M > 64.  Sources that are all dense and 16-byte addressable get one
+//   16-byte load per row (dense), gathered / group sources four dword loads.  (Narrow layers, M <= 64, are HBM/latency-bound and measured
+//   25-35 % faster on the scalar stager, whose K-step 16 skips the rows k >= K instead of re-reading clamped ones.)
+//   64 x 64 tiles for every vec layer.  Alone, the big point layers are a few per cent faster on 128 x 128 tiles, but in the 8-stream pipeline
+//   the small tile (32 KB of LDS and 100 registers per workgroup instead of 64 KB and 200) packs better beside the pose solver's workgroups and
+//   the family's own serial time drops too (2.05 -> 1.95 ms): +1.5-2 % frames/s (tools/sweep_packing.sh).  (64 x 128 where N is no multiple of 64.)
+//   Depth-2 prefetch pays from three K-steps on; the knob conv_depth1 = 1 selects depth 1.
+struct PwRoute { int vec, bm, bn, dense, depth, bk; };
+static PwRoute pw_route(int M, int K, int N, int B, bool dense, bool wt_aligned) {
+    PwRoute rt{};
+    rt.vec = M > 64 && N % 4 == 0 && N >= 4 && M % 4 == 0 && wt_aligned && !di2p_opt(DI2P_OPT_PW_NOVEC);
+    if (rt.vec) {
+        rt.bm = 64; rt.bn = N % 64 != 0 ? 128 : 64; rt.bk = 32;
+        rt.dense = dense;
+        rt.depth = di2p_opt(DI2P_OPT_CONV_DEPTH1) == 0 && K > 2 * rt.bk ? 2 : 1;
+        return rt;
+    }
+    rt.bn = 128; rt.bk = 16; rt.dense = 0; rt.depth = 1;
+    if (M <= 32) rt.bm = 32;
+    else if (M <= 64 || (long long)B * di2p_cdiv(N, 128) * di2p_cdiv(M, 128) < 256) rt.bm = 64;
+    else rt.bm = 128;
+    return rt;
+}
+
+// The routing decision of di2p_point_chain: instance (width, K-step of layer 0, layers, column blocks per trip) and the persistent grid on `cus`
+// compute units -- whole workgroups per compute unit (w = waves per SIMD the kernel's registers allow) and as few, equal trips per wave as possible.
+struct ChainRoute { int ks0, layers, tn, nblk, wgs, w; long long total; };
+static ChainRoute chain_route(int M, int K0, bool three, int B, int N, int cus) {
+    ChainRoute rt{};
+    rt.layers = three ? 3 : 2;
+    rt.ks0 = M == 32 ? (K0 <= 8 ? 4 : 16) : (K0 <= 32 ? 16 : 32);
+    rt.tn = M == 32 ? DI2P_CHAIN_TN32 : DI2P_CHAIN_TN64;
+    const int wmax = M == 32 ? DI2P_CHAIN_W32 : DI2P_CHAIN_W64;
+    rt.nblk = di2p_cdiv(N, 32 * rt.tn);
+    rt.total = (long long)B * rt.nblk;
+    rt.w = 1;
+    long long best_trips = 1ll << 62;
+    for (int w = wmax; w >= 1; --w) {
+        const long long trips = (rt.total + 4ll * cus * w - 1) / (4ll * cus * w);
+        if (trips < best_trips) { best_trips = trips; rt.w = w; }
+    }
+    rt.wgs = (int)std::min<long long>((long long)cus * rt.w, (rt.total + 3) / 4);
+    return rt;
+}
+
+// The routing decision of di2p_point_head: the wave-autonomous kernel (reg) where layer 0 fits its register plan -- K0 <= 96, at most two sources,
+// an even first source of two (both half-waves of a K-step read the same source), sources within the buffer-descriptor range -- and the knob
+// head_reg allows it; else the LDS-tile kernel.  g33: both gathered tables with k = 3 (the specialised epilogue of either kernel).
+struct HeadRoute { int reg, g33, bn, nblk, wgs; long long total; };
+static HeadRoute head_route(int K0, int n_src, int c0, bool reg_range, bool g33, int B, int N, int cus) {
+    HeadRoute rt{};
+    rt.reg = K0 <= 96 && n_src <= 2 && di2p_opt(DI2P_OPT_HEAD_REG) != 0 && (n_src != 2 || c0 % 2 == 0) && reg_range;
+    rt.g33 = g33;
+    rt.bn = rt.reg ? 32 : HEAD_BN;
+    rt.nblk = di2p_cdiv(N, rt.bn);
+    rt.total = (long long)B * rt.nblk;
+    rt.wgs = rt.reg ? (int)std::min<long long>(cus, (rt.total + 7) / 8) : (int)std::min<long long>(rt.total, 1ll << 30);
+    return rt;
+}
+
 // ---- host struct -> device struct with the argument checks, once for every pointwise entry point (`who`: its name, for the message)
 #define PW_CHECK(cond, msg) do { if (!(cond)) { di2p_set_error("%s: %s", who, msg); return -1; } } while (0)
 
@@ -1361,24 +1422,26 @@ extern "C" int di2p_pointwise_gemm(const di2p_src_t* srcs, int n_src, const floa
     EpiDev e;
     if (pw_sources(__func__, srcs, n_src, K, "K", s, dense) || pw_epilogue(__func__, epi, Y, M, N, false, e)) return -1;
     hipStream_t st = (hipStream_t)stream;
-    // 4-column staged path (weights 16-byte addressable, whole 4-column groups); sources that are all dense and 16-byte
-    // addressable get one 16-byte load per row, gathered / group sources four dword loads
-    // (narrow layers, M <= 64, are HBM/latency-bound and measured 25-35 % faster on the scalar stager below, whose K-step 16
-    //  skips the rows k >= K instead of re-reading clamped ones)
-    const bool vec = M > 64 && N % 4 == 0 && N >= 4 && M % 4 == 0 && aligned16(Wt) && !di2p_opt(DI2P_OPT_PW_NOVEC);
-    if (vec) {
-        // 64 x 64 tiles for every layer.  Alone, the big point layers are a few per cent faster on 128 x 128 tiles, but in the 8-stream
-        // pipeline the small tile (32 KB of LDS and 100 registers per workgroup instead of 64 KB and 200) packs better beside the pose
-        // solver's workgroups and the family's own serial time drops too (2.05 -> 1.95 ms): +1.5-2 % frames/s (tools/sweep_packing.sh).
-        // (64 x 128 where N is no multiple of 64.)
-        if (N % 64 != 0) launch_pw_vec<TileCfg<2, 2, 1, 2, 32>>(dense, s, Wt, Y, B, M, K, N, e, st);
-        else launch_pw_vec<TileCfg<2, 2, 1, 1, 32>>(dense, s, Wt, Y, B, M, K, N, e, st);
+    const PwRoute rt = pw_route(M, K, N, B, dense, aligned16(Wt));
+    if (rt.vec) {
+        if (rt.bn == 128) launch_pw_vec<TileCfg<2, 2, 1, 2, 32>>(rt.dense, rt.depth == 2, s, Wt, Y, B, M, K, N, e, st);
+        else launch_pw_vec<TileCfg<2, 2, 1, 1, 32>>(rt.dense, rt.depth == 2, s, Wt, Y, B, M, K, N, e, st);
         DI2P_RETURN_LAUNCH();
     }
-    if (M <= 32) launch_pw<Cfg32x128>(s, Wt, Y, B, M, K, N, e, st);
-    else if (M <= 64 || (long long)B * di2p_cdiv(N, 128) * di2p_cdiv(M, 128) < 256) launch_pw<Cfg64x128>(s, Wt, Y, B, M, K, N, e, st);
+    if (rt.bm == 32) launch_pw<Cfg32x128>(s, Wt, Y, B, M, K, N, e, st);
+    else if (rt.bm == 64) launch_pw<Cfg64x128>(s, Wt, Y, B, M, K, N, e, st);
     else launch_pw<Cfg128x128>(s, Wt, Y, B, M, K, N, e, st);
     DI2P_RETURN_LAUNCH();
+}
+
+// What di2p_pointwise_gemm would launch (host code: nothing is launched): the launch entry's own pw_route.  dense: every source is DENSE with
+// row_stride % 4 == 0, batch_stride % 4 == 0 and a 16-byte aligned base; wt_aligned: Wt is 16-byte aligned.
+// out[0..5] = stager (0 scalar, 1 16-byte), tile rows, tile columns, DENSE loader, prefetch depth, K-step.
+extern "C" int di2p_pointwise_route(int M, int K, int N, int B, int dense, int wt_aligned, int32_t* out) {
+    DI2P_CHECK_ARG(out && M >= 1 && K >= 1 && N >= 1 && B >= 1, "bad args");
+    const PwRoute rt = pw_route(M, K, N, B, dense != 0, wt_aligned != 0);
+    out[0] = rt.vec; out[1] = rt.bm; out[2] = rt.bn; out[3] = rt.dense; out[4] = rt.depth; out[5] = rt.bk;
+    return 0;
 }
 
 extern "C" long long di2p_bf16x3_packed_bytes(int K, int M) {
@@ -1487,18 +1550,19 @@ extern "C" int di2p_point_head(const di2p_src_t* srcs, int n_src, const float* W
     EpiDev e;
     if (pw_epilogue(__func__, epi0, nullptr, M, N, false, e)) return -1;
     HeadTail tl{W1t, scale1, shift1, W2t, scale2, shift2, relu1, relu2, P};
-    bool reg_ok = K0 <= 96 && n_src <= 2 && di2p_opt(DI2P_OPT_HEAD_REG) != 0;
-    if (n_src == 2) reg_ok = reg_ok && srcs[0].channels % 2 == 0;            // both half-waves of a K-step read the same source
-    for (int i = 0; i < n_src; ++i) reg_ok = reg_ok && (long long)srcs[i].channels * srcs[i].row_stride * 4 < (1ll << 31);   // buffer-descriptor range
-    if (reg_ok) {
+    bool reg_range = true;
+    for (int i = 0; i < n_src; ++i) reg_range = reg_range && (long long)srcs[i].channels * srcs[i].row_stride * 4 < (1ll << 31);   // buffer-descriptor range
+    const HeadRoute rt = head_route(K0, n_src, srcs[0].channels, reg_range, e.g_table[0] && e.g_table[1] && e.g_k[0] == 3 && e.g_k[1] == 3, B, N,
+                                    di2p_cu_count());
+    if (rt.reg) {
         // wave-autonomous kernel: one 8-wave workgroup per compute unit (118 KB of weights in LDS), equal trips per wave where the sizes allow
         constexpr int KS0 = 48;
-        const int nblk = di2p_cdiv(N, 32);
-        const long long total = (long long)B * nblk;
+        const int nblk = rt.nblk;
+        const long long total = rt.total;
         DI2P_CHECK_ARG(total < (1ll << 30), "too many column blocks");
-        const int wgs = (int)std::min<long long>(di2p_cu_count(), (total + 7) / 8);
+        const int wgs = rt.wgs;
         const size_t lds_reg = (size_t)(2 * KS0 * HEAD_M + HEAD_M * HEAD_M + HEAD_M * 4 + 4 * HEAD_M) * sizeof(float);
-        if (e.g_table[0] && e.g_table[1] && e.g_k[0] == 3 && e.g_k[1] == 3) {
+        if (rt.g33) {
             if (di2p_allow_dynamic_lds((const void*)point_head_reg_kernel<true, KS0>, lds_reg, __func__)) return -1;
             hipLaunchKernelGGL((point_head_reg_kernel<true, KS0>), dim3(wgs), dim3(512), lds_reg, (hipStream_t)stream, s, W0t, K0, e, tl, out, N, nblk, (int)total);
         } else {
@@ -1509,7 +1573,7 @@ extern "C" int di2p_point_head(const di2p_src_t* srcs, int n_src, const float* W
     }
     const size_t lds = (HeadCfg::LDS_FLOATS + HEAD_M * HEAD_BN) * sizeof(float);
     // > 64 KB of dynamic LDS needs the opt-in (per device; the call is cheap, so it is simply made every time)
-    if (e.g_table[0] && e.g_table[1] && e.g_k[0] == 3 && e.g_k[1] == 3) {      // the reference's configuration (k_interp_point_a = k_interp_point_b = 3)
+    if (rt.g33) {      // the reference's configuration (k_interp_point_a = k_interp_point_b = 3)
         if (di2p_allow_dynamic_lds((const void*)point_head_kernel<true>, lds, __func__)) return -1;
         hipLaunchKernelGGL(point_head_kernel<true>, dim3(di2p_cdiv(N, HEAD_BN), B), dim3(HeadCfg::THREADS), lds, (hipStream_t)stream, s, W0t, K0, e, tl, out, N);
     } else {
@@ -1537,34 +1601,46 @@ extern "C" int di2p_point_chain(const di2p_src_t* srcs, int n_src, const float* 
     const long long x_bs = srcs[0].batch_stride;
     const int x_rs = (int)srcs[0].row_stride;
     hipStream_t st = (hipStream_t)stream;
-    // Grid: whole workgroups per compute unit (w = waves per SIMD the kernel's registers allow) and as few, equal trips per wave as possible
-    const int cus = di2p_cu_count();
-#define DI2P_CHAIN_LAUNCH(MM, KS0, NL, TN, WMAX)                                                                                    \
+    const ChainRoute rt = chain_route(M, K0, W2t != nullptr, B, N, di2p_cu_count());
+    DI2P_CHECK_ARG(rt.total < (1ll << 30), "too many column blocks");
+#define DI2P_CHAIN_LAUNCH(MM, KS0, NL, TN)                                                                                          \
     do {                                                                                                                            \
-        const int nblk = di2p_cdiv(N, 32 * (TN));                                                                                   \
-        const long long total = (long long)B * nblk;                                                                                \
-        DI2P_CHECK_ARG(total < (1ll << 30), "too many column blocks");                                                              \
-        int best_w = 1;                                                                                                             \
-        long long best_trips = 1ll << 62;                                                                                           \
-        for (int w = (WMAX); w >= 1; --w) {                                                                                         \
-            const long long trips = (total + 4ll * cus * w - 1) / (4ll * cus * w);                                                  \
-            if (trips < best_trips) { best_trips = trips; best_w = w; }                                                             \
-        }                                                                                                                           \
-        const int wgs = (int)std::min<long long>((long long)cus * best_w, (total + 3) / 4);                                         \
         const size_t lds = (size_t)(2 * (KS0) * (MM) + ((NL) - 1) * (MM) * (MM) + 6 * (MM)) * sizeof(float);                        \
-        hipLaunchKernelGGL((point_chain_kernel<MM, KS0, NL, TN>), dim3(wgs), dim3(256), lds, st, X, x_bs, x_rs, W0t, K0, e, tl, Y, N, \
-                           nblk, (int)total);                                                                                       \
+        hipLaunchKernelGGL((point_chain_kernel<MM, KS0, NL, TN>), dim3(rt.wgs), dim3(256), lds, st, X, x_bs, x_rs, W0t, K0, e, tl, Y, N, \
+                           rt.nblk, (int)rt.total);                                                                                 \
     } while (0)
-    const bool three = W2t != nullptr;
+    const bool three = rt.layers == 3;
     if (M == 32) {
-        if (K0 <= 8) { if (three) DI2P_CHAIN_LAUNCH(32, 4, 3, DI2P_CHAIN_TN32, DI2P_CHAIN_W32); else DI2P_CHAIN_LAUNCH(32, 4, 2, DI2P_CHAIN_TN32, DI2P_CHAIN_W32); }
-        else           { if (three) DI2P_CHAIN_LAUNCH(32, 16, 3, DI2P_CHAIN_TN32, DI2P_CHAIN_W32); else DI2P_CHAIN_LAUNCH(32, 16, 2, DI2P_CHAIN_TN32, DI2P_CHAIN_W32); }
+        if (rt.ks0 == 4) { if (three) DI2P_CHAIN_LAUNCH(32, 4, 3, DI2P_CHAIN_TN32); else DI2P_CHAIN_LAUNCH(32, 4, 2, DI2P_CHAIN_TN32); }
+        else             { if (three) DI2P_CHAIN_LAUNCH(32, 16, 3, DI2P_CHAIN_TN32); else DI2P_CHAIN_LAUNCH(32, 16, 2, DI2P_CHAIN_TN32); }
     } else {
-        if (K0 <= 32) { if (three) DI2P_CHAIN_LAUNCH(64, 16, 3, DI2P_CHAIN_TN64, DI2P_CHAIN_W64); else DI2P_CHAIN_LAUNCH(64, 16, 2, DI2P_CHAIN_TN64, DI2P_CHAIN_W64); }
-        else           { if (three) DI2P_CHAIN_LAUNCH(64, 32, 3, DI2P_CHAIN_TN64, DI2P_CHAIN_W64); else DI2P_CHAIN_LAUNCH(64, 32, 2, DI2P_CHAIN_TN64, DI2P_CHAIN_W64); }
+        if (rt.ks0 == 16) { if (three) DI2P_CHAIN_LAUNCH(64, 16, 3, DI2P_CHAIN_TN64); else DI2P_CHAIN_LAUNCH(64, 16, 2, DI2P_CHAIN_TN64); }
+        else              { if (three) DI2P_CHAIN_LAUNCH(64, 32, 3, DI2P_CHAIN_TN64); else DI2P_CHAIN_LAUNCH(64, 32, 2, DI2P_CHAIN_TN64); }
     }
 #undef DI2P_CHAIN_LAUNCH
     DI2P_RETURN_LAUNCH();
+}
+
+// What di2p_point_chain would launch on a device of `cus` compute units (host code: nothing is launched): the launch entry's own chain_route.
+// out[0..7] = M, K-step of layer 0, layers, column blocks of 32 per wave trip, nblk (trips per frame), total (trips), wgs (workgroups of 4 waves),
+// workgroups per compute unit chosen.
+extern "C" int di2p_point_chain_route(int M, int K0, int layers, int B, int N, int cus, int32_t* out) {
+    DI2P_CHECK_ARG(out && (M == 32 || M == 64) && K0 >= 1 && K0 <= M && (layers == 2 || layers == 3) && B >= 1 && N >= 1 && cus >= 1, "bad args");
+    const ChainRoute rt = chain_route(M, K0, layers == 3, B, N, cus);
+    DI2P_CHECK_ARG(rt.total < (1ll << 30), "too many column blocks");
+    out[0] = M; out[1] = rt.ks0; out[2] = rt.layers; out[3] = rt.tn; out[4] = rt.nblk; out[5] = (int)rt.total; out[6] = rt.wgs; out[7] = rt.w;
+    return 0;
+}
+
+// What di2p_point_head would launch on a device of `cus` compute units (host code): the launch entry's own head_route.  c0: channels of the first
+// source; reg_range: every source's channels * row_stride * 4 is below 2^31 (the buffer-descriptor range); g33: both gathered tables given with k = 3.
+// out[0..5] = kernel (0 LDS-tile, 1 wave-autonomous head_reg), G33, columns per block, nblk (blocks per frame), total, wgs.
+extern "C" int di2p_point_head_route(int K0, int n_src, int c0, int reg_range, int g33, int B, int N, int cus, int32_t* out) {
+    DI2P_CHECK_ARG(out && K0 >= 1 && n_src >= 1 && n_src <= DI2P_MAX_SRC && c0 >= 1 && c0 <= K0 && B >= 1 && N >= 4 && N % 4 == 0 && cus >= 1, "bad args");
+    const HeadRoute rt = head_route(K0, n_src, c0, reg_range != 0, g33 != 0, B, N, cus);
+    DI2P_CHECK_ARG(!rt.reg || rt.total < (1ll << 30), "too many column blocks");
+    out[0] = rt.reg; out[1] = rt.g33; out[2] = rt.bn; out[3] = rt.nblk; out[4] = (int)rt.total; out[5] = rt.wgs;
+    return 0;
 }
 
 extern "C" int di2p_batch_gemv(const float* Wt, int M, int k0, const float* v, int Kv, float* out, int B, void* stream) {

@@ -435,6 +435,42 @@ __global__ __launch_bounds__(NW * 64, 2) void wino_reg_kernel(const float* __res
 
 }  // namespace
 
+// The one routing decision of di2p_conv3x3_winograd: kernel, co-block, K-step, waves and grid of a launch (the knobs wino_cob, wino_kc and
+// wino_reg included).  The entry point runs what this returns; di2p_winograd_route reports it.
+struct WinoRoute { int reg, cob, kc, waves, n_tb, tiles, n_cb, grid, by_co; };
+static WinoRoute wino_route(int B, int Cin, int H, int W, int Cout) {
+    WinoRoute rt{};
+    const int TH = (H + 1) / 2, TW = (W + 1) / 2;
+    const long long total = (long long)B * TH * TW;
+    const int n_tb = di2p_cdiv(total, WG_TILES);
+    // co-block 64 when that still leaves >= 3 workgroups per CU, else 32 (more, smaller workgroups for the small late stages)
+    const long long opt = di2p_opt(DI2P_OPT_WINO_COB);
+    const bool cob64 = opt ? (opt == 64 && Cout % 64 == 0) : (Cout % 64 == 0 && (long long)n_tb * (Cout / 64) >= 768);
+    const long long reg_opt = di2p_opt(DI2P_OPT_WINO_REG);      // 0: automatic, 1: LDS-panel kernel, 2: register-resident, 4 waves, 3: 2 waves
+    // automatic: the register-resident kernel wherever its 64-tile workgroups number at least REG_MIN_WGS (ResNet stages 1-3).  Alone, the LDS-panel
+    // kernel is level or ahead from stage 2 on (stage 3: 85 vs 93 us), but in the 8-stream pipeline the register-resident kernel's
+    // 16 KB of LDS per workgroup (against 32-64 KB) lets it share a CU with the pose solver's workgroups: +2.8 % frames/s with the
+    // threshold at 300 instead of 1024 (round 3); at the 512-channel stage (192 workgroups) the LDS-panel kernel stays
+    constexpr long long REG_MIN_WGS = 256;      // all but the 512-channel stage
+    const bool reg_auto = reg_opt == 0 && (long long)di2p_cdiv(total, 64) * (Cout / 32) >= REG_MIN_WGS;
+    if ((reg_opt >= 2 || reg_auto) && Cin % 4 == 0) {
+        rt.reg = 1; rt.cob = 32; rt.kc = 0;
+        rt.waves = reg_opt == 3 ? 2 : 4;
+        rt.tiles = rt.waves * 16;
+        rt.n_tb = di2p_cdiv(total, rt.tiles); rt.n_cb = Cout / 32;
+        rt.grid = di2p_cdiv(rt.n_tb, 8) * 8 * rt.n_cb;
+        return rt;
+    }
+    const long long kc_opt = di2p_opt(DI2P_OPT_WINO_KC);
+    const bool kc4 = kc_opt ? kc_opt == 4 : Cin <= 256;      // measured in the pipeline: K-step 4 wins up to 256 input channels, 8 at 512
+    rt.cob = cob64 ? 64 : 32; rt.kc = kc4 ? 4 : 8; rt.waves = 4; rt.n_tb = n_tb; rt.tiles = WG_TILES;
+    rt.n_cb = Cout / rt.cob;
+    // co-blocks over the XCDs where U is larger than 2 MB (else tile blocks); needs n_cb % 8 == 0 (the kernel divides by n_cb / 8)
+    rt.by_co = rt.n_cb % 8 == 0 && (long long)16 * Cin * Cout * 4 > (2ll << 20);
+    rt.grid = rt.by_co ? rt.n_cb * n_tb : di2p_cdiv(n_tb, 8) * 8 * rt.n_cb;
+    return rt;
+}
+
 extern "C" int di2p_winograd_weight_transform(const float* weight, float* U, int Cin, int Cout, void* stream) {
     DI2P_CHECK_ARG(weight && U && Cin >= 1 && Cout >= 1, "bad args");
     hipLaunchKernelGGL(wino_weight_kernel<false>, dim3(di2p_cdiv((long long)Cin * Cout, 256)), dim3(256), 0, (hipStream_t)stream, weight, U, Cin, Cout);
@@ -462,44 +498,38 @@ extern "C" int di2p_conv3x3_winograd(const float* x, const float* U, const float
     const int TH = (H + 1) / 2, TW = (W + 1) / 2;
     const long long total = (long long)B * TH * TW;
     DI2P_CHECK_ARG(total < (1ll << 31), "too many tiles");
-    const int n_tb = di2p_cdiv(total, WG_TILES);
-    // co-block 64 when that still leaves >= 3 workgroups per CU, else 32 (more, smaller workgroups for the small late stages)
-    const long long opt = di2p_opt(DI2P_OPT_WINO_COB);
-    const bool cob64 = opt ? (opt == 64 && Cout % 64 == 0) : (Cout % 64 == 0 && (long long)n_tb * (Cout / 64) >= 768);
+    const WinoRoute rt = wino_route(B, Cin, H, W, Cout);
+    const int n_tb = rt.n_tb, n_cb = rt.n_cb;
     hipStream_t st = (hipStream_t)stream;
-#define DI2P_WINO_LAUNCH(COBV, KCV)                                                                                                          \
-    do {                                                                                                                                     \
-        const int n_cb = Cout / COBV;                                                                                                        \
-        /* co-blocks over the XCDs where U is larger than 2 MB (else tile blocks); needs n_cb % 8 == 0 (the kernel divides by n_cb / 8) */  \
-        const int by_co = n_cb % 8 == 0 && (long long)16 * Cin * Cout * 4 > (2ll << 20);                                                     \
-        const int grid = by_co ? n_cb * n_tb : di2p_cdiv(n_tb, 8) * 8 * n_cb;                                                                \
-        const size_t lds = WinoLds<COBV, KCV>::TOTAL * sizeof(float);                                                                        \
-        if (di2p_allow_dynamic_lds((const void*)wino_conv_kernel<COBV, KCV>, lds, __func__)) return -1;                                      \
-        hipLaunchKernelGGL((wino_conv_kernel<COBV, KCV>), dim3(grid), dim3(256), lds, st, x, U, scale, shift, residual, y, Cin, H, W, Cout, \
-                           TH, TW, (int)total, n_tb, n_cb, relu, by_co);                                                                     \
-    } while (0)
-    const long long reg_opt = di2p_opt(DI2P_OPT_WINO_REG);      // 0: automatic, 1: LDS-panel kernel, 2: register-resident, 4 waves, 3: 2 waves
-    // automatic: the register-resident kernel wherever its 64-tile workgroups number at least REG_MIN_WGS (ResNet stages 1-3).  Alone, the LDS-panel
-    // kernel is level or ahead from stage 2 on (stage 3: 85 vs 93 us), but in the 8-stream pipeline the register-resident kernel's
-    // 16 KB of LDS per workgroup (against 32-64 KB) lets it share a CU with the pose solver's workgroups: +2.8 % frames/s with the
-    // threshold at 300 instead of 1024 (round 3); at the 512-channel stage (192 workgroups) the LDS-panel kernel stays
-    constexpr long long REG_MIN_WGS = 256;      // all but the 512-channel stage
-    const bool reg_auto = reg_opt == 0 && (long long)di2p_cdiv(total, 64) * (Cout / 32) >= REG_MIN_WGS;
-    if ((reg_opt >= 2 || reg_auto) && Cin % 4 == 0) {
-        const int nw = reg_opt == 3 ? 2 : 4;
-        const int n_tb_r = di2p_cdiv(total, nw * 16), n_cb = Cout / 32;
-        const int grid = di2p_cdiv(n_tb_r, 8) * 8 * n_cb;
-        if (nw == 4) hipLaunchKernelGGL(wino_reg_kernel<4>, dim3(grid), dim3(256), 0, st, x, U, scale, shift, residual, y, Cin, H, W, Cout, TH, TW, (int)total, n_tb_r, n_cb, relu);
-        else hipLaunchKernelGGL(wino_reg_kernel<2>, dim3(grid), dim3(128), 0, st, x, U, scale, shift, residual, y, Cin, H, W, Cout, TH, TW, (int)total, n_tb_r, n_cb, relu);
+    if (rt.reg) {
+        if (rt.waves == 4) hipLaunchKernelGGL(wino_reg_kernel<4>, dim3(rt.grid), dim3(256), 0, st, x, U, scale, shift, residual, y, Cin, H, W, Cout, TH, TW, (int)total, n_tb, n_cb, relu);
+        else hipLaunchKernelGGL(wino_reg_kernel<2>, dim3(rt.grid), dim3(128), 0, st, x, U, scale, shift, residual, y, Cin, H, W, Cout, TH, TW, (int)total, n_tb, n_cb, relu);
         DI2P_RETURN_LAUNCH();
     }
-    const long long kc_opt = di2p_opt(DI2P_OPT_WINO_KC);
-    const bool kc4 = kc_opt ? kc_opt == 4 : Cin <= 256;      // measured in the pipeline: K-step 4 wins up to 256 input channels, 8 at 512
-    if (cob64) {
-        if (kc4) DI2P_WINO_LAUNCH(64, 4); else DI2P_WINO_LAUNCH(64, 8);
+#define DI2P_WINO_LAUNCH(COBV, KCV)                                                                                                          \
+    do {                                                                                                                                     \
+        const size_t lds = WinoLds<COBV, KCV>::TOTAL * sizeof(float);                                                                        \
+        if (di2p_allow_dynamic_lds((const void*)wino_conv_kernel<COBV, KCV>, lds, __func__)) return -1;                                      \
+        hipLaunchKernelGGL((wino_conv_kernel<COBV, KCV>), dim3(rt.grid), dim3(256), lds, st, x, U, scale, shift, residual, y, Cin, H, W, Cout, \
+                           TH, TW, (int)total, n_tb, n_cb, relu, rt.by_co);                                                                  \
+    } while (0)
+    if (rt.cob == 64) {
+        if (rt.kc == 4) DI2P_WINO_LAUNCH(64, 4); else DI2P_WINO_LAUNCH(64, 8);
     } else {
-        if (kc4) DI2P_WINO_LAUNCH(32, 4); else DI2P_WINO_LAUNCH(32, 8);
+        if (rt.kc == 4) DI2P_WINO_LAUNCH(32, 4); else DI2P_WINO_LAUNCH(32, 8);
     }
 #undef DI2P_WINO_LAUNCH
     DI2P_RETURN_LAUNCH();
+}
+
+// What di2p_conv3x3_winograd would launch (host code: nothing is launched): the launch entry's own wino_route.
+// out[0..7] = kernel (0 LDS-panel, 1 register-resident), output channels per workgroup, K-step (0 for the register-resident kernel), waves per
+// workgroup, tile blocks, tiles per block, co-blocks, workgroups.
+extern "C" int di2p_winograd_route(int B, int Cin, int H, int W, int Cout, int32_t* out) {
+    DI2P_CHECK_ARG(out && B >= 1 && Cin >= 8 && Cin % 8 == 0 && Cout >= 32 && Cout % 32 == 0 && H >= 1 && W >= 4 && W % 2 == 0,
+                   "needs Cin % 8 == 0, Cout % 32 == 0 and an even width >= 4");
+    DI2P_CHECK_ARG((long long)B * ((H + 1) / 2) * ((W + 1) / 2) < (1ll << 31), "too many tiles");
+    const WinoRoute rt = wino_route(B, Cin, H, W, Cout);
+    out[0] = rt.reg; out[1] = rt.cob; out[2] = rt.kc; out[3] = rt.waves; out[4] = rt.n_tb; out[5] = rt.tiles; out[6] = rt.n_cb; out[7] = rt.grid;
+    return 0;
 }

@@ -737,6 +737,60 @@ def rc_route(kind, Z, rows, cols, R, a_vec=False, b_vec=False):
     return dict(zip(RC_ROUTE_FIELDS, (int(v) for v in out)))
 
 
+PW_ROUTE_FIELDS = ("vec", "bm", "bn", "dense", "depth", "bk")
+CONV2D_ROUTE_FIELDS = ("kernel", "bm", "bn", "bk", "variant", "depth", "splits")
+CONV2D_KERNELS = ("scalar", "vec", "stem_row")
+WINO_ROUTE_FIELDS = ("reg", "cob", "kc", "waves", "n_tb", "tiles", "n_cb", "grid")
+CHAIN_ROUTE_FIELDS = ("M", "ks0", "layers", "tn", "nblk", "total", "wgs", "w")
+HEAD_ROUTE_FIELDS = ("reg", "g33", "bn", "nblk", "total", "wgs")
+
+
+def _route(name, fields, *args):
+    out = (ctypes.c_int32 * len(fields))()
+    _lib.call(name, *(int(a) for a in args), out)
+    return dict(zip(fields, (int(v) for v in out)))
+
+
+def pointwise_route(M, K, N, B=1, dense=True, wt_aligned=True):
+    """What di2p_pointwise_gemm would launch (di2p_pointwise_route: the entry's own routing function; host code, no GPU needed): a dict of
+    PW_ROUTE_FIELDS -- stager (vec 0 scalar / 1 16-byte), tile bm x bn, the dense loader, prefetch depth and K-step.  dense: every source
+    dense with strides % 4 == 0 and a 16-byte aligned base; wt_aligned: Wt 16-byte aligned."""
+    return _route("di2p_pointwise_route", PW_ROUTE_FIELDS, M, K, N, B, bool(dense), bool(wt_aligned))
+
+
+def conv2d_route(x_shape, Cout, KH, KW, stride, pad, tap_major=False, x_aligned=True, wt_aligned=True, workspace_bytes=0):
+    """What di2p_conv2d / di2p_conv2d_ws would launch (di2p_conv2d_route; host code): a dict of CONV2D_ROUTE_FIELDS -- kernel (an index
+    into CONV2D_KERNELS), tile, K-step, stride variant (1, 2, 22 = aligned windows; 0 off the 16-byte stager), prefetch depth and the
+    K-slices actually used with a 16-byte aligned workspace of workspace_bytes (0: none)."""
+    B, Cin, H, W = x_shape
+    return _route("di2p_conv2d_route", CONV2D_ROUTE_FIELDS, B, Cin, H, W, Cout, KH, KW, stride, pad, bool(tap_major), bool(x_aligned),
+                  bool(wt_aligned), workspace_bytes)
+
+
+def conv2d_workspace_bytes(x_shape, Cout, KH, KW, stride, pad, tap_major=False):
+    """The split-K workspace conv2d wants for this shape (di2p_conv2d_workspace_bytes; 0: no split, or a shape conv2d refuses)."""
+    B, Cin, H, W = x_shape
+    return int(_lib.load().di2p_conv2d_workspace_bytes(int(B), int(Cin), int(H), int(W), int(Cout), int(KH), int(KW), int(stride), int(pad),
+                                                       int(bool(tap_major))))
+
+
+def winograd_route(x_shape, Cout):
+    """What di2p_conv3x3_winograd would launch (di2p_winograd_route; host code): a dict of WINO_ROUTE_FIELDS -- kernel (reg 0 LDS-panel /
+    1 register-resident), output channels per workgroup, K-step, waves, tile blocks, tiles per block, co-blocks, workgroups."""
+    B, Cin, H, W = x_shape
+    return _route("di2p_winograd_route", WINO_ROUTE_FIELDS, B, Cin, H, W, Cout)
+
+
+def point_chain_route(M, K0, layers, B, N, cus):
+    """What di2p_point_chain would launch on `cus` compute units (di2p_point_chain_route; host code): a dict of CHAIN_ROUTE_FIELDS."""
+    return _route("di2p_point_chain_route", CHAIN_ROUTE_FIELDS, M, K0, layers, B, N, cus)
+
+
+def point_head_route(K0, n_src, c0, B, N, cus, g33=False, reg_range=True):
+    """What di2p_point_head would launch on `cus` compute units (di2p_point_head_route; host code): a dict of HEAD_ROUTE_FIELDS."""
+    return _route("di2p_point_head_route", HEAD_ROUTE_FIELDS, K0, n_src, c0, bool(reg_range), bool(g33), B, N, cus)
+
+
 def conv3x3_x3(x, Wp, Cout, scale, shift, stride, relu, residual=None, downsample=None, cfg=-1):
     """3x3 / pad 1 convolution on the bf16 matrix instructions with exact three-way fp32 splits (di2p_conv3x3_x3):
     y = relu?(scale * conv(x) + shift + residual).  Wp = bf16x3_pack(tap-major Wt[9 Cin, Cout]).  stride 2 takes

@@ -235,6 +235,31 @@ int di2p_winograd_weight_transform(const float* weight, float* U, int Cin, int C
 int di2p_winograd_weight_transform_dgrad(const float* weight, float* U, int Cin_g, int Cout_g, void* stream);
 int di2p_conv3x3_winograd(const float* x, const float* U, const float* scale, const float* shift, const float* residual, float* y, int B,
                           int Cin, int H, int W, int Cout, int relu, void* stream);
+/* Routing queries of the fp32-MFMA inference family (additive; detect by symbol): which kernel instance a call would launch -- host code, each
+ * launch entry's own routing function, nothing is launched and no device is needed (for tests and tools).  Each honours the knobs its entry
+ * reads.  0 on success, -1 (di2p_last_error) on sizes the entry itself refuses.
+ *   di2p_pointwise_route (di2p_pointwise_gemm; knobs pw_novec, conv_depth1).  dense: every source is DI2P_SRC_DENSE with row_stride % 4 == 0,
+ *     batch_stride % 4 == 0 and a 16-byte aligned base; wt_aligned: Wt 16-byte aligned.
+ *     out[0..5] = stager (0 scalar, 1 16-byte), tile rows, tile columns, dense loader, prefetch depth (1 / 2), K-step.
+ *   di2p_conv2d_route (di2p_conv2d / _ws; knobs conv_nosplit, conv_s2scalar, conv_depth1).  x_aligned / wt_aligned: x / Wt 16-byte aligned;
+ *     workspace_bytes: size of a 16-byte aligned workspace, 0 for none.
+ *     out[0..6] = kernel (0 scalar stager, 1 16-byte stager, 2 the 7x7/2 row-decoding stager), tile rows, tile columns, K-step, stride
+ *     variant (0 n/a, 1, 2, 22 = stride 2 through aligned 8-float windows), prefetch depth, K-slices actually used (1: no split-K).
+ *   di2p_winograd_route (di2p_conv3x3_winograd; knobs wino_cob, wino_kc, wino_reg).
+ *     out[0..7] = kernel (0 LDS-panel, 1 register-resident), output channels per workgroup, K-step (0: register-resident), waves, tile
+ *     blocks, tiles per block, co-blocks, workgroups.
+ *   di2p_point_chain_route (di2p_point_chain) on a device of `cus` compute units (the launch passes its own count).  layers: 2 or 3.
+ *     out[0..7] = M, K-step of layer 0, layers, 32-column blocks per wave trip, nblk (trips per frame), total (trips), wgs (workgroups of
+ *     4 waves), workgroups per compute unit.
+ *   di2p_point_head_route (di2p_point_head; knob head_reg) on `cus` compute units.  c0: channels of source 0; reg_range: every source's
+ *     channels * row_stride * 4 < 2^31; g33: both gathered tables given with k = 3.
+ *     out[0..5] = kernel (0 LDS-tile, 1 wave-autonomous), G33 epilogue, columns per block, nblk (blocks per frame), total, wgs. */
+int di2p_pointwise_route(int M, int K, int N, int B, int dense, int wt_aligned, int32_t* out);
+int di2p_conv2d_route(int B, int Cin, int H, int W, int Cout, int KH, int KW, int stride, int pad, int tap_major, int x_aligned,
+                      int wt_aligned, long long workspace_bytes, int32_t* out);
+int di2p_winograd_route(int B, int Cin, int H, int W, int Cout, int32_t* out);
+int di2p_point_chain_route(int M, int K0, int layers, int B, int N, int cus, int32_t* out);
+int di2p_point_head_route(int K0, int n_src, int c0, int reg_range, int g33, int B, int N, int cus, int32_t* out);
 /* The coarse per-point head (per_point_pn, models/networks_united.py:57-74 applied at :188-197: 736 -> 128 -> 128 -> P) in ONE launch on the bf16
  * matrix instructions with exact three-way fp32 splits, wave-autonomous (a wave keeps all 128 channels of 32 points in registers through the three
  * layers).  Layer 0 = the dense channels of the point (two sources f32[B, ch, N], channels multiples of 16) through W0 PLUS the per-node products

@@ -73,6 +73,49 @@ def test_argument_errors_are_reported_not_crashed():
     _lib.call("di2p_index_max_forward", None, None, None, 0, 4, 10, 8, None, None)
 
 
+def test_conv2d_refuses_a_filter_that_does_not_fit_the_padded_input():
+    # in a thread of its own: di2p_last_error is per thread
+    import concurrent.futures
+    with concurrent.futures.ThreadPoolExecutor(1) as ex:
+        ex.submit(_conv2d_empty_output_checks).result()
+
+
+def _conv2d_empty_output_checks():
+    """A filter larger than the padded input has no output at ANY stride (C's truncating division gives (H + 2 pad - KH) / stride + 1 = 1
+    for -stride < H + 2 pad - KH < 0): di2p_conv2d, di2p_conv2d_ws, di2p_conv2d_workspace_bytes and di2p_conv2d_route refuse it before any
+    device call -- the addresses below are made up and never dereferenced."""
+    from deepi2p_amd import _lib, ops
+    lib = _lib.load()
+    fake = 4096
+
+    def conv(H, W, KH, KW, stride, pad, ws=False, Cin=3, Cout=4, tap_major=0):
+        args = (fake, fake, fake, fake, None, fake, 1, Cin, H, W, Cout, KH, KW, stride, pad, 0, tap_major)
+        if ws:
+            _lib.call("di2p_conv2d_ws", *args, fake, 1 << 30, None)
+        else:
+            _lib.call("di2p_conv2d", *args, None)
+
+    # (H, W, KH, KW, stride, pad): too tall, too wide, both; by one and by stride - 1; with padding that still does not reach
+    empty = [(2, 8, 3, 3, 2, 0), (8, 2, 3, 3, 2, 0), (2, 2, 3, 3, 2, 0), (1, 8, 3, 1, 3, 0), (8, 4, 1, 7, 4, 1), (5, 5, 7, 7, 2, 0), (3, 3, 7, 7, 2, 1),
+             (2, 8, 3, 3, 1, 0), (1, 1, 4, 4, 3, 1), (6, 6, 9, 9, 100, 1)]
+    for H, W, KH, KW, stride, pad in empty:
+        assert H + 2 * pad < KH or W + 2 * pad < KW
+        for ws in (False, True):
+            with pytest.raises(_lib.DeepI2PHipError, match="conv2d_impl: empty output"):
+                conv(H, W, KH, KW, stride, pad, ws)
+        assert lib.di2p_conv2d_workspace_bytes(1, 3, H, W, 4, KH, KW, stride, pad, 0) == 0
+        with pytest.raises(_lib.DeepI2PHipError, match="di2p_conv2d_route: empty output"):
+            ops.conv2d_route((1, 3, H, W), 4, KH, KW, stride, pad)
+    # the same refusal on a shape that would split K (the workspace query must not size a workspace for it): Cin 512, Cout 128, tap-major
+    assert lib.di2p_conv2d_workspace_bytes(1, 512, 2, 9, 128, 3, 3, 2, 0, 1) == 0
+    assert lib.di2p_conv2d_workspace_bytes(1, 512, 3, 9, 128, 3, 3, 2, 0, 1) == 3 * 128 * 4 * 4       # ... and does for the smallest that fits
+    with pytest.raises(_lib.DeepI2PHipError, match="empty output"):
+        conv(2, 9, 3, 3, 2, 0, ws=True, Cin=512, Cout=128, tap_major=1)
+    # a filter that exactly fits is one output pixel, at any stride: the route query answers (nothing is launched)
+    for H, W, KH, KW, stride, pad in ((3, 3, 3, 3, 2, 0), (1, 1, 3, 3, 5, 1), (7, 7, 7, 7, 2, 0), (2, 3, 2, 3, 9, 0)):
+        assert ops.conv2d_route((1, 3, H, W), 4, KH, KW, stride, pad)["kernel"] == 0
+
+
 def test_pointwise_entry_points_share_their_argument_checks():
     # in a thread of its own: di2p_last_error is per thread, and the export test above expects "ok" on the main thread
     import concurrent.futures
