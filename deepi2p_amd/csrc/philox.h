@@ -2,6 +2,7 @@
 // definition, so that a stream keeps its bits wherever it is drawn.  The fourth counter word is the stream tag:
 //   0, 1 restart list   2 random choice   3 dropout keep-mask   4 per-frame sample draws   5 point / intensity / normal jitter
 //   6 point shuffle (range filter of the Oxford loader)   7 synthetic-world scan: dropout, range and intensity noise (world.hip)
+//   8 synthetic-world push-broom profiles: dropout, range and reflectance noise (world.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -3,6 +3,7 @@
 // and the workspace helpers); everything is in the anonymous namespace, so each of them gets its own offsets_kernel.  Integer code throughout.
 //   check_offsets2   (device, wave-wide) the acceptance of one entry's offsets on both levels
 //   wave_prefix      (device, wave-wide) chunked exclusive prefix over a range of int counts, 64-bit lanes, clamped at 2^31 - 1
+//   frame_of         (device) the entry a row or unit of a non-decreasing offset table belongs to, by binary search
 //   offsets_kernel   one wave: exclusive prefix over the entries' totals, the final status
 // and the status codes, the workspace helpers and wave_id.
 #pragma once
@@ -64,6 +65,16 @@ __device__ __forceinline__ int wave_prefix(const int* __restrict__ cnt, long lon
         run = min(run + __shfl(v, 63), (long long)0x7fffffff);          // a chunk adds at most 64 * (2^31 - 1): no overflow of the 64-bit sum
     }
     return (int)run;
+}
+
+// largest b in [0, B) with off[b] <= i (off non-decreasing)
+__device__ __forceinline__ int frame_of(const int* __restrict__ off, int B, long long i) {
+    int lo = 0, hi = B - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if ((long long)off[mid] <= i) lo = mid; else hi = mid - 1;
+    }
+    return lo;
 }
 
 // One wave: out_offsets over the entries, the final status.  An entry above max_frame_points rows, or whose rows would pass cap, has none.

@@ -194,16 +194,6 @@ __global__ __launch_bounds__(WAVES * 64) void write_kernel(const double* __restr
     }
 }
 
-// largest b in [0, B) with off[b] <= i (off non-decreasing)
-__device__ __forceinline__ int frame_of(const int* __restrict__ off, int B, long long i) {
-    int lo = 0, hi = B - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if ((long long)off[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 // Stage E: q = G_cam[b] . (mean, 1) in fp64 (ascending k), the record row (q, intensity) rounded once.
 __global__ __launch_bounds__(256) void to_camera_kernel(const double* __restrict__ cen, const float* __restrict__ inten, const int* __restrict__ off,
                                                         const double* __restrict__ G_cam, int B, int cap, float* __restrict__ out) {

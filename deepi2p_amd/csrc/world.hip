@@ -17,6 +17,7 @@
 //                   two ends of a workgroup's range: a frame may start off a dword when 3 H0 W0 is no multiple of 4)
 //   scan: rays_kernel (trace + keep rule + noise -> a full row per ray, the wave's keep mask, the workgroup's count), prefix_kernel (one
 //   wave per frame, ragged2.h's wave_prefix), scan_offsets_kernel, write_kernel (stable compaction in ray order)
+//   push-broom profiles (a 2-D laser with one pose per profile, one scene per sub-map; stream tag 8): the section further down
 #include "common.h"
 #include "philox.h"
 #include "ragged2.h"
@@ -303,6 +304,146 @@ __global__ __launch_bounds__(BLOCK) void write_kernel(int R, const float4* __res
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- push-broom profiles
+// Ray g = s * beams + k: beam k of profile s, profiles of sub-map b = [sub_off[b], sub_off[b+1]), one scene per sub-map.  The rays of a
+// batch are ONE line of S * beams rays cut into parts of BLOCK; a part that holds profiles of several sub-maps stages their tables one
+// after the other.  Compaction is global and stable (profile after profile, beam order), so scan_offsets[s] is simply the number of kept
+// rays before ray s * beams:
+//   accept_kernel         one wave: the leading sub-maps whose offsets are acceptable (ragged2.h's rule, outer level), status
+//   profile_rays_kernel   trace + keep rule + noise -> the row of every kept ray, the wave's keep mask, the part's count
+//   group_prefix_kernel   one wave per GROUP parts: wave_prefix of the part counts inside the group, the group's total
+//   top_prefix_kernel     one wave: wave_prefix over the groups
+//   profile_offsets_kernel  one thread per profile: scan_offsets and out_count from the prefixes and the mask of the wave ray s * beams is in
+//   profile_write_kernel  stable compaction of the parked rows
+constexpr unsigned TAG_PROFILES = 8u;
+constexpr int GROUP = 1024;          // parts of one group_prefix_kernel wave (16 chunks of wave_prefix)
+
+struct PLayout { size_t rows, mask, part_cnt, part_off, group_cnt, group_off, head, total; };
+
+PLayout playout(long long R) {
+    PLayout L;
+    Take take;
+    const size_t parts = (size_t)di2p_cdiv(R, (long long)BLOCK), groups = (size_t)di2p_cdiv((long long)parts, (long long)GROUP);
+    L.rows = take(24 * (size_t)R);
+    L.mask = take(8 * parts * (BLOCK / 64));
+    L.part_cnt = take(4 * parts); L.part_off = take(4 * parts);
+    L.group_cnt = take(4 * groups); L.group_off = take(4 * groups);
+    L.head = take(8);          // n_ok (accepted sub-maps), total (kept rays)
+    L.total = take.o;
+    return L;
+}
+
+// Sub-map b is accepted iff sub_off[0 .. b+1] is a non-decreasing sequence in [0, S_cap] that starts at 0: the accepted ones are the first
+// n_ok, they share no profile and cover the profiles [0, sub_off[n_ok]).
+__global__ __launch_bounds__(64) void accept_kernel(const int* __restrict__ sub_off, int B, int S_cap, int* __restrict__ status, int* __restrict__ head) {
+    const int lane = threadIdx.x;
+    int first_bad = B;
+    for (int j = lane; j < B; j += 64) {
+        const int o0 = sub_off[j], o1 = sub_off[j + 1];
+        if ((o0 < 0 || o1 < o0 || o1 > S_cap || (j == 0 && o0 != 0)) && j < first_bad) first_bad = j;
+    }
+    for (int o = 32; o; o >>= 1) first_bad = min(first_bad, __shfl_xor(first_bad, o));
+    for (int j = lane; j < B; j += 64) status[j] = j < first_bad ? ST_OK : ST_OFFSETS;
+    if (lane == 0) head[0] = first_bad;
+}
+
+// The draws are Philox counter (k, frame0 + s, j, 8): block 0 the dropout uniform, block 1 the range noise, block 2 the reflectance noise.
+__global__ __launch_bounds__(BLOCK) void profile_rays_kernel(const double* __restrict__ prims, const int* __restrict__ count, const int* __restrict__ sub_off,
+                                                             const int* __restrict__ head, const double* __restrict__ laser_to_world,
+                                                             const double* __restrict__ beam, int P, int beams, ScanOpt o, double* __restrict__ rows,
+                                                             unsigned long long* __restrict__ masks, int* __restrict__ part_cnt) {
+    __shared__ double tab[MAX_PRIMS * SLOTS];
+    __shared__ int wc[BLOCK / 64];
+    const int n_ok = head[0];
+    const long long R = n_ok > 0 ? (long long)sub_off[n_ok] * beams : 0;          // rays of the accepted sub-maps, < 2^31 (checked on the host)
+    const long long g0 = (long long)blockIdx.x * BLOCK, g = g0 + threadIdx.x;
+    bool keep = false;
+    if (g0 < R) {          // the same in every thread, and so is the loop: its barriers are met by all of them
+        const int s = (int)(g / beams), k = (int)(g - (long long)s * beams);
+        const int b_last = frame_of(sub_off, n_ok, (min(R, g0 + BLOCK) - 1) / beams);
+        for (int b = frame_of(sub_off, n_ok, g0 / beams); b <= b_last; ++b) {
+            const int p0 = sub_off[b], p1 = sub_off[b + 1];
+            if (p0 == p1) continue;
+            __syncthreads();          // the previous sub-map's table may still be read
+            const int n = stage_table(prims, count, b, P, tab);
+            if (g >= R || s < p0 || s >= p1) continue;
+            const double c = beam[2 * k], sn = beam[2 * k + 1];
+            const double* M = laser_to_world + 16 * (long long)s;
+            const Ray ray = make_ray(M[3], M[7], M[11], __dadd_rn(__dadd_rn(__dmul_rn(M[0], c), __dmul_rn(M[1], sn)), __dmul_rn(M[2], 0.0)),
+                                     __dadd_rn(__dadd_rn(__dmul_rn(M[4], c), __dmul_rn(M[5], sn)), __dmul_rn(M[6], 0.0)),
+                                     __dadd_rn(__dadd_rn(__dmul_rn(M[8], c), __dmul_rn(M[9], sn)), __dmul_rn(M[10], 0.0)));
+            const Hit h = trace(tab, n, ray);
+            const unsigned long long seed = o.seed_dev ? *o.seed_dev : o.seed;
+            const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32), f = (unsigned)(o.frame0 + s);
+            const U4 d0 = philox4x32_10(U4{(unsigned)k, f, 0u, TAG_PROFILES}, k0, k1);
+            keep = h.t < o.max_range && u53(d0.x, d0.y) >= o.dropout;          // decided before the noise
+            double t = h.t, refl = h.prim >= 0 ? tab[SLOTS * h.prim + 10] : 0.0;
+            if (o.range_sigma > 0.0) t = __dadd_rn(t, __dmul_rn(o.range_sigma, gauss(philox4x32_10(U4{(unsigned)k, f, 1u, TAG_PROFILES}, k0, k1))));
+            if (o.intensity_sigma > 0.0)
+                refl = __dadd_rn(refl, __dmul_rn(o.intensity_sigma, gauss(philox4x32_10(U4{(unsigned)k, f, 2u, TAG_PROFILES}, k0, k1))));
+            if (keep) {
+                double* row = rows + 3 * g;
+                row[0] = __dmul_rn(t, c); row[1] = __dmul_rn(t, sn); row[2] = clamp255(__dmul_rn(255.0, refl));
+            }
+        }
+    }
+    const unsigned long long mask = __ballot(keep);
+    const int w = wave_id();
+    if ((threadIdx.x & 63) == 0) { masks[(long long)blockIdx.x * (BLOCK / 64) + w] = mask; wc[w] = __popcll(mask); }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int c = 0;
+        for (int j = 0; j < BLOCK / 64; ++j) c += wc[j];
+        part_cnt[blockIdx.x] = c;
+    }
+}
+
+__global__ __launch_bounds__(64) void group_prefix_kernel(int parts, const int* __restrict__ part_cnt, int* __restrict__ part_off, int* __restrict__ group_cnt) {
+    const long long j0 = (long long)blockIdx.x * GROUP;
+    const int total = wave_prefix(part_cnt, j0, min(j0 + GROUP, (long long)parts), threadIdx.x, part_off);
+    if (threadIdx.x == 0) group_cnt[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(64) void top_prefix_kernel(int groups, const int* __restrict__ group_cnt, int* __restrict__ group_off, int* __restrict__ head) {
+    const int total = wave_prefix(group_cnt, 0, groups, threadIdx.x, group_off);
+    if (threadIdx.x == 0) head[1] = total;
+}
+
+// kept rays before ray g (g <= parts * BLOCK)
+__device__ __forceinline__ int kept_before(long long g, int parts, const unsigned long long* __restrict__ masks, const int* __restrict__ part_off,
+                                           const int* __restrict__ group_off, int total) {
+    const long long part = g / BLOCK;
+    if (part >= parts) return total;
+    const int w = (int)((g % BLOCK) >> 6), lane = (int)(g & 63);
+    int n = group_off[part / GROUP] + part_off[part];
+    for (int j = 0; j < w; ++j) n += __popcll(masks[part * (BLOCK / 64) + j]);
+    return n + __popcll(masks[part * (BLOCK / 64) + w] & ((1ull << lane) - 1ull));
+}
+
+__global__ __launch_bounds__(BLOCK) void profile_offsets_kernel(int S_cap, int beams, int parts, const unsigned long long* __restrict__ masks,
+                                                                const int* __restrict__ part_off, const int* __restrict__ group_off,
+                                                                const int* __restrict__ head, int* __restrict__ scan_off, int* __restrict__ out_count) {
+    const int s = blockIdx.x * BLOCK + threadIdx.x;
+    if (s > S_cap) return;
+    const int total = head[1];
+    const int here = kept_before((long long)s * beams, parts, masks, part_off, group_off, total);
+    scan_off[s] = here;
+    if (s < S_cap) out_count[s] = kept_before((long long)(s + 1) * beams, parts, masks, part_off, group_off, total) - here;
+}
+
+__global__ __launch_bounds__(BLOCK) void profile_write_kernel(long long R_cap, const double* __restrict__ rows, const unsigned long long* __restrict__ masks,
+                                                              const int* __restrict__ part_off, const int* __restrict__ group_off, double* __restrict__ out) {
+    const long long g = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    const int w = wave_id(), lane = threadIdx.x & 63;
+    const unsigned long long mask = masks[(long long)blockIdx.x * (BLOCK / 64) + w];
+    if (g >= R_cap || !((mask >> lane) & 1ull)) return;
+    int dst = group_off[blockIdx.x / GROUP] + part_off[blockIdx.x] + __popcll(mask & ((1ull << lane) - 1ull));
+    for (int j = 0; j < w; ++j) dst += __popcll(masks[(long long)blockIdx.x * (BLOCK / 64) + j]);
+    const double* src = rows + 3 * g;
+    double* q = out + 3 * (long long)dst;
+    q[0] = src[0]; q[1] = src[1]; q[2] = src[2];
+}
+
 bool finite_nonneg(double x) { return x >= 0.0 && x < 1e300; }
 
 }  // namespace
@@ -371,5 +512,48 @@ extern "C" int di2p_world_render_scan(const double* prims, const int32_t* count,
     hipLaunchKernelGGL(prefix_kernel, dim3(B), dim3(64), 0, st, parts, part_cnt, part_off, out_count);
     hipLaunchKernelGGL(scan_offsets_kernel, dim3(1), dim3(64), 0, st, B, out_count, out_offsets);
     if (R > 0) hipLaunchKernelGGL(write_kernel, dim3(parts, B), dim3(BLOCK), 0, st, R, rows, masks, part_off, out_offsets, (float4*)out_points);
+    DI2P_RETURN_LAUNCH();
+}
+
+extern "C" long long di2p_world_profiles_workspace_bytes(int S_cap, int beams) {
+    if (S_cap < 0 || beams < 0 || (long long)S_cap * beams >= (1ll << 31)) return 0;
+    return (long long)playout((long long)S_cap * beams).total;
+}
+
+extern "C" int di2p_world_render_profiles(const double* prims, const int32_t* count, int B, int P, const int32_t* submap_offsets,
+                                          const double* laser_to_world, const double* beam, int S_cap, int beams, double max_range, double dropout,
+                                          double range_sigma, double reflectance_sigma, unsigned long long seed, const unsigned long long* seed_dev,
+                                          int frame0, double* scan_xyr, int32_t* scan_offsets, int32_t* out_count, int32_t* status, void* workspace,
+                                          void* stream) {
+    DI2P_CHECK_ARG(B >= 0 && S_cap >= 0 && beams >= 0, "bad sizes (B, S_cap, beams >= 0)");
+    DI2P_CHECK_ARG(P >= 0 && P <= MAX_PRIMS, "more than 32 primitives per sub-map");
+    DI2P_CHECK_ARG(B <= 65535 && (long long)S_cap * beams < (1ll << 31), "B above 65535 or a capacity S_cap * beams above 2^31 - 1");
+    DI2P_CHECK_ARG(max_range > 0.0 && max_range < 1e300 && dropout >= 0.0 && dropout <= 1.0 && finite_nonneg(range_sigma) && finite_nonneg(reflectance_sigma),
+                   "max_range > 0, 0 <= dropout <= 1 and sigmas >= 0 are needed");
+    DI2P_CHECK_ARG(frame0 >= 0 && (long long)frame0 + S_cap < (1ll << 31), "frame0 must be >= 0 and frame0 + S_cap below 2^31");
+    DI2P_CHECK_ARG(scan_offsets && workspace && (S_cap == 0 || out_count), "null pointer (scan_offsets, out_count, workspace)");
+    DI2P_CHECK_ARG(B == 0 || (count && submap_offsets && status && (P == 0 || prims)), "null pointer");
+    const long long R = (long long)S_cap * beams;
+    DI2P_CHECK_ARG(B == 0 || R == 0 || (laser_to_world && beam && scan_xyr), "null pointer (laser_to_world, beam, scan_xyr)");
+    DI2P_CHECK_ARG((((uintptr_t)prims | (uintptr_t)laser_to_world | (uintptr_t)beam | (uintptr_t)seed_dev | (uintptr_t)scan_xyr) & 7) == 0 &&
+                       ((uintptr_t)workspace & 255) == 0,
+                   "the tables, laser_to_world, seed_dev and scan_xyr must be 8-byte, workspace 256-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int parts = di2p_cdiv(R, BLOCK), groups = di2p_cdiv(parts, GROUP);
+    const PLayout L = playout(R);
+    double* rows = at<double>(workspace, L.rows);
+    unsigned long long* masks = at<unsigned long long>(workspace, L.mask);
+    int *part_cnt = at<int>(workspace, L.part_cnt), *part_off = at<int>(workspace, L.part_off);
+    int *group_cnt = at<int>(workspace, L.group_cnt), *group_off = at<int>(workspace, L.group_off), *head = at<int>(workspace, L.head);
+    hipLaunchKernelGGL(accept_kernel, dim3(1), dim3(64), 0, st, submap_offsets, B, S_cap, status, head);
+    if (parts > 0) {
+        hipLaunchKernelGGL(profile_rays_kernel, dim3(parts), dim3(BLOCK), 0, st, prims, count, submap_offsets, head, laser_to_world, beam, P, beams,
+                           ScanOpt{max_range, dropout, range_sigma, reflectance_sigma, seed, seed_dev, frame0}, rows, masks, part_cnt);
+        hipLaunchKernelGGL(group_prefix_kernel, dim3(groups), dim3(64), 0, st, parts, part_cnt, part_off, group_cnt);
+    }
+    hipLaunchKernelGGL(top_prefix_kernel, dim3(1), dim3(64), 0, st, groups, group_cnt, group_off, head);
+    hipLaunchKernelGGL(profile_offsets_kernel, dim3(di2p_cdiv(S_cap + 1, BLOCK)), dim3(BLOCK), 0, st, S_cap, beams, parts, masks, part_off, group_off, head,
+                       scan_offsets, out_count);
+    if (parts > 0) hipLaunchKernelGGL(profile_write_kernel, dim3(parts), dim3(BLOCK), 0, st, R, rows, masks, part_off, group_off, scan_xyr);
     DI2P_RETURN_LAUNCH();
 }

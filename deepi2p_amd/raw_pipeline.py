@@ -8,6 +8,7 @@ evaluation mode.  A front end is a subclass that names its staged inputs, its ho
   RawFrameExecutor                        a KITTI scan and a camera frame          raw_prep.RawFramePlan (voxel grid, normals, nearest-raw
                                                                                    intensity, the loader's sample preparation, image path)
   sweep_pipeline.SweepFrameExecutor       a nuScenes sample's sweeps and records   sweeps.NuScenesRawPlan
+  submap_pipeline.OxfordFrameExecutor     an Oxford traversal's LMS profiles       submap.OxfordRawPlan
 """
 import numpy as np
 import torch

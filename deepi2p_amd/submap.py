@@ -264,20 +264,32 @@ class OxfordRawPlan:
         self.submap = SubmapPlan(B, S_cap, P_cap, cap_raw, max_frame_points, voxel, skip_threshold, ground_threshold, dev, ws=self.sample.points.ws)
         self.B = int(B)
         self.status = torch.zeros((max(self.B, 1),), dtype=torch.int32, device=dev)
+        self._T_scan = torch.zeros((max(self.B, 1), 4, 4), dtype=torch.float64, device=dev)
 
     @property
     def seed(self):
         """i64[1] device: the seed slot of the draws (sample_prep.SamplePlan.seed)"""
         return self.sample.seed
 
-    def run(self, scan_xyr, scan_offsets, submap_offsets, poses, present, G_posesource_laser, G_cam, images_u8, K_raw, P_cam_pc, seed=None):
+    @property
+    def T_scan(self):
+        """f64[B,4,4] device: Pr . G_cam of the last run(with_T_scan=True) -- from the sub-map's origin vehicle frame (what build_raw writes)
+        onto the prepared points.  The record is already in the camera's frame, so the draw's Pr alone maps the RECORD onto them."""
+        return self._T_scan[:self.B]
+
+    def run(self, scan_xyr, scan_offsets, submap_offsets, poses, present, G_posesource_laser, G_cam, images_u8, K_raw, P_cam_pc, seed=None,
+            with_T_scan=False):
         """the batch (SubmapPlan.run), images u8[B,H0,W0,3], K_raw f64[B,3,3], P_cam_pc f64[B,4,4] (all device) -> SamplePlan.run's nine
-        tensors + status i32[B], views of the plans' buffers.  seed=None leaves the seed slot as it is (graph replays)."""
+        tensors + status i32[B], views of the plans' buffers.  seed=None leaves the seed slot as it is (graph replays).
+        with_T_scan=True: one launch more (di2p_compose_poses) and T_scan as an eleventh entry: sample_prep.PREPARED."""
         sample_prep._check_images(images_u8, self.B, self.sample.image.raw_hw)
         record, offsets, _ = self.submap.run(scan_xyr, scan_offsets, submap_offsets, poses, present, G_posesource_laser, G_cam)
         out = self.sample.run(record, None, offsets, images_u8, K_raw, P_cam_pc, seed=seed)
         torch.maximum(self.submap.status, self.sample.status, out=self.status)
-        return tuple(out) + (self.status[:self.B],)
+        if not with_T_scan:
+            return tuple(out) + (self.status[:self.B],)
+        call("di2p_compose_poses", ptr(self.sample.table.Pr), ptr(G_cam), self.B, ptr(self._T_scan), stream())
+        return tuple(out) + (self.status[:self.B], self.T_scan)
 
 
 def prepare_oxford_raw(submaps, G_posesource_laser, G_cam, images, K_raw, P_cam_pc, opt, mode="val", seed=0, skip_threshold=None,

@@ -819,6 +819,25 @@ int di2p_world_render_scan(const double* prims, const int32_t* count, int B, int
                            double intensity_sigma, unsigned long long seed, const unsigned long long* seed_dev, int frame0, float* out_points,
                            int32_t* out_offsets, int32_t* out_count, void* workspace, void* stream);
 
+/* ---- (additive, ABI 9; detect by symbol) push-broom profiles of a synthetic world (csrc/world.hip) ----------------------------------------------
+ * di2p_world_render_profiles, six launches, no allocation, no synchronisation: a 2-D laser carried through one scene per SUB-MAP (prims
+ *   f64[B,P,16], count i32[B] as above), with one pose per PROFILE.  Profiles of sub-map b: [submap_offsets[b], submap_offsets[b+1]) (i32[B+1]).
+ *   Beam k of profile s casts R_s . (c_k, s_k, 0) from the translation of laser_to_world[s] (f64[S_cap,4,4], used as given; beam f64[beams,2]
+ *   holds (cos, sin) of the angle in the laser's x-y plane; every entry of the direction is a sum of three rounded products in ascending index,
+ *   the last one with 0).  Kept iff t < max_range and u >= dropout (before the noise); t += range_sigma g; the row is (t c_k, t s_k,
+ *   clip(255 (reflectance + reflectance_sigma g'), 0, 255)) in float64, not rounded to an integer.  u, g, g' from Philox counter
+ *   (k, frame0 + s, 0 | 1 | 2, 8), seed = *seed_dev if seed_dev else seed.
+ *   -> scan_xyr f64[S_cap * beams, 3] (the kept rays in beam order, profile after profile; rows past scan_offsets[S_cap] are not written),
+ *   scan_offsets i32[S_cap+1] (entries past submap_offsets[B] hold the end of the rows), out_count i32[S_cap]: the first two arguments of
+ *   di2p_submap_build.  status i32[B]: 0, or 3 for a sub-map whose offsets submap_offsets[0 .. b+1] are not a non-decreasing sequence in
+ *   [0, S_cap] that starts at 0 (that sub-map and every later one have no rows; nothing is read out of range).
+ *   workspace: di2p_world_profiles_workspace_bytes(S_cap, beams) bytes (0 for bad sizes), 256-byte aligned.  B <= 65535, S_cap * beams < 2^31. */
+long long di2p_world_profiles_workspace_bytes(int S_cap, int beams);
+int di2p_world_render_profiles(const double* prims, const int32_t* count, int B, int P, const int32_t* submap_offsets, const double* laser_to_world,
+                               const double* beam, int S_cap, int beams, double max_range, double dropout, double range_sigma,
+                               double reflectance_sigma, unsigned long long seed, const unsigned long long* seed_dev, int frame0, double* scan_xyr,
+                               int32_t* scan_offsets, int32_t* out_count, int32_t* status, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,6 +3,11 @@
 scenes, on the device) -> raw_prep.RawFramePlan(mode="train") (the KITTI raw stage and the loader's augmentation) -> ClassifierTrainer.optimize.
 
     python tools/train_synthetic.py [--steps 300] [--batch 8] [--points 20480] [--height 160] [--width 512] [--coarse] [--seed 0] [--every 25] [--blind]
+                                    [--dataset oxford [--profiles 300] [--lms-beams 541]]
+
+--dataset oxford is the same loop on a push-broom traversal: per step B fresh streets and drives (world.make_street, make_trajectory) ->
+TraversalPlan (camera frames + LMS profiles of the same scenes) -> submap.OxfordRawPlan(mode="train") (the Oxford raw stage and the loader's
+augmentation) -> ClassifierTrainer.optimize, on 960 x 1280 frames (--height 384 --width 640 is the reference's Oxford image).
 
 Every `--every` steps one line: the loss and the coarse / fine accuracy of the step's own batch (train-mode forward, before the update), and
 the share of inside points of that batch -- 1 minus it is the accuracy of the classifier that answers "outside" for every point.
@@ -31,6 +36,9 @@ def main():
     ap.add_argument("--blind", action="store_true", help="control: uniform-noise frames instead of the rendered ones")
     ap.add_argument("--beams", type=int, default=64)
     ap.add_argument("--azimuths", type=int, default=1800)
+    ap.add_argument("--dataset", choices=("kitti", "oxford"), default="kitti")
+    ap.add_argument("--profiles", type=int, default=300, help="oxford: LMS profiles per sub-map")
+    ap.add_argument("--lms-beams", type=int, default=541, help="oxford: beams per profile")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -46,19 +54,41 @@ def main():
     det.load_state_dict(synthetic.random_state_dict(opt, a.seed))
     tr = ClassifierTrainer(det.to(dev), opt, seed=a.seed)
     rng = np.random.default_rng(a.seed)
-    raw = raw_prep.RawFramePlan(opt, B, B * a.beams * a.azimuths, min(a.beams * a.azimuths, scan_prep.MAX_FRAME_POINTS), raw_hw, "train", "kitti", "cells", dev)
-    wp = world.WorldPlan(B, raw_hw[0], raw_hw[1], a.beams, a.azimuths, dev, seed_slot=raw.seed)
-    K = np.tile(np.array([[718.856, 0.0, 607.1928], [0.0, 718.856, 185.2157], [0.0, 0.0, 1.0]]), (B, 1, 1))
-    Pc = np.tile(np.array([[0.0, -1, 0, 0.06], [0, 0, -1, -0.08], [1, 0, 0, -0.27], [0, 0, 0, 1]]), (B, 1, 1))
-    wp.set_cameras(K, Pc)
+    if a.dataset == "oxford":
+        from deepi2p_amd import submap
+        S, raw_hw = a.profiles, (960, 1280)
+        cal = synthetic.make_lms_traversal(np.random.default_rng(0), 1, 1, 1)          # the mounting of the laser and of the camera
+        Gl, Gc = cal["G_posesource_laser"], cal["G_cam"]
+        raw = submap.OxfordRawPlan(opt, B, B * S, B * S * a.lms_beams, B * S * a.lms_beams, min(S * a.lms_beams, submap.MAX_FRAME_POINTS), raw_hw,
+                                   "train", skip_threshold=submap.VOXEL / 16.0, device=dev)
+        tp = world.TraversalPlan(B, S, a.lms_beams, raw_hw[0], raw_hw[1], dev, seed_slot=raw.seed)
+        tp.set_calibration(Gl, Gc)
+        tp.set_camera(np.tile(np.array([[964.828979, 0.0, 643.788025], [0.0, 964.828979, 484.40799], [0.0, 0.0, 1.0]]), (B, 1, 1)))
+
+        def one_batch(step):
+            tp.set_world(world.make_street(rng, B, 0.2 * S + 20.0))
+            tp.set_traversal(*world.traversal_inputs(world.make_trajectory(rng, B, S), S // 2, S // 2, Gl, Gc))
+            outs = tp.run(seed=a.seed * 1000003 + step)
+            if a.blind:
+                outs[7].random_(0, 256)
+            return raw.run(*outs, seed=None)
+    else:
+        raw = raw_prep.RawFramePlan(opt, B, B * a.beams * a.azimuths, min(a.beams * a.azimuths, scan_prep.MAX_FRAME_POINTS), raw_hw, "train", "kitti", "cells", dev)
+        wp = world.WorldPlan(B, raw_hw[0], raw_hw[1], a.beams, a.azimuths, dev, seed_slot=raw.seed)
+        K = np.tile(np.array([[718.856, 0.0, 607.1928], [0.0, 718.856, 185.2157], [0.0, 0.0, 1.0]]), (B, 1, 1))
+        Pc = np.tile(np.array([[0.0, -1, 0, 0.06], [0, 0, -1, -0.08], [1, 0, 0, -0.27], [0, 0, 0, 1]]), (B, 1, 1))
+        wp.set_cameras(K, Pc)
+
+        def one_batch(step):
+            wp.set_pattern(world.hdl64_pattern(rng, B, a.beams, a.azimuths))
+            points, offsets, images = wp.run(world.make_world(rng, B), seed=a.seed * 1000003 + step)
+            if a.blind:
+                images.random_(0, 256)
+            return raw.run(points, offsets, images, wp.K_raw, wp.Pc, seed=None)
     curve, window = [], []
     t0 = time.perf_counter()
     for step in range(a.steps):
-        wp.set_pattern(world.hdl64_pattern(rng, B, a.beams, a.azimuths))
-        points, offsets, images = wp.run(world.make_world(rng, B), seed=a.seed * 1000003 + step)
-        if a.blind:
-            images.random_(0, 256)
-        out = raw.run(points, offsets, images, wp.K_raw, wp.Pc, seed=None)
+        out = one_batch(step)
         pc, intensity, sn, node_a, node_b, P, img, Kf = out[:8]
         L = tr.optimize(pc, intensity, sn, node_a, node_b, img, Kf, P)
         window.append(torch.stack([L["loss"], L["coarse_accuracy"], L["fine_accuracy"], L["inside"] / float(B * N)]))
