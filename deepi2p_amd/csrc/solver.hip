@@ -18,6 +18,7 @@
 //     in LDS and is advanced by thread 0 between sweeps.
 // The algorithm statement is the oracle's (oracle/frustum_lm.cpp); DESIGN.md lists it step by step.
 #include "common.h"
+#include "pose_diff.h"
 #include "solver_prep.h"
 
 #include <float.h>
@@ -1855,6 +1856,273 @@ __global__ __launch_bounds__(256) void residuals_kernel(const double* __restrict
     if (tid == 0) { counts[f] = s_base; cost_out[f] = s_cost[0]; }
 }
 
+// ----------------------------------------------------------------------------------------------
+// Pose confidence: the normal matrix A = sum_blocks rho'(s) J^T J, the gradient g = sum rho'(s) J^T r and the cost 1/2 sum log1p(s) at GIVEN
+// parameters, by the plain per-point evaluation of residuals_kernel (no clusters, no cache, no fast reciprocal) with the analytic Jacobian
+// rows of eval_active.  Grid (F, C): workgroup (f, c) owns the points [c * INFO_CHUNK, (c + 1) * INFO_CHUNK) of frame f, thread t the points
+// c * INFO_CHUNK + t + 256 j in ascending j; the wave butterflies and the in-order sum of the four wave partials give one partial per
+// workgroup, and info_finish_kernel adds the C partials of a frame in index order.  No atomics: a frame's sums are a function of its own
+// points, labels, K and parameters alone.
+constexpr int INFO_CHUNK = 1024;                 // points per workgroup: C = ceil(N / INFO_CHUNK) depends on N only
+constexpr int INFO_STRIDE = 32;                  // fp64 words per partial: NP (NP + 1) / 2 of A | NP of g | cost | label-1 count | label-0 count
+template <int NP> struct InfoWords { static constexpr int A = 0, G = Tri<NP>::N, COST = G + NP, ACT1 = COST + 1, ACT0 = COST + 2, N = COST + 3; };
+static_assert(InfoWords<6>::N <= INFO_STRIDE && InfoWords<4>::N <= INFO_STRIDE, "a partial has INFO_STRIDE words");
+
+template <int NP>
+__global__ __launch_bounds__(256) void info_partial_kernel(const float* __restrict__ points, const int* __restrict__ labels,
+                                                           const double* __restrict__ Kmat, const double* __restrict__ params, double H,
+                                                           double W, int N, int C, double* __restrict__ partial) {
+    using IW = InfoWords<NP>;
+    __shared__ double s_part[4][INFO_STRIDE];
+    constexpr int TOFF = NP == 4 ? 1 : 3;
+    const int f = blockIdx.x, c = blockIdx.y, tid = threadIdx.x;
+    const float* px = points + (long long)f * 3 * N;
+    const int* lab = labels + (long long)f * N;
+    const double* Kf = Kmat + (long long)f * 9;
+    const Cam k{Kf[0], Kf[4], Kf[2], Kf[5], H - 1.0, W - 1.0};
+    double xr[NP];
+    for (int i = 0; i < NP; ++i) xr[i] = params[(long long)f * NP + i];
+    Rot<NP> rot;
+    make_rot<NP>(xr, rot);
+    double acc[IW::N];
+#pragma unroll
+    for (int i = 0; i < IW::N; ++i) acc[i] = 0.0;
+    const int n_end = min(N, (c + 1) * INFO_CHUNK);
+    for (int n = c * INFO_CHUNK + tid; n < n_end; n += 256) {
+        const int l = lab[n];
+        if (l != 0 && l != 1) continue;
+        const double X = (double)px[n], Y = (double)px[N + n], Z = (double)px[2 * (long long)N + n];
+        const double qx = rot.R[0] * X + rot.R[1] * Y + rot.R[2] * Z, qy = rot.R[3] * X + rot.R[4] * Y + rot.R[5] * Z,
+                     qz = rot.R[6] * X + rot.R[7] * Y + rot.R[8] * Z;
+        const double p0 = qx + xr[TOFF], p1 = qy + xr[TOFF + 1], p2 = qz + xr[TOFF + 2];
+        const double pix_x = p0 * k.fx / p2 + k.cx, pix_y = p1 * k.fy / p2 + k.cy;
+        // residual rows as value and slopes (d/dpix_x, d/dpix_y, d/dp2 direct); fmax(v, 0) keeps v and its slope at v == 0 (Ceres' Jet max)
+        double rv[3] = {0, 0, 0}, sx[3] = {0, 0, 0}, sy[3] = {0, 0, 0}, sz[3] = {0, 0, 0};
+        if (l == 1) {
+            const double a0 = -pix_x, b0 = pix_x - k.W1, a1 = -pix_y, b1 = pix_y - k.H1, a2 = -p2;
+            rv[0] = fmax(a0, 0.0) + fmax(b0, 0.0);
+            sx[0] = (a0 < 0.0 ? 0.0 : -1.0) + (b0 < 0.0 ? 0.0 : 1.0);
+            rv[1] = fmax(a1, 0.0) + fmax(b1, 0.0);
+            sy[1] = (a1 < 0.0 ? 0.0 : -1.0) + (b1 < 0.0 ? 0.0 : 1.0);
+            rv[2] = fmax(a2, 0.0) * 100.0;
+            sz[2] = a2 < 0.0 ? 0.0 : -100.0;
+        } else {
+            const double ex = pix_x - k.W1 * 0.5, ey = pix_y - k.H1 * 0.5;
+            const double dx = k.W1 * 0.5 - fabs(ex), dy = k.H1 * 0.5 - fabs(ey);
+            // the three indicators are constant where they are defined: 1 inside the frustum, 0 outside, NaN on a plane (as the functor's)
+            const double ind = (fmax(p2, 0.0) / p2) * (fmax(dx, 0.0) / dx) * (fmax(dy, 0.0) / dy);
+            rv[0] = (dx + dy) * ind;
+            sx[0] = (ex < 0.0 ? 1.0 : -1.0) * ind;
+            sy[0] = (ey < 0.0 ? 1.0 : -1.0) * ind;
+        }
+        const double s = rv[0] * rv[0] + rv[1] * rv[1] + rv[2] * rv[2];       // rows 1 and 2 of a label-0 block are 0
+        acc[IW::COST] += 0.5 * log1p(s);
+        if (s != 0.0) { acc[IW::ACT1] += l == 1 ? 1.0 : 0.0; acc[IW::ACT0] += l == 1 ? 0.0 : 1.0; }
+        const double rho1 = 1.0 / (1.0 + s);
+        // dp_i / dparam: rotation columns from dR (NP == 6) or d/dtheta of Ry(theta) X (NP == 4), then the identity of t
+        double dp0[NP], dp1[NP], dp2[NP];
+        if (NP == 4) {
+            const bool first_order = !(xr[0] * xr[0] > DBL_EPSILON);
+            dp0[0] = first_order ? Z : qz; dp1[0] = 0.0; dp2[0] = first_order ? -X : -qx;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                dp0[i] = rot.dR[i][0] * X + rot.dR[i][1] * Y + rot.dR[i][2] * Z;
+                dp1[i] = rot.dR[i][3] * X + rot.dR[i][4] * Y + rot.dR[i][5] * Z;
+                dp2[i] = rot.dR[i][6] * X + rot.dR[i][7] * Y + rot.dR[i][8] * Z;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { dp0[TOFF + i] = i == 0 ? 1.0 : 0.0; dp1[TOFF + i] = i == 1 ? 1.0 : 0.0; dp2[TOFF + i] = i == 2 ? 1.0 : 0.0; }
+        const double iz = 1.0 / p2;
+        const double ax = k.fx * iz, bx = -k.fx * p0 * iz * iz;   // dpix_x = ax*dp0 + bx*dp2
+        const double ay = k.fy * iz, by = -k.fy * p1 * iz * iz;   // dpix_y = ay*dp1 + by*dp2
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            if (sx[i] == 0.0 && sy[i] == 0.0 && sz[i] == 0.0) continue;       // a constant row (NaN slopes do not compare equal: they are added)
+            double J[NP];
+#pragma unroll
+            for (int a = 0; a < NP; ++a) J[a] = sx[i] * (ax * dp0[a] + bx * dp2[a]) + sy[i] * (ay * dp1[a] + by * dp2[a]) + sz[i] * dp2[a];
+            const double wr = rho1 * rv[i];
+#pragma unroll
+            for (int a = 0; a < NP; ++a) {
+                acc[IW::G + a] += wr * J[a];
+                const double wa = rho1 * J[a];
+#pragma unroll
+                for (int b = 0; b <= a; ++b) acc[IW::A + a * (a + 1) / 2 + b] += wa * J[b];
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < IW::N; ++i) acc[i] = wave_sum(acc[i]);
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int i = 0; i < IW::N; ++i) s_part[tid >> 6][i] = acc[i];
+    }
+    __syncthreads();
+    if (tid < IW::N) partial[((long long)f * C + c) * INFO_STRIDE + tid] = ((s_part[0][tid] + s_part[1][tid]) + s_part[2][tid]) + s_part[3][tid];
+}
+
+template <int NP>
+__global__ __launch_bounds__(64) void info_finish_kernel(const double* __restrict__ partial, int C, double* __restrict__ info,
+                                                         double* __restrict__ grad, double* __restrict__ cost, int* __restrict__ active) {
+    using IW = InfoWords<NP>;
+    __shared__ double s_sum[INFO_STRIDE];
+    const int f = blockIdx.x, tid = threadIdx.x;
+    if (tid < IW::N) {
+        double v = 0.0;
+        for (int c = 0; c < C; ++c) v += partial[((long long)f * C + c) * INFO_STRIDE + tid];
+        s_sum[tid] = v;
+    }
+    __syncthreads();
+    if (tid < NP * NP) info[(long long)f * NP * NP + tid] = s_sum[IW::A + tri<NP>(tid / NP, tid % NP)];
+    if (tid < NP) grad[(long long)f * NP + tid] = s_sum[IW::G + tid];
+    if (tid == 0) cost[f] = s_sum[IW::COST];
+    if (tid < 2) active[2 * f + tid] = (int)s_sum[tid == 0 ? IW::ACT1 : IW::ACT0];
+}
+
+// params[f, best[f]] -> out[f] (a frame without a selected restart, best < 0, takes restart 0: its covariance reports status 2 anyway)
+__global__ __launch_bounds__(64) void gather_best_kernel(const double* __restrict__ params, const int* __restrict__ best, int F, int R, int np,
+                                                         double* __restrict__ out) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= F * np) return;
+    const int f = i / np;
+    int b = best[f];
+    if (b < 0 || b >= R) b = 0;
+    out[i] = params[((long long)f * R + b) * np + (i - f * np)];
+}
+
+// Bounded inverse of the information matrix, one thread per frame.  A translation parameter exactly on its bound is fixed: its row and
+// column are replaced by the identity's before the Cholesky factorisation (the factor of the free block is then the factor of the free
+// sub-matrix, operation for operation: the replaced entries contribute exact zeros) and its covariance entries are written as 0.
+template <int NP>
+__global__ __launch_bounds__(64) void pose_covariance_kernel(const double* __restrict__ info, const double* __restrict__ params,
+                                                             const int* __restrict__ has_inside, Bounds bnd, int F, double* __restrict__ cov,
+                                                             int* __restrict__ free_mask, int* __restrict__ status, double* __restrict__ sigma_t,
+                                                             double* __restrict__ sigma_r) {
+    constexpr int TOFF = NP == 4 ? 1 : 3;
+    const int f = blockIdx.x * 64 + threadIdx.x;
+    if (f >= F) return;
+    double A[NP][NP], x[NP];
+    bool finite = true;
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        x[i] = params[(long long)f * NP + i];
+        finite = finite && isfinite(x[i]);
+#pragma unroll
+        for (int j = 0; j < NP; ++j) { A[i][j] = info[((long long)f * NP + i) * NP + j]; finite = finite && isfinite(A[i][j]); }
+    }
+    int mask = 0;
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        const int ti = i >= TOFF ? i - TOFF : 0;
+        const bool fixed = i >= TOFF && (x[i] == bnd.lb[ti] || x[i] == bnd.ub[ti]);
+        if (!fixed) mask |= 1 << i;
+    }
+    free_mask[f] = mask;
+    int st = (!finite || (has_inside && has_inside[f] == 0)) ? 2 : (mask == 0 ? 1 : 0);
+    double amax = 0.0;
+#pragma unroll
+    for (int i = 0; i < NP; ++i) if ((mask >> i) & 1) amax = fmax(amax, A[i][i]);
+    const double tiny = NP * DBL_EPSILON * amax;
+    // L: Cholesky factor of the free block (identity on the fixed parameters)
+    double L[NP][NP];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        const bool fi = (mask >> i) & 1;
+#pragma unroll
+        for (int j = 0; j <= i; ++j) {
+            const bool fj = (mask >> j) & 1;
+            double s = (fi && fj) ? A[i][j] : (i == j ? 1.0 : 0.0);
+#pragma unroll
+            for (int q = 0; q < j; ++q) s -= L[i][q] * L[j][q];
+            if (i == j) {
+                if (fi && !(s > tiny) && st == 0) st = 1;
+                L[i][i] = sqrt(s);
+            } else {
+                L[i][j] = s / L[j][j];
+            }
+        }
+    }
+    // M = L^-1 (lower triangular, column by column), cov = M^T M
+    double M[NP][NP];
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+#pragma unroll
+        for (int i = j; i < NP; ++i) {
+            double s = i == j ? 1.0 : 0.0;
+#pragma unroll
+            for (int q = j; q < i; ++q) s -= L[i][q] * M[q][j];
+            M[i][j] = s / L[i][i];
+        }
+    }
+    const double nan = __builtin_nan("");
+    double tr_r = 0.0, tr_t = 0.0;
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+#pragma unroll
+        for (int j = 0; j <= i; ++j) {
+            double s = 0.0;
+#pragma unroll
+            for (int q = i; q < NP; ++q) s += M[q][i] * M[q][j];
+            if (!((mask >> i) & 1) || !((mask >> j) & 1)) s = 0.0;
+            if (st != 0) s = nan;
+            cov[((long long)f * NP + i) * NP + j] = s;
+            cov[((long long)f * NP + j) * NP + i] = s;
+            if (i == j) { if (i < TOFF) tr_r += s; else tr_t += s; }
+        }
+    }
+    status[f] = st;
+    sigma_t[f] = sqrt(tr_t);
+    sigma_r[f] = sqrt(tr_r) * (180.0 / 3.14159265358979323846);
+}
+
+__device__ __forceinline__ void params_to_pose(const double* x, int np, double* P) {      // row-major 4x4, as select_best_kernel assembles it
+    double w[3] = {0, 0, 0};
+    int toff;
+    if (np == 4) { w[1] = x[0]; toff = 1; } else { w[0] = x[0]; w[1] = x[1]; w[2] = x[2]; toff = 3; }
+    double Rm[9];
+    angle_axis_to_R(w, Rm);
+    for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) P[r * 4 + c] = Rm[r * 3 + c]; P[r * 4 + 3] = x[toff + r]; }
+    P[12] = P[13] = P[14] = 0.0; P[15] = 1.0;
+}
+
+// What the other restarts say: one wave per frame, lanes stride over R.  A restart AGREES when its cost is finite and get_P_diff of
+// P_r^-1 P_best is below both tolerances (pose_diff.h, the rule of di2p_pose_errors); the gap is the cheapest disagreeing restart's cost
+// minus the best's.
+__global__ __launch_bounds__(64) void restart_consensus_kernel(const double* __restrict__ params, const double* __restrict__ cost,
+                                                               const int* __restrict__ best, const int* __restrict__ has_inside, int np, int R,
+                                                               double t_tol, double r_tol_deg, int* __restrict__ finite_out,
+                                                               int* __restrict__ agree_out, double* __restrict__ gap) {
+    const int f = blockIdx.x, lane = threadIdx.x;
+    const int b = best[f];
+    if ((has_inside && has_inside[f] == 0) || b < 0 || b >= R) {        // wave-uniform
+        if (lane == 0) { finite_out[f] = 0; agree_out[f] = 0; gap[f] = __builtin_nan(""); }
+        return;
+    }
+    double G[16], A[16];
+    params_to_pose(params + ((long long)f * R + b) * np, np, G);
+    int n_finite = 0, n_agree = 0;
+    double other = __builtin_inf();
+    for (int r = lane; r < R; r += 64) {
+        const double c = cost[(long long)f * R + r];
+        if (!isfinite(c)) continue;
+        n_finite += 1;
+        params_to_pose(params + ((long long)f * R + r) * np, np, A);
+        double t, ang;
+        di2p_pose_diff(A, G, t, ang);
+        if (t < t_tol && ang < r_tol_deg) n_agree += 1;
+        else other = fmin(other, c);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        n_finite += __shfl_xor(n_finite, o);
+        n_agree += __shfl_xor(n_agree, o);
+        other = fmin(other, __shfl_xor(other, o));
+    }
+    if (lane == 0) { finite_out[f] = n_finite; agree_out[f] = n_agree; gap[f] = other - cost[(long long)f * R + b]; }
+}
+
 static long long* g_prof = nullptr;   // diagnostics hook, see di2p_solver_set_profile_buffer
 
 constexpr size_t kStateBytes = sizeof(LMState<6>) > sizeof(LMState<4>) ? sizeof(LMState<6>) : sizeof(LMState<4>);
@@ -2013,6 +2281,68 @@ extern "C" int di2p_solver_residuals(const double* points, const int32_t* labels
         hipLaunchKernelGGL(residuals_kernel<4>, dim3(F), dim3(256), 0, (hipStream_t)stream, points, labels, K, params, H, W, N, residuals, counts, cost);
     else
         hipLaunchKernelGGL(residuals_kernel<6>, dim3(F), dim3(256), 0, (hipStream_t)stream, points, labels, K, params, H, W, N, residuals, counts, cost);
+    DI2P_RETURN_LAUNCH();
+}
+
+static int info_chunks(int N) { return N > 0 ? (N + INFO_CHUNK - 1) / INFO_CHUNK : 1; }      // (an empty cloud still launches: a grid of 0 is an error)
+
+extern "C" long long di2p_pose_information_workspace_bytes(int F, int N) {
+    if (F < 0 || N < 0) return 0;
+    return (long long)F * info_chunks(N) * INFO_STRIDE * (long long)sizeof(double);
+}
+
+extern "C" int di2p_pose_information(const float* points, const int32_t* labels, const double* K, const double* params, double H, double W,
+                                     int is_2d, int F, int N, double* info, double* grad, double* cost, int32_t* active, void* workspace,
+                                     void* stream) {
+    DI2P_CHECK_ARG(F >= 0 && N >= 0, "bad size");
+    if (F == 0) return 0;
+    DI2P_CHECK_ARG(points && labels && K && params && info && grad && cost && active && workspace, "null pointer");
+    const int C = info_chunks(N);
+    DI2P_CHECK_ARG(C <= 65535, "N too large");
+    double* partial = (double*)workspace;
+    if (is_2d) {
+        hipLaunchKernelGGL(info_partial_kernel<4>, dim3(F, C), dim3(256), 0, (hipStream_t)stream, points, labels, K, params, H, W, N, C, partial);
+        hipLaunchKernelGGL(info_finish_kernel<4>, dim3(F), dim3(64), 0, (hipStream_t)stream, (const double*)partial, C, info, grad, cost, active);
+    } else {
+        hipLaunchKernelGGL(info_partial_kernel<6>, dim3(F, C), dim3(256), 0, (hipStream_t)stream, points, labels, K, params, H, W, N, C, partial);
+        hipLaunchKernelGGL(info_finish_kernel<6>, dim3(F), dim3(64), 0, (hipStream_t)stream, (const double*)partial, C, info, grad, cost, active);
+    }
+    DI2P_RETURN_LAUNCH();
+}
+
+extern "C" int di2p_gather_best_params(const double* params, const int32_t* best, int is_2d, int F, int R, double* out, void* stream) {
+    DI2P_CHECK_ARG(F >= 0 && R >= 1, "bad size (F >= 0, R >= 1)");
+    if (F == 0) return 0;
+    DI2P_CHECK_ARG(params && best && out, "null pointer");
+    const int np = is_2d ? 4 : 6;
+    hipLaunchKernelGGL(gather_best_kernel, dim3(di2p_cdiv((long long)F * np, 64)), dim3(64), 0, (hipStream_t)stream, params, best, F, R, np, out);
+    DI2P_RETURN_LAUNCH();
+}
+
+extern "C" int di2p_pose_covariance(const double* info, const double* params, const int32_t* has_inside, const double* lb_host,
+                                    const double* ub_host, int is_2d, int F, double* cov, int32_t* free_mask, int32_t* status, double* sigma_t,
+                                    double* sigma_r, void* stream) {
+    DI2P_CHECK_ARG(F >= 0, "bad size");
+    if (F == 0) return 0;
+    DI2P_CHECK_ARG(info && params && lb_host && ub_host && cov && free_mask && status && sigma_t && sigma_r, "null pointer");
+    Bounds b;
+    for (int i = 0; i < 3; ++i) { b.lb[i] = lb_host[i]; b.ub[i] = ub_host[i]; }
+    if (is_2d)
+        hipLaunchKernelGGL(pose_covariance_kernel<4>, dim3(di2p_cdiv(F, 64)), dim3(64), 0, (hipStream_t)stream, info, params, has_inside, b, F, cov,
+                           free_mask, status, sigma_t, sigma_r);
+    else
+        hipLaunchKernelGGL(pose_covariance_kernel<6>, dim3(di2p_cdiv(F, 64)), dim3(64), 0, (hipStream_t)stream, info, params, has_inside, b, F, cov,
+                           free_mask, status, sigma_t, sigma_r);
+    DI2P_RETURN_LAUNCH();
+}
+
+extern "C" int di2p_restart_consensus(const double* params, const double* cost, const int32_t* best, const int32_t* has_inside, int is_2d,
+                                      int F, int R, double t_tol, double r_tol_deg, int32_t* finite, int32_t* agree, double* gap, void* stream) {
+    DI2P_CHECK_ARG(F >= 0 && R >= 1, "bad size (F >= 0, R >= 1)");
+    if (F == 0) return 0;
+    DI2P_CHECK_ARG(params && cost && best && finite && agree && gap, "null pointer");
+    hipLaunchKernelGGL(restart_consensus_kernel, dim3(F), dim3(64), 0, (hipStream_t)stream, params, cost, best, has_inside, is_2d ? 4 : 6, R, t_tol,
+                       r_tol_deg, finite, agree, gap);
     DI2P_RETURN_LAUNCH();
 }
 

@@ -999,3 +999,119 @@ def solver_residuals(points64, labels, K, params, H, W, is_2d):
     call("di2p_solver_residuals", ptr(points64), ptr(labels), ptr(K), ptr(params), float(H), float(W), int(bool(is_2d)),
          F, N, ptr(res), ptr(counts), ptr(cost), stream())
     return res, counts, cost
+
+
+# ------------------------------------------------------------------------------------ pose confidence
+def _npar(is_2d):
+    return 4 if is_2d else 6
+
+
+def pose_information_workspace(F, N, device):
+    """A workspace for pose_information_into: di2p_pose_information_workspace_bytes(F, N) bytes as a uint8 tensor"""
+    need = int(_lib.load().di2p_pose_information_workspace_bytes(int(F), int(N)))
+    return torch.empty((max(need, 8),), dtype=torch.uint8, device=device)
+
+
+def pose_information_into(points, labels, K, params, H, W, is_2d, info, grad, cost, active, workspace):
+    """pose_information with the outputs and the workspace supplied: two launches, no allocation -- the form graphs capture."""
+    require_cuda(points, labels, K, params, info, grad, cost, active, workspace)
+    _chk(points, _f32, "points")
+    _chk(labels, _i32, "labels")
+    _chk(K, _f64, "K")
+    _chk(params, _f64, "params")
+    if points.dim() != 3 or points.shape[1] != 3:
+        raise ValueError("pose_information: points must be f32 [F,3,N]")
+    F, _, N = points.shape
+    npar = _npar(is_2d)
+    if tuple(labels.shape) != (F, N) or tuple(K.shape) != (F, 3, 3) or tuple(params.shape) != (F, npar):
+        raise ValueError("pose_information: labels must be i32 [F,N], K f64 [F,3,3] and params f64 [F,%d]" % npar)
+    if (info.dtype, grad.dtype, cost.dtype, active.dtype) != (_f64, _f64, _f64, _i32) or tuple(info.shape) != (F, npar, npar) \
+            or tuple(grad.shape) != (F, npar) or tuple(cost.shape) != (F,) or tuple(active.shape) != (F, 2):
+        raise ValueError("pose_information: outputs must be info f64[F,np,np], grad f64[F,np], cost f64[F], active i32[F,2]")
+    need = int(_lib.load().di2p_pose_information_workspace_bytes(F, N))
+    if workspace.dtype != torch.uint8 or workspace.numel() < need:
+        raise ValueError("pose_information: the workspace must be uint8 with at least di2p_pose_information_workspace_bytes(%d, %d) = %d bytes"
+                         % (F, N, need))
+    call("di2p_pose_information", ptr(points), ptr(labels), ptr(K), ptr(params), float(H), float(W), int(bool(is_2d)), F, N, ptr(info),
+         ptr(grad), ptr(cost), ptr(active), ptr(workspace), stream())
+    return info, grad, cost, active
+
+
+def pose_information(points, labels, K, params, H, W, is_2d, workspace=None):
+    """The Cauchy-weighted normal matrix, gradient and cost of the registration problem at GIVEN parameters (csrc/solver.hip).
+    points f32[F,3,N], labels i32[F,N] (labels outside {0, 1} are skipped), K f64[F,3,3], params f64[F,np]
+    -> info f64[F,np,np] = sum rho'(s) J^T J, grad f64[F,np] = sum rho'(s) J^T r, cost f64[F] = 1/2 sum log1p(s), active i32[F,2] (label-1 /
+    label-0 points with a non-zero residual block).  In the solver's parameterisation; deterministic (no atomics), independent of F."""
+    F, _, N = points.shape
+    npar = _npar(is_2d)
+    dev = points.device
+    info = torch.empty((F, npar, npar), dtype=_f64, device=dev)
+    grad = torch.empty((F, npar), dtype=_f64, device=dev)
+    cost = torch.empty((F,), dtype=_f64, device=dev)
+    active = torch.empty((F, 2), dtype=_i32, device=dev)
+    ws = workspace if workspace is not None else pose_information_workspace(F, N, dev)
+    return pose_information_into(points, labels, K, params, H, W, is_2d, info, grad, cost, active, ws)
+
+
+def gather_best_params(params, best, is_2d):
+    """params f64[F,R,np], best i32[F] -> f64[F,np] = params[f, best[f]] (best outside [0, R): restart 0), on the device"""
+    require_cuda(params, best)
+    _chk(params, _f64, "params")
+    _chk(best, _i32, "best")
+    npar = _npar(is_2d)
+    if params.dim() != 3 or params.shape[2] != npar or best.numel() != params.shape[0] or params.shape[1] < 1:
+        raise ValueError("gather_best_params: params must be f64 [F,R,%d] with R >= 1 and best i32 [F]" % npar)
+    F, R = int(params.shape[0]), int(params.shape[1])
+    out = torch.empty((F, npar), dtype=_f64, device=params.device)
+    call("di2p_gather_best_params", ptr(params), ptr(best), int(bool(is_2d)), F, R, ptr(out), stream())
+    return out
+
+
+def pose_covariance(info, params, lb, ub, is_2d, has_inside=None):
+    """The bounded inverse of the information matrix.  info f64[F,np,np], params f64[F,np], lb / ub: the solve's translation bounds (3 values
+    each), has_inside i32[F] | None -> (cov f64[F,np,np], free_mask i32[F], status i32[F], sigma_t f64[F], sigma_r f64[F] in degrees).
+    A translation parameter exactly on a bound is fixed (removed before the inversion, 0 in cov); status 0 ok, 1 not positive definite, 2
+    has_inside == 0 or non-finite input (then cov and the sigmas are NaN).  The sigmas carry no fitted noise scale: they compare frames of one
+    configuration with each other, they are not metres or degrees of expected error (include/deepi2p_hip.h)."""
+    require_cuda(info, params, has_inside)
+    _chk(info, _f64, "info")
+    _chk(params, _f64, "params")
+    npar = _npar(is_2d)
+    F = int(info.shape[0])
+    if tuple(info.shape) != (F, npar, npar) or tuple(params.shape) != (F, npar):
+        raise ValueError("pose_covariance: info must be f64 [F,%d,%d] and params f64 [F,%d]" % (npar, npar, npar))
+    if has_inside is not None and (has_inside.dtype != _i32 or has_inside.numel() != F):
+        raise ValueError("pose_covariance: has_inside must be i32 [F]")
+    dev = info.device
+    cov = torch.empty((F, npar, npar), dtype=_f64, device=dev)
+    free_mask = torch.empty((F,), dtype=_i32, device=dev)
+    status = torch.empty((F,), dtype=_i32, device=dev)
+    sigma_t = torch.empty((F,), dtype=_f64, device=dev)
+    sigma_r = torch.empty((F,), dtype=_f64, device=dev)
+    call("di2p_pose_covariance", ptr(info), ptr(params), ptr(has_inside), _dbl3(lb), _dbl3(ub), int(bool(is_2d)), F, ptr(cov), ptr(free_mask),
+         ptr(status), ptr(sigma_t), ptr(sigma_r), stream())
+    return cov, free_mask, status, sigma_t, sigma_r
+
+
+def restart_consensus(params, cost, best, is_2d, t_tol=2.0, r_tol_deg=5.0, has_inside=None):
+    """What the other restarts of a multi-start solve say about the selected one.  params f64[F,R,np], cost f64[F,R], best i32[F]
+    -> (finite i32[F]: restarts with a finite cost; agree i32[F]: those within t_tol / r_tol_deg of the best pose by get_P_diff's rule on
+    P_r^-1 P_best, the best included; gap f64[F]: the cheapest disagreeing restart's cost minus the best's, +inf when all agree).
+    Frames with has_inside == 0 (or best outside [0, R)) get 0, 0, NaN."""
+    require_cuda(params, cost, best, has_inside)
+    _chk(params, _f64, "params")
+    _chk(cost, _f64, "cost")
+    _chk(best, _i32, "best")
+    npar = _npar(is_2d)
+    if cost.dim() != 2 or cost.shape[1] < 1 or tuple(params.shape) != (cost.shape[0], cost.shape[1], npar) or best.numel() != cost.shape[0]:
+        raise ValueError("restart_consensus: params must be f64 [F,R,%d], cost f64 [F,R] with R >= 1 and best i32 [F]" % npar)
+    F, R = int(cost.shape[0]), int(cost.shape[1])
+    if has_inside is not None and (has_inside.dtype != _i32 or has_inside.numel() != F):
+        raise ValueError("restart_consensus: has_inside must be i32 [F]")
+    dev = cost.device
+    finite = torch.empty((F,), dtype=_i32, device=dev)
+    agree = torch.empty((F,), dtype=_i32, device=dev)
+    gap = torch.empty((F,), dtype=_f64, device=dev)
+    call("di2p_restart_consensus", ptr(params), ptr(cost), ptr(best), ptr(has_inside), int(bool(is_2d)), F, R, float(t_tol), float(r_tol_deg),
+         ptr(finite), ptr(agree), ptr(gap), stream())
+    return finite, agree, gap

@@ -114,10 +114,16 @@ class RegistrationExecutor:
     points as given with P = P_cam . P_convert, which is the same projection mathematically but not to the last bit.
     "classification" -> results["vis_classification"]: prediction against ground truth at the ground-truth projection (the third output of
     the prep.project_labels call evaluation mode makes anyway), the fine variant with its grid when the model has the fine head, else the
-    coarse one; it needs evaluate=True for the ground truth (ValueError otherwise).  A custom step_fn with visualize raises, as with evaluate."""
+    coarse one; it needs evaluate=True for the ground truth (ValueError otherwise).  A custom step_fn with visualize raises, as with evaluate.
+
+    confidence=True (off by default, and then nothing here is launched differently and the results gain no keys): the pose solve of the step
+    ends with the pipeline's confidence stage (RegistrationPipeline(confidence=True) does the same on its own), on the step's stream and
+    inside its capture -- six launches.  Results gain info, grad, cov, cov_status, free_mask, sigma_t, sigma_r, active, agree, finite, gap
+    (RegistrationPipeline's docstring says what they are and what they are not).  A custom step_fn or a PnPPipeline with it raises ValueError."""
 
     def __init__(self, mm, pipe, K, example_batch, n_streams=8, use_graph=True, restarts=None, labels_override=None, step_fn=None,
-                 post_fn=None, h2d_mode="copy_stream", split_solver=False, double_buffer=False, samples=None, evaluate=False, visualize=None):
+                 post_fn=None, h2d_mode="copy_stream", split_solver=False, double_buffer=False, samples=None, evaluate=False, visualize=None,
+                 confidence=False):
         from .registration_pnp import PnPPipeline
         self.pnp = isinstance(pipe, PnPPipeline)
         if self.pnp:
@@ -139,6 +145,11 @@ class RegistrationExecutor:
         if visualize is not None and step_fn is not None:
             raise ValueError("visualize draws the pose and labels of the executor's own step; a custom step_fn has none it knows of")
         self.visualize = visualize
+        self.confidence = bool(confidence)
+        if self.confidence and step_fn is not None:
+            raise ValueError("confidence=True measures the pose solve of the executor's own step; a custom step_fn has none it knows of")
+        if self.confidence and self.pnp:
+            raise ValueError("confidence=True needs the Gauss-Newton RegistrationPipeline; a PnPPipeline's confidence is its inlier count")
         self.mm, self.pipe = mm, pipe
         self.device = mm.device
         self.n_streams = max(1, int(n_streams))
@@ -308,7 +319,8 @@ class RegistrationExecutor:
             out.update(net)
             return self._finish(slot, out)
         labels = self.labels_override if self.labels_override is not None else net["pred"]
-        out = self.pipe(d["pc"], labels, d[K_NAME], self.restarts)           # same stream: the pose solve follows its classification
+        kw = {"confidence": True} if self.confidence else {}                 # off: the pipeline's own setting, the call as it always was
+        out = self.pipe(d["pc"], labels, d[K_NAME], self.restarts, **kw)     # same stream: the pose solve follows its classification
         out.update(net)
         return self._finish(slot, out)
 

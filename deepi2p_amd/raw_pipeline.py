@@ -183,7 +183,7 @@ class RawFrameExecutor(PreparedFrameExecutor):
 
     def __init__(self, mm, pipe, opt, example_batch, cap_raw, max_frame_points, n_streams=4, use_graph=True, restarts=None, samples=None,
                  labels_override=None, mode="val", dataset="kitti", normals_method="query", h2d_mode="copy_stream", post_fn=None, evaluate=False,
-                 visualize=None):
+                 visualize=None, confidence=False):
         raw_prep._check_dataset(dataset)
         scan_prep._normals_entry(normals_method)
         self._check_h2d_mode(h2d_mode)
@@ -192,7 +192,7 @@ class RawFrameExecutor(PreparedFrameExecutor):
         self.cap_raw, self.max_frame_points = int(cap_raw), int(max_frame_points)
         self._check_batch(example_batch)
         super().__init__(mm, pipe, example_batch, n_streams=n_streams, use_graph=use_graph, restarts=restarts, labels_override=labels_override,
-                         post_fn=post_fn, h2d_mode=h2d_mode, samples=samples, evaluate=evaluate, visualize=visualize)
+                         post_fn=post_fn, h2d_mode=h2d_mode, samples=samples, evaluate=evaluate, visualize=visualize, confidence=confidence)
 
     def _check_batch(self, host_batch):
         return host_frames(host_batch, self.B, self.cap_raw, self.raw_hw)

@@ -161,12 +161,23 @@ class RegistrationPipeline:
 
     frame="enu": the points are z-up (nuScenes).  The 2-D solve only rotates about y, so the reference swaps axes first (enu2cam,
     registration_lsq.py:237-248, 301-302): the call converts the points (x, y, z) -> (x, -z, y), runs the same launches on them and
-    returns P_cam (the solver's pose of the converted points) next to P = P_cam . P_convert (the pose of the points as given)."""
+    returns P_cam (the solver's pose of the converted points) next to P = P_cam . P_convert (the pose of the points as given).
+
+    confidence=True (off by default, and then the returned dict and every launch are as without it): the call also says how far to trust
+    the selected pose.  Local: info / grad (the Cauchy-weighted normal matrix and the gradient at the selected restart's parameters, from
+    the front-filtered labels the solve used), active, and their bounded inverse cov with cov_status, free_mask, sigma_t, sigma_r
+    (ops.pose_covariance).  Global: finite, agree, gap -- how many of the R restarts ended within agree_tol = (metres, degrees) of the
+    selected pose and how far below the best other basin it lies (ops.restart_consensus).  All of it is in the SOLVER's parameterisation
+    (for frame="enu": P_cam's) and carries no fitted noise scale: the sigmas rank frames of one configuration, they are not metres or degrees."""
+    CONFIDENCE_KEYS = ("info", "grad", "cov", "cov_status", "free_mask", "sigma_t", "sigma_r", "active", "agree", "finite", "gap")
 
     def __init__(self, H, W, R=60, ry_sigma=10 * math.pi / 180, init_t_amplitude=10.0,
-                 t_lowerbound=(-5, -0.1, -10), t_upperbound=(5, 0.1, 10), max_iter=500, is_2d=True, seed=0, frame="cam"):
+                 t_lowerbound=(-5, -0.1, -10), t_upperbound=(5, 0.1, 10), max_iter=500, is_2d=True, seed=0, frame="cam",
+                 confidence=False, agree_tol=(2.0, 5.0)):
         from . import evaluation
         self.enu, self.frame = bool(evaluation.check_frame(frame)), frame
+        self.confidence = bool(confidence)
+        self.agree_tol = (float(agree_tol[0]), float(agree_tol[1]))
         self._convert = {}
         self.H, self.W, self.R = H, W, R
         self.ry_sigma, self.amp = ry_sigma, init_t_amplitude
@@ -187,9 +198,10 @@ class RegistrationPipeline:
                  ops.stream())
         return noise, Ts
 
-    def __call__(self, pc_f32, labels_i32, K_f64, restarts):
+    def __call__(self, pc_f32, labels_i32, K_f64, restarts, confidence=None):
         """pc f32[F,3,N], labels i32[F,N], K f64[F,3,3], restarts = (ry_noise f64[F,R], t_init f64[F,R,3])
-        -> dict(P f64[F,4,4], cost f64[F], best i32[F], yaw0, costs f64[F,R], iters i32[F,R])."""
+        -> dict(P f64[F,4,4], cost f64[F], best i32[F], yaw0, costs f64[F,R], iters i32[F,R]).
+        confidence: None = the pipeline's own setting; True / False overrides it for this call (the executor's confidence=True)."""
         F, _, N = pc_f32.shape
         if self.enu:
             from . import evaluation
@@ -205,7 +217,19 @@ class RegistrationPipeline:
         out = dict(P=P, cost=bc, best=best, yaw0=yaw0, costs=cost, iters=iters, sweeps=sweeps, params=params, labels_front=lab_front)
         if self.enu:
             out["P_cam"], out["P"] = P, compose_convert(self._convert, P)
+        if self.confidence if confidence is None else confidence:
+            out.update(self._confidence(pc_f32, lab_front, K_f64, params, cost, best, has_inside))
         return out
+
+    def _confidence(self, pc_f32, lab_front, K_f64, params, cost, best, has_inside):
+        """The confidence stage, on the current stream: four launches behind the argmin (gather, two of the information matrix, covariance)
+        and the consensus.  pc_f32: the points the solve ran on (converted already for frame="enu")."""
+        x = ops.gather_best_params(params, best, self.is_2d)
+        info, grad, _, active = ops.pose_information(pc_f32, lab_front, K_f64, x, self.H, self.W, self.is_2d)
+        cov, free_mask, status, sigma_t, sigma_r = ops.pose_covariance(info, x, self.lb, self.ub, self.is_2d, has_inside=has_inside)
+        finite, agree, gap = ops.restart_consensus(params, cost, best, self.is_2d, self.agree_tol[0], self.agree_tol[1], has_inside=has_inside)
+        return dict(info=info, grad=grad, cov=cov, cov_status=status, free_mask=free_mask, sigma_t=sigma_t, sigma_r=sigma_r, active=active,
+                    agree=agree, finite=finite, gap=gap)
 
 
 def compose_convert(cache, P_cam):

@@ -136,7 +136,7 @@ class OxfordFrameExecutor(PreparedFrameExecutor):
 
     def __init__(self, mm, pipe, opt, example_batch, S_cap, P_cap, cap_raw, max_frame_points, n_streams=4, use_graph=True, restarts=None,
                  samples=None, labels_override=None, mode="val", voxel=submap.VOXEL, skip_threshold=None, ground_threshold=None,
-                 h2d_mode="copy_stream", post_fn=None, evaluate=False, visualize=None):
+                 h2d_mode="copy_stream", post_fn=None, evaluate=False, visualize=None, confidence=False):
         self._check_h2d_mode(h2d_mode)
         _ragged._check_max_frame_points("submap", max_frame_points)
         submap._skip_arg(skip_threshold)
@@ -147,7 +147,7 @@ class OxfordFrameExecutor(PreparedFrameExecutor):
         sample_prep.option_block(opt, self.raw_hw, mode, dataset="oxford")
         self._check_batch(example_batch)
         super().__init__(mm, pipe, example_batch, n_streams=n_streams, use_graph=use_graph, restarts=restarts, labels_override=labels_override,
-                         post_fn=post_fn, h2d_mode=h2d_mode, samples=samples, evaluate=evaluate, visualize=visualize)
+                         post_fn=post_fn, h2d_mode=h2d_mode, samples=samples, evaluate=evaluate, visualize=visualize, confidence=confidence)
 
     def _check_batch(self, host_batch):
         return host_submap_frames(host_batch, self.B, self.S_cap, self.P_cap, self.raw_hw)

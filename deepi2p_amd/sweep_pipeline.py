@@ -96,7 +96,7 @@ class SweepFrameExecutor(PreparedFrameExecutor):
     cols = None          # while the example batch itself is checked: whatever it has
 
     def __init__(self, mm, pipe, opt, example_batch, S_cap, cap_raw, max_frame_points, n_streams=4, use_graph=True, restarts=None, samples=None,
-                 labels_override=None, mode="val", box=sweeps.BOX, h2d_mode="copy_stream", post_fn=None, evaluate=False, visualize=None):
+                 labels_override=None, mode="val", box=sweeps.BOX, h2d_mode="copy_stream", post_fn=None, evaluate=False, visualize=None, confidence=False):
         self._check_h2d_mode(h2d_mode)
         _ragged._check_max_frame_points("sweeps", max_frame_points)
         sweeps._box(box)
@@ -106,7 +106,7 @@ class SweepFrameExecutor(PreparedFrameExecutor):
         sample_prep.option_block(opt, self.raw_hw, mode, dataset="nuscenes")
         self.cols = self._check_batch(example_batch)[-1]          # 4 or 5: the example's
         super().__init__(mm, pipe, example_batch, n_streams=n_streams, use_graph=use_graph, restarts=restarts, labels_override=labels_override,
-                         post_fn=post_fn, h2d_mode=h2d_mode, samples=samples, evaluate=evaluate, visualize=visualize)
+                         post_fn=post_fn, h2d_mode=h2d_mode, samples=samples, evaluate=evaluate, visualize=visualize, confidence=confidence)
 
     def _check_batch(self, host_batch):
         return host_sweep_frames(host_batch, self.B, self.S_cap, self.cap_raw, self.raw_hw, self.cols)

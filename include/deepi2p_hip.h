@@ -838,6 +838,46 @@ int di2p_world_render_profiles(const double* prims, const int32_t* count, int B,
                                double reflectance_sigma, unsigned long long seed, const unsigned long long* seed_dev, int frame0, double* scan_xyr,
                                int32_t* scan_offsets, int32_t* out_count, int32_t* status, void* workspace, void* stream);
 
+/* ---- (additive, ABI 9; detect by symbol) pose confidence (csrc/solver.hip): information matrix, covariance, restart consensus ----------------------
+ * No allocation, no synchronisation, no atomics: every entry point can be captured into a hipGraph, and a frame's outputs are bit-identical
+ * from run to run and do not depend on F or on the frame's position in the batch.
+ * WHAT THE NUMBERS ARE.  info, grad and cov live in the SOLVER's parameterisation ([ry, tx, ty, tz] or [angle-axis, t] of the points the
+ *   solve was given; for a frame="enu" pipeline that is the pose P_cam of the converted points, not P).  No noise scale is fitted: the
+ *   residuals are pixels (and 100 x metres behind the camera) under a Cauchy loss of scale 1, so cov = info^-1 is NOT a covariance in
+ *   metres^2 / radians^2 of the expected pose error.  sigma_t and sigma_r are a RELATIVE measure between frames of one configuration (same
+ *   camera, image size, point count, labels source): a larger value means a flatter minimum, nothing more.
+ * di2p_pose_information: at given parameters, the Cauchy-weighted normal matrix the Levenberg-Marquardt step uses (and Ceres' covariance
+ *   would): info f64[F,np,np] = sum over residual blocks of rho'(s) J^T J (full symmetric matrix, rho' = 1 / (1 + s), s = |r_block|^2; a
+ *   label-1 point is a block of 3 rows, a label-0 point a block of 1, residuals and Jacobians those of registration_2d.hpp /
+ *   registration_3d.hpp, the angle-axis rotation with its first-order branch at theta^2 <= DBL_EPSILON), grad f64[F,np] = sum rho'(s) J^T r
+ *   (the gradient of the cost), cost f64[F] = 1/2 sum log1p(s), active i32[F,2] = the label-1 and the label-0 points with a non-zero
+ *   residual block (the points that constrain the pose).  points f32[F,3,N] (widened per element), labels i32[F,N] (anything outside
+ *   {0, 1} is skipped: di2p_initial_guess' labels_out works as it is), K f64[F,3,3], params f64[F,np], np = 4 if is_2d else 6.
+ *   Two launches: grid (F, C), C = ceil(N / 1024), every workgroup reducing its 1024 points in a fixed order into the workspace, then the C
+ *   partials of a frame added in index order.  workspace: di2p_pose_information_workspace_bytes(F, N) bytes, 8-byte aligned.  N <= 65535 * 1024.
+ * di2p_gather_best_params: out f64[F,np] = params[f, best[f]] of params f64[F,R,np] (di2p_select_best's best; a frame with best outside
+ *   [0, R) -- has_inside == 0 -- takes restart 0).
+ * di2p_pose_covariance: cov f64[F,np,np] = the inverse of info over the FREE parameters, by fp64 Cholesky, one thread per frame.  A
+ *   translation parameter exactly on its bound (x == lb or x == ub; the solver projects onto the box, so equality is exact) is fixed: its
+ *   row and column are removed before the inversion and its entries of cov are 0.  free_mask i32[F]: bit i set = parameter i is free.
+ *   status i32[F]: 0 ok; 1 not positive definite (a pivot <= np * DBL_EPSILON * max_i info_ii over the free i, or no free parameter);
+ *   2 has_inside[f] == 0 (has_inside may be NULL) or a non-finite entry of info or params.  sigma_t f64[F] = sqrt(trace of the translation
+ *   block of cov), sigma_r f64[F] = sqrt(trace of the rotation block) * 180 / pi.  For status != 0 cov, sigma_t and sigma_r are NaN;
+ *   free_mask is written all the same.  cov is exactly symmetric.  lb_host / ub_host: f64[3] HOST arrays, the solve's bounds.
+ * di2p_restart_consensus: params f64[F,R,np], cost f64[F,R] (di2p_solve_batched's outputs), best i32[F] -> finite i32[F]: restarts with a
+ *   finite cost; agree i32[F]: those of them whose pose is within t_tol and r_tol_deg of the best one's, by get_P_diff's rule (the device
+ *   code of di2p_pose_errors) on P_r^-1 P_best: translation norm < t_tol and summed absolute 'xzy' Euler angles in degrees < r_tol_deg; the
+ *   best counts itself.  gap f64[F] = (smallest cost among the finite restarts that do not agree) - cost[best]; +inf when all agree.  A frame
+ *   with has_inside[f] == 0 (may be NULL) or best outside [0, R) gets finite = agree = 0 and gap = NaN.  One wave per frame, any R >= 1. */
+long long di2p_pose_information_workspace_bytes(int F, int N);
+int di2p_pose_information(const float* points, const int32_t* labels, const double* K, const double* params, double H, double W, int is_2d,
+                          int F, int N, double* info, double* grad, double* cost, int32_t* active, void* workspace, void* stream);
+int di2p_gather_best_params(const double* params, const int32_t* best, int is_2d, int F, int R, double* out, void* stream);
+int di2p_pose_covariance(const double* info, const double* params, const int32_t* has_inside, const double* lb_host, const double* ub_host,
+                         int is_2d, int F, double* cov, int32_t* free_mask, int32_t* status, double* sigma_t, double* sigma_r, void* stream);
+int di2p_restart_consensus(const double* params, const double* cost, const int32_t* best, const int32_t* has_inside, int is_2d, int F, int R,
+                           double t_tol, double r_tol_deg, int32_t* finite, int32_t* agree, double* gap, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
