@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libdeepi2p_hip.so")
-SOURCES = ["common.cpp", "index_max.hip", "ball_query.hip", "point_ops.hip", "gemm.hip", "conv.hip", "solver.hip", "prep.hip", "pnp.hip", "rng.hip", "loss.hip", "train.hip", "winograd.hip", "stem.hip", "conv_x3.hip", "head_x3.hip", "stem_x3.hip", "head_labels_x3.hip", "scan_prep.hip", "sample_prep.hip", "eval.hip", "vis.hip", "submap.hip", "sweeps.hip", "world.hip"]
+SOURCES = ["common.cpp", "index_max.hip", "ball_query.hip", "point_ops.hip", "gemm.hip", "conv.hip", "solver.hip", "solver_aux.hip", "prep.hip", "pnp.hip", "rng.hip", "loss.hip", "train.hip", "winograd.hip", "stem.hip", "conv_x3.hip", "head_x3.hip", "stem_x3.hip", "head_labels_x3.hip", "scan_prep.hip", "sample_prep.hip", "eval.hip", "vis.hip", "submap.hip", "sweeps.hip", "world.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc"] + os.environ.get("DI2P_EXTRA_HIPCC_FLAGS", "").split()
 # hipcc's SLP vectoriser turns adjacent scalar fp32 adds / multiplies (epilogues, the Winograd transforms, the solver's fp32
@@ -23,7 +23,10 @@ SLP_ON = set(os.environ.get("DI2P_SLP_ON", "pnp.hip prep.hip").split())
 # the one lane whose latency the whole workgroup waits for.  Without that pass the kernel has no scratch at all (tools/kernel_resources.py)
 # and measures 7.8 vs 8.2 ms per launch; `-mllvm -sink-insts-to-avoid-spills` (the targeted fix) measures 7.95.  IR-level LICM is unaffected.
 # scan_prep.hip: voxel keys, means and distances are compared with numpy bit for bit; no multiply-add pair may become an FMA.
-PER_FILE_FLAGS = {"solver.hip": os.environ.get("DI2P_SOLVER_FLAGS", "-mllvm -disable-machine-licm").split(),
+SOLVER_FLAGS = os.environ.get("DI2P_SOLVER_FLAGS", "-mllvm -disable-machine-licm").split()
+PER_FILE_FLAGS = {"solver.hip": SOLVER_FLAGS,
+                  # solver_aux.hip: inherited from solver.hip, where these kernels came from, to keep their code identical; never measured for them
+                  "solver_aux.hip": SOLVER_FLAGS,
                   "scan_prep.hip": ["-ffp-contract=off"],
                   # point_ops.hip: the kNN distances and weights and the interpolation sums are written with __fmul_rn / __fadd_rn and documented
                   # as separately rounded, but hipcc expands those to plain * and + and contracted them into FMAs all the same (a third of the

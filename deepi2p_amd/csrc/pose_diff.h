@@ -1,5 +1,5 @@
 // get_P_diff (evaluation/registration_lsq.py:87-95) on the device, shared by pose_errors_kernel (eval.hip) and restart_consensus_kernel
-// (solver.hip): translation norm and summed absolute extrinsic 'xzy' Euler angles, in degrees, of A^-1 G.
+// (solver_aux.hip): translation norm and summed absolute extrinsic 'xzy' Euler angles, in degrees, of A^-1 G.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

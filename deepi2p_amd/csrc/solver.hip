@@ -17,9 +17,13 @@
 //     Levenberg-Marquardt state machine (damping, box projection, Armijo search, accept/reject, termination tests) lives
 //     in LDS and is advanced by thread 0 between sweeps.
 // The algorithm statement is the oracle's (oracle/frustum_lm.cpp); DESIGN.md lists it step by step.
+// This file: the sweep, solve_kernel, the workspace layout and the two solve entry points.  solver_model.h: the shared geometry;
+// solver_prep.h: frame preparation; solver_lm.h: the LM lane; solver_aux.hip: the once-per-frame kernels (initial guess, argmin,
+// residuals, pose confidence).
 #include "common.h"
-#include "pose_diff.h"
+#include "solver_model.h"
 #include "solver_prep.h"
+#include "solver_lm.h"
 
 #include <float.h>
 #include <math.h>
@@ -43,71 +47,6 @@
 #endif
 
 namespace {
-
-enum { T_MAX_ITER = 0, T_GRADIENT = 1, T_PARAMETER = 2, T_FUNCTION = 3, T_RADIUS = 4, T_INVALID = 5, T_EVAL_FAIL = 6 };
-
-struct Cam { double fx, fy, cx, cy, H1, W1; };
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-template <int NP> struct Tri { static constexpr int N = NP * (NP + 1) / 2; };
-template <int NP> __device__ __forceinline__ constexpr int tri(int a, int b) { return a >= b ? a * (a + 1) / 2 + b : b * (b + 1) / 2 + a; }
-
-// Rotation of the current iterate and its parameter derivatives, computed once per sweep.
-template <int NP>
-struct Rot {
-    double R[9];        // row-major
-    double dR[3][9];    // NP == 6 only: dR/dw_i
-};
-
-__device__ __forceinline__ void skew_add(double* M, double s, double ux, double uy, double uz) {  // M += s*[u]x
-    M[1] -= s * uz; M[2] += s * uy; M[3] += s * uz; M[5] -= s * ux; M[6] -= s * uy; M[7] += s * ux;
-}
-
-template <int NP>
-__device__ __forceinline__ void make_rot(const double* x, Rot<NP>& r) {
-    if (NP == 4) {
-        // AngleAxisRotatePoint with axis (0,theta,0): Ry(theta); first-order branch for theta^2 <= eps
-        const double th = x[0];
-        double c, s;
-        if (th * th > DBL_EPSILON) { sincos(th, &s, &c); } else { c = 1.0; s = th; }      // one argument reduction for both
-        r.R[0] = c; r.R[1] = 0; r.R[2] = s; r.R[3] = 0; r.R[4] = 1; r.R[5] = 0; r.R[6] = -s; r.R[7] = 0; r.R[8] = c;
-    } else {
-        const double wx = x[0], wy = x[1], wz = x[2];
-        const double t2 = wx * wx + wy * wy + wz * wz;
-        for (int i = 0; i < 9; ++i) { r.R[i] = 0; r.dR[0][i] = r.dR[1][i] = r.dR[2][i] = 0; }
-        if (t2 > DBL_EPSILON) {
-            const double th = sqrt(t2), ux = wx / th, uy = wy / th, uz = wz / th;
-            double c, s;
-            sincos(th, &s, &c);
-            const double oc = 1.0 - c;
-            const double u[3] = {ux, uy, uz};
-            r.R[0] = r.R[4] = r.R[8] = c;
-            skew_add(r.R, s, ux, uy, uz);
-            for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) r.R[a * 3 + b] += oc * u[a] * u[b];
-            for (int i = 0; i < 3; ++i) {
-                double du[3];
-                for (int j = 0; j < 3; ++j) du[j] = ((i == j ? 1.0 : 0.0) - u[i] * u[j]) / th;
-                double* D = r.dR[i];
-                D[0] = D[4] = D[8] = -s * u[i];
-                skew_add(D, c * u[i], ux, uy, uz);
-                skew_add(D, s, du[0], du[1], du[2]);
-                for (int a = 0; a < 3; ++a)
-                    for (int b = 0; b < 3; ++b) D[a * 3 + b] += s * u[i] * u[a] * u[b] + oc * (du[a] * u[b] + u[a] * du[b]);
-            }
-        } else {  // pt + w x pt
-            r.R[0] = r.R[4] = r.R[8] = 1.0;
-            skew_add(r.R, 1.0, wx, wy, wz);
-            skew_add(r.dR[0], 1.0, 1, 0, 0);
-            skew_add(r.dR[1], 1.0, 0, 1, 0);
-            skew_add(r.dR[2], 1.0, 0, 0, 1);
-        }
-    }
-}
 
 // ----------------------------------------------------------------------------------------------
 // One sweep over the frame's records by the 4 waves of a hypothesis' workgroup.
@@ -144,43 +83,6 @@ struct SweepShared {
     alignas(16) double ring[8][NP];                // iterates of the last RING sweeps (slot = sweep number % RING), see the classification cache
     double rot_cs[2];                              // 2-D solver: cos / sin of the iterate about to be swept, computed ONCE per sweep by the LM lane
 };
-
-// v_rcp_f64 + two Newton steps: <= 1 ulp for finite non-zero inputs; 0 / inf / NaN give inf / 0 / NaN-like values that the
-// callers' finiteness tests catch.  ~5 instructions instead of the ~15 of the IEEE division sequence.
-__device__ __forceinline__ double fast_rcp(double v) {
-    double r = __builtin_amdgcn_rcp(v);
-    r = fma(fma(-v, r, 1.0), r, r);
-    r = fma(fma(-v, r, 1.0), r, r);
-    return r;
-}
-
-// Division and square root of the LM update's linear solve: reciprocal / reciprocal square root + Newton corrections (<= 1 ulp) instead of
-// the IEEE sequences (~25 instructions each with their scaling and fix-up steps) -- 16 of them sit on the critical lane per LM iteration
-// (finish + begin 5.8 k -> 4.9 k cycles per sweep).  The HIP-vs-oracle agreement is unchanged hypothesis for hypothesis, iteration
-// counts included (tools/solver_oracle_agreement.py, tools/ab_fastdiv.sh); -DDI2P_SOLVER_IEEEDIV restores the IEEE forms.
-#ifndef DI2P_SOLVER_IEEEDIV
-#define DI2P_SOLVER_FASTDIV 1
-#endif
-__device__ __forceinline__ double lm_div(double a, double b) {
-#ifdef DI2P_SOLVER_FASTDIV
-    const double r = fast_rcp(b), q = a * r;
-    return fma(fma(-b, q, a), r, q);
-#else
-    return a / b;
-#endif
-}
-__device__ __forceinline__ double lm_sqrt(double a) {
-#ifdef DI2P_SOLVER_FASTDIV
-    const double y = __builtin_amdgcn_rsq(a);
-    double g = a * y, h = 0.5 * y;
-    const double r = fma(-h, g, 0.5);
-    g = fma(g, r, g); h = fma(h, r, h);
-    const double v = fma(fma(-g, g, a), h, g);
-    return a == 0.0 ? 0.0 : v;              // rsq(0) = inf would turn sqrt(0) into NaN: a zero step / iterate norm must satisfy the parameter tolerance
-#else
-    return sqrt(a);
-#endif
-}
 
 template <int NP, typename PT, bool FAST_RCP = false>
 __device__ __forceinline__ void project(const Rec<PT>& rc, const Rot<NP>& rot, double tx, double ty, double tz, const Cam& k,
@@ -951,531 +853,6 @@ __device__ __forceinline__ void sweep(const Rec<PT>* __restrict__ recs, const Bo
     if (PROFILE) tp[3] += clock64() - tq1;      // wave totals
 }
 
-// Cholesky solve of M y = rhs IN PLACE: M (lower triangle, row-major) is overwritten by its factor L, y holds rhs on entry and the
-// solution on return (forward substitution, then backward substitution, both in place).  Same operations in the same order as the
-// oracle's chol_solve; written in place because the LM update runs on one lane of a kernel whose register budget is set by the sweep --
-// separate M / L / z arrays pushed it into scratch.
-template <int NP>
-__device__ __forceinline__ bool chol_solve_inplace(double* M, double* y) {
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-#pragma unroll
-        for (int j = 0; j <= i; ++j) {
-            double s = M[i * (i + 1) / 2 + j];
-#pragma unroll
-            for (int q = 0; q < j; ++q) s -= M[i * (i + 1) / 2 + q] * M[j * (j + 1) / 2 + q];
-            if (i == j) {
-                if (!(s > 0.0) || !isfinite(s)) return false;
-                M[i * (i + 1) / 2 + i] = lm_sqrt(s);
-            } else {
-                M[i * (i + 1) / 2 + j] = lm_div(s, M[j * (j + 1) / 2 + j]);
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-        double s = y[i];
-#pragma unroll
-        for (int q = 0; q < i; ++q) s -= M[i * (i + 1) / 2 + q] * y[q];
-        y[i] = lm_div(s, M[i * (i + 1) / 2 + i]);
-    }
-#pragma unroll
-    for (int i = NP - 1; i >= 0; --i) {
-        double s = y[i];
-#pragma unroll
-        for (int q = i + 1; q < NP; ++q) s -= M[q * (q + 1) / 2 + i] * y[q];
-        y[i] = lm_div(s, M[i * (i + 1) / 2 + i]);
-    }
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < NP; ++i) ok &= isfinite(y[i]);
-    return ok;
-}
-
-template <int NP>
-__device__ __forceinline__ void plus_proj(const double* x, const double* d, double t, const double* lb, const double* ub, double* out) {
-#pragma unroll
-    for (int i = 0; i < NP; ++i) out[i] = fmin(fmax(x[i] + t * d[i], lb[i]), ub[i]);
-}
-
-template <int NP>
-__device__ __forceinline__ double grad_max_norm(const double* x, const double* g, const double* lb, const double* ub) {
-    double m = 0.0;
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-        const double pr = fmin(fmax(x[i] - g[i], lb[i]), ub[i]);
-        m = fmax(m, fabs(x[i] - pr));
-    }
-    return m;
-}
-
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Ceres' ArmijoLineSearch with CUBIC interpolation (line_search.cc, polynomial.cc), same statement as the oracle's:
-// the next step minimises, over [1e-3, 0.6] x current step, the polynomial interpolating value + directional derivative at
-// step 0, at the current trial and (when valid) at the previous trial.  Fitted in u = step / current step with the two
-// constraints at 0 eliminated; minimiser = best of {interval midpoint, ends, real critical points} (MinimizePolynomial).
-// Runs on ONE lane between sweeps: loops are unrolled over compile-time indices so that everything stays in registers.
-template <int DEG> __device__ __forceinline__ double poly_eval(const double* c, double u) {
-    double v = c[DEG];
-#pragma unroll
-    for (int i = DEG - 1; i >= 0; --i) v = fma(v, u, c[i]);
-    return v;
-}
-
-// ---- real critical points by the WHOLE wavefront (wave 0 runs this between sweeps; arguments are wave-uniform).
-// Same statement as the oracle's real_roots_in(): the roots of q inside [a,b] are isolated between consecutive roots of q'
-// (found the same way one degree down; degree 2 in closed form, as polynomial.cc's FindQuadraticPolynomialRoots), q is
-// monotone on each piece, so a sign change pins exactly one root.  The oracle solves a piece by scalar Newton/bisection
-// (~25 dependent fp64 divisions); here the 64 lanes sample the piece at 64 points, a ballot finds the sub-interval with the
-// sign change (three rounds: 63^3 = 2.5e5 x narrower), and three Newton steps with a reciprocal finish it to rounding.
-template <int DEG>
-__device__ __forceinline__ double wave_bracket_root(const double* q, double l, double r, double ql) {
-    const int lane = threadIdx.x & 63;
-    const bool lneg = ql < 0.0;
-#pragma unroll 1
-    for (int round = 0; round < 3; ++round) {
-        const double h = (r - l) * (1.0 / 63.0);
-        const double u = fma((double)lane, h, l);
-        const double v = poly_eval<DEG>(q, u);
-        const unsigned long long same = __ballot(v != 0.0 && (v < 0.0) == lneg);       // monotone piece: a prefix of lanes
-        const unsigned long long zero = __ballot(v == 0.0);
-        if (zero) return fma((double)__builtin_ctzll(zero), h, l);                       // a sample hit the root exactly
-        const int idx = same ? 63 - (int)__builtin_clzll(same) : 0;                      // last lane on the left side
-        l = fma((double)idx, h, l);
-        r = l + h;
-    }
-    double dq[DEG];
-#pragma unroll
-    for (int i = 1; i <= DEG; ++i) dq[i - 1] = i * q[i];
-    double x = 0.5 * (l + r);
-#pragma unroll
-    for (int it = 0; it < 3; ++it) {
-        const double qx = poly_eval<DEG>(q, x), d = poly_eval<DEG - 1>(dq, x);
-        const double xn = fma(-qx, fast_rcp(d), x);
-        x = (xn >= l && xn <= r) ? xn : x;         // NaN / runaway steps keep the bracketed iterate
-    }
-    return x;
-}
-
-template <int DEG> struct WaveRoots {
-    __device__ __forceinline__ static void run(const double* q, double a, double b, bool* has, double* val) {
-        if (q[DEG] == 0.0) {                                   // RemoveLeadingZeros (polynomial.cc)
-            WaveRoots<DEG - 1>::run(q, a, b, has, val);
-            has[DEG - 1] = false;
-            return;
-        }
-        double dq[DEG], vc[DEG - 1];
-        bool hc[DEG - 1];
-#pragma unroll
-        for (int i = 1; i <= DEG; ++i) dq[i - 1] = i * q[i];
-        WaveRoots<DEG - 1>::run(dq, a, b, hc, vc);
-        double l = a, ql = poly_eval<DEG>(q, a);
-#pragma unroll
-        for (int i = 0; i < DEG; ++i) {
-            has[i] = false;
-            const bool last = i == DEG - 1;
-            if (last || hc[last ? 0 : i]) {                    // wave-uniform
-                const double r = last ? b : vc[last ? 0 : i];
-                const double qr = poly_eval<DEG>(q, r);
-                if (ql == 0.0) { has[i] = true; val[i] = l; }
-                else if (qr != 0.0 && (ql < 0.0) != (qr < 0.0)) { has[i] = true; val[i] = wave_bracket_root<DEG>(q, l, r, ql); }
-                l = r; ql = qr;
-            }
-        }
-    }
-};
-template <> struct WaveRoots<2> {      // closed form, the numerically stable pair of FindQuadraticPolynomialRoots; ascending, inside [a,b]
-    __device__ __forceinline__ static void run(const double* q, double a, double b, bool* has, double* val) {
-        has[0] = has[1] = false;
-        if (q[2] == 0.0) {
-            if (q[1] == 0.0) return;
-            const double r = -q[0] / q[1];
-            if (r >= a && r <= b) { has[0] = true; val[0] = r; }
-            return;
-        }
-        const double D = q[1] * q[1] - 4.0 * q[2] * q[0];
-        if (!(D >= 0.0)) return;
-        const double sD = sqrt(D);
-        const double t = q[1] >= 0.0 ? -q[1] - sD : -q[1] + sD;
-        double r0 = t / (2.0 * q[2]), r1 = t != 0.0 ? (2.0 * q[0]) / t : r0;
-        if (r0 > r1) { const double tmp = r0; r0 = r1; r1 = tmp; }
-        if (r0 >= a && r0 <= b) { has[0] = true; val[0] = r0; }
-        if (r1 >= a && r1 <= b && r1 != r0) { has[1] = true; val[1] = r1; }
-        if (!has[0] && has[1]) { has[0] = true; val[0] = val[1]; has[1] = false; }
-    }
-};
-template <> struct WaveRoots<1> {
-    __device__ __forceinline__ static void run(const double* q, double a, double b, bool* has, double* val) {
-        has[0] = false;
-        if (q[1] == 0.0) return;
-        const double r = -q[0] / q[1];
-        if (r >= a && r <= b) { has[0] = true; val[0] = r; }
-    }
-};
-
-// MinimizePolynomial (polynomial.cc): interval midpoint first, then both ends, then the critical points, strict "<".
-// Called by every lane of wave 0 with the same arguments; returns the same value on every lane.
-__device__ __forceinline__ double poly_min_on_wave(const double* p, double umin, double umax) {     // p: degree <= 5, ascending
-    double best_u = 0.5 * (umin + umax), best_v = poly_eval<5>(p, best_u);
-    const double vmin = poly_eval<5>(p, umin);
-    if (vmin < best_v) { best_v = vmin; best_u = umin; }
-    const double vmax = poly_eval<5>(p, umax);
-    if (vmax < best_v) { best_v = vmax; best_u = umax; }
-    double dp[5], val[4];
-    bool has[4];
-#pragma unroll
-    for (int i = 1; i <= 5; ++i) dp[i - 1] = i * p[i];
-    WaveRoots<4>::run(dp, umin, umax, has, val);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-        if (has[i]) {
-            const double v = poly_eval<5>(p, val[i]);
-            if (v < best_v) { best_v = v; best_u = val[i]; }
-        }
-    return best_u;
-}
-
-struct LsSample { double x, value, gradient; bool value_ok, grad_ok; };
-
-// LineSearch::InterpolatingPolynomialMinimizingStepSize, CUBIC: p(u) = f0 + g0 xc u + u^2 (r0 + r1 u + r2 u^2 + r3 u^3) with one
-// coefficient per valid constraint {cur value, cur gradient, prev value, prev gradient}; missing constraints pin the
-// highest coefficients to zero (unit rows), so the 4x4 elimination below always runs on compile-time indices.
-// -> true: p[0..5] holds the interpolant in u = step / cur.x, to be minimised over [min_step, max_step] / cur.x ; false: the next
-// step is the bisection step (invalid current sample, or a non-finite fit).
-__device__ __forceinline__ bool interpolating_fit(double f0, double g0, const LsSample& cur, const LsSample& prev, double* p) {
-    if (!cur.value_ok) return false;
-    const double xc = cur.x, G0 = g0 * xc;
-    const double up = prev.value_ok ? lm_div(prev.x, xc) : 2.0;
-    const bool valid[4] = {true, cur.grad_ok, prev.value_ok, prev.value_ok && prev.grad_ok};
-    const int m = 1 + (valid[1] ? 1 : 0) + (valid[2] ? 1 : 0) + (valid[3] ? 1 : 0);
-    double A[4][5];
-    {
-        const double us[4] = {1.0, 1.0, up, up};
-        const double rhs[4] = {cur.value - f0 - G0, cur.gradient * xc - G0, prev.value - f0 - G0 * up, prev.gradient * xc - G0};
-        int pad = m;                                           // next coefficient pinned to zero
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const bool is_grad = (i & 1) != 0;
-            double pw = is_grad ? us[i] : us[i] * us[i];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const double e = is_grad ? (j + 2) * pw : pw;
-                A[i][j] = valid[i] ? (j < m ? e : 0.0) : (j == pad ? 1.0 : 0.0);
-                pw *= us[i];
-            }
-            A[i][4] = valid[i] ? rhs[i] : 0.0;
-            if (!valid[i]) ++pad;
-        }
-    }
-    // Gaussian elimination with partial pivoting
-    bool singular = false;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        int piv = c;
-        double pv = fabs(A[c][c]);
-#pragma unroll
-        for (int i = c + 1; i < 4; ++i) if (fabs(A[i][c]) > pv) { pv = fabs(A[i][c]); piv = i; }
-        if (pv == 0.0) singular = true;
-#pragma unroll
-        for (int i = c + 1; i < 4; ++i)
-            if (i == piv) {
-#pragma unroll
-                for (int j = 0; j < 5; ++j) { const double t = A[i][j]; A[i][j] = A[c][j]; A[c][j] = t; }
-            }
-        const double inv = singular ? 0.0 : lm_div(1.0, A[c][c]);
-#pragma unroll
-        for (int i = c + 1; i < 4; ++i) {
-            const double f = A[i][c] * inv;
-#pragma unroll
-            for (int j = c; j < 5; ++j) A[i][j] -= f * A[c][j];
-        }
-    }
-    double r[4] = {0.0, 0.0, 0.0, 0.0};
-    if (!singular) {
-#pragma unroll
-        for (int c = 3; c >= 0; --c) {
-            double v = A[c][4];
-#pragma unroll
-            for (int j = c + 1; j < 4; ++j) v -= A[c][j] * r[j];
-            r[c] = lm_div(v, A[c][c]);
-        }
-    }
-    p[0] = f0; p[1] = G0; p[2] = r[0]; p[3] = m > 1 ? r[1] : 0.0; p[4] = m > 2 ? r[2] : 0.0; p[5] = m > 3 ? r[3] : 0.0;
-    bool fin = true;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) if (!isfinite(p[j])) fin = false;
-    return fin;
-}
-
-struct Bounds { double lb[3], ub[3]; };
-
-// Levenberg-Marquardt state of one hypothesis.  Lives ONCE per workgroup in LDS; thread 0 advances it between
-// sweeps (a few hundred scalar flops), so the sweep's register budget is not shared with it.
-enum { PH_INIT = 0, PH_TRIAL = 1 };
-template <int NP>
-struct LMState {
-    double x[NP], g[NP], A[Tri<NP>::N], S[NP], diag[NP], delta[NP], xe[NP];
-    double lb[NP], ub[NP];
-    double cost, gmax, radius, decrease, gd, dmax, t, f1, model_change;
-    int iter, nsweep, invalid_run, ls_it, phase, reuse_diag, ok1, done, max_iter;
-    int want_j;        // what the NEXT sweep must produce: 2 = cost + gradient + normal equations, 1 = cost + gradient
-    double g1[NP], A1[Tri<NP>::N];     // sums of the FIRST trial point (t = 1): the candidate when the line search fails
-    double prev_t, prev_f, prev_g;     // previous line-search sample (step, cost, directional derivative)
-    int prev_vok, prev_gok;
-    double poly[6], tn;                // pending interpolant (u = step / t) for the wave-wide minimiser, and the step it returns
-    int poly_req, pad_;
-    int n_ls_extra, n_ls_late_accept, n_resweep;      // diagnostics: line-search trials beyond the first, accepted ones among them, re-sweeps
-};
-
-// Round 6: the LM stages fetch the state they work on from LDS IN ONE BATCH into registers (pinned: every load is issued, then one wait)
-// instead of field by field between the arithmetic -- the update runs on one lane, so every LDS round trip it waits for (the copy loops
-// alone were 14 read -> wait -> write pairs) is a round trip the whole workgroup waits for.  Same operations on the same values:
-// bit-identical; finish + begin 8.5 k -> 7.5 k cycles per iteration (profiles/r06_c6_prepare.txt), no more scratch.
-#ifdef DI2P_SOLVER_LMPROF
-// variant build: cycles of the LM lane's sub-stages, summed over a hypothesis' iterations (tools/bench_solver.py LMPROF=1 prints them)
-//   [0] finish_iteration  [1] begin: fetch + scaled matrix  [2] Cholesky solve  [3] model change  [4] begin: step, projection, stores
-//   [5] decide without the fit  [6] interpolating fit  [7] trial_next_decide
-__shared__ long long g_lmclk[8];
-#define DI2P_LMSTAMP(t) long long t = clock64()                         // start a stamp
-#define DI2P_LMRESTAMP(t) t = clock64()                                 // restart it
-#define DI2P_LMCLK(i, t0) g_lmclk[i] += clock64() - (t0)                // add the time since a stamp to sub-stage i ...
-#define DI2P_LMADD(field, t0) field += (int)(clock64() - (t0))          // ... or to a field of the LM state
-#else
-#define DI2P_LMSTAMP(t) ((void)0)
-#define DI2P_LMRESTAMP(t) ((void)0)
-#define DI2P_LMCLK(i, t0) ((void)0)
-#define DI2P_LMADD(field, t0) ((void)0)
-#endif
-template <int N> __device__ __forceinline__ void pin_regs(double* v) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) asm volatile("" : "+v"(v[i]));
-}
-
-template <int NP>
-__device__ __forceinline__ void lm_begin_iteration(LMState<NP>& st) {
-    constexpr int NT = Tri<NP>::N;
-    const double kMinDiag = 1e-6, kMaxDiag = 1e32, kMinRadius = 1e-32, kGradTol = 1e-10;
-    DI2P_LMSTAMP(tb0);
-    double S[NP], A[NT], g[NP], diag[NP], sc[3];
-#pragma unroll
-    for (int a = 0; a < NP; ++a) { S[a] = st.S[a]; g[a] = st.g[a]; diag[a] = st.diag[a]; }
-#pragma unroll
-    for (int i = 0; i < NT; ++i) A[i] = st.A[i];
-    sc[0] = st.gmax; sc[1] = st.radius; sc[2] = st.decrease;
-    int iter = st.iter, reuse_diag = st.reuse_diag, invalid_run = st.invalid_run;
-    const int max_iter = st.max_iter;
-    pin_regs<NP>(S); pin_regs<NP>(g); pin_regs<NP>(diag); pin_regs<NT>(A); pin_regs<3>(sc);
-    const double gmax = sc[0];
-    double radius = sc[1], decrease = sc[2];
-    auto scaled_A = [&](int a, int b) { const int hi = a >= b ? a : b, lo = a >= b ? b : a; return S[hi] * A[hi * (hi + 1) / 2 + lo] * S[lo]; };
-    auto write_back = [&]() { st.iter = iter; st.radius = radius; st.decrease = decrease; st.reuse_diag = reuse_diag; st.invalid_run = invalid_run; };
-    for (;;) {
-        if (iter >= max_iter || gmax <= kGradTol || radius <= kMinRadius) { write_back(); st.done = 1; return; }
-        ++iter;
-        double M[NT], ds[NP];
-#pragma unroll
-        for (int a = 0; a < NP; ++a)
-#pragma unroll
-            for (int b = 0; b <= a; ++b) M[a * (a + 1) / 2 + b] = scaled_A(a, b);
-        if (!reuse_diag) {
-#pragma unroll
-            for (int a = 0; a < NP; ++a) { diag[a] = fmin(fmax(M[a * (a + 1) / 2 + a], kMinDiag), kMaxDiag); st.diag[a] = diag[a]; }
-        }
-#pragma unroll
-        for (int a = 0; a < NP; ++a) { M[a * (a + 1) / 2 + a] += lm_div(diag[a], radius); ds[a] = -(S[a] * g[a]); }
-        DI2P_LMCLK(1, tb0);
-        DI2P_LMSTAMP(tc0);
-        bool valid = chol_solve_inplace<NP>(M, ds);
-        DI2P_LMADD(st.n_resweep, tc0);
-        DI2P_LMCLK(2, tc0);
-        DI2P_LMSTAMP(tm0);
-        double model_change = 0.0;
-        if (valid) {
-            double q = 0.0, l = 0.0;
-#pragma unroll
-            for (int a = 0; a < NP; ++a) {
-                l += ds[a] * (S[a] * g[a]);
-#pragma unroll
-                for (int b = 0; b < NP; ++b) q += ds[a] * scaled_A(a, b) * ds[b];
-            }
-            model_change = -(l + 0.5 * q);
-            valid = model_change > 0.0;
-        }
-        DI2P_LMCLK(3, tm0);
-        DI2P_LMSTAMP(tp0);
-        if (!valid) {
-            if (++invalid_run >= 5) { write_back(); st.done = 1; return; }
-            radius /= decrease; decrease *= 2.0; reuse_diag = 1;
-            DI2P_LMRESTAMP(tb0);
-            continue;
-        }
-        invalid_run = 0;
-        write_back();
-        st.model_change = model_change;
-        double x[NP], lb[NP], ub[NP], delta[NP];
-#pragma unroll
-        for (int a = 0; a < NP; ++a) { x[a] = st.x[a]; lb[a] = st.lb[a]; ub[a] = st.ub[a]; }
-        pin_regs<NP>(x); pin_regs<NP>(lb); pin_regs<NP>(ub);
-        double gd = 0.0, dmax = 0.0;
-#pragma unroll
-        for (int a = 0; a < NP; ++a) {
-            delta[a] = ds[a] * S[a];
-            gd += g[a] * delta[a];
-            dmax = fmax(dmax, fabs(delta[a]));
-        }
-        double xe[NP];
-        plus_proj<NP>(x, delta, 1.0, lb, ub, xe);
-#pragma unroll
-        for (int a = 0; a < NP; ++a) { st.delta[a] = delta[a]; st.xe[a] = xe[a]; }
-        st.gd = gd; st.dmax = dmax; st.t = 1.0; st.ls_it = 0;
-        st.phase = PH_TRIAL; st.want_j = 2; st.prev_vok = 0; st.prev_gok = 0;
-        DI2P_LMCLK(4, tp0);
-        return;   // needs a sweep at xe
-    }
-}
-
-// The LM update is a chain of STAGES, each instantiated exactly once in the kernel (lm_decide -> [wave-wide minimiser] ->
-// lm_trial_next_decide -> lm_apply = {lm_finish_iteration, lm_begin_iteration}); a stage hands the next one an action code.  (As
-// mutually calling inline functions the iteration start was instantiated five times: 13 k instructions, and the register allocator
-// spilled inside the sweep loops.)
-enum { ACT_NONE = 0, ACT_BEGIN = 1, ACT_FINISH_CUR = 2, ACT_FINISH_FIRST = 3, ACT_TRIAL_NEXT = 4, ACT_POLY = 5 };
-
-// candidate (xe, cand_cost, ge, Ae) against the current iterate: tolerance tests, accept / reject.  -> true: start the next iteration
-template <int NP>
-__device__ __forceinline__ bool lm_finish_iteration(LMState<NP>& st, double cand_cost, const double* ge, const double* Ae) {
-    constexpr int NT = Tri<NP>::N;
-    const double kMaxRadius = 1e16, kMinRelDec = 1e-3, kFuncTol = 1e-6, kParamTol = 1e-8;
-    double xo[NP], xn[NP], gl[NP], Al[NT], lb[NP], ub[NP], sc[4];
-#pragma unroll
-    for (int a = 0; a < NP; ++a) { xo[a] = st.x[a]; xn[a] = st.xe[a]; gl[a] = ge[a]; lb[a] = st.lb[a]; ub[a] = st.ub[a]; }
-#pragma unroll
-    for (int i = 0; i < NT; ++i) Al[i] = Ae[i];
-    sc[0] = st.cost; sc[1] = st.model_change; sc[2] = st.radius; sc[3] = st.decrease;
-    pin_regs<NP>(xo); pin_regs<NP>(xn); pin_regs<NP>(gl); pin_regs<NT>(Al); pin_regs<NP>(lb); pin_regs<NP>(ub); pin_regs<4>(sc);
-    double step_norm = 0.0, x_norm = 0.0;
-#pragma unroll
-    for (int a = 0; a < NP; ++a) { step_norm += (xo[a] - xn[a]) * (xo[a] - xn[a]); x_norm += xo[a] * xo[a]; }
-    step_norm = lm_sqrt(step_norm); x_norm = lm_sqrt(x_norm);
-    if (step_norm <= kParamTol * (x_norm + kParamTol)) { st.done = 1; return false; }
-    if (fabs(sc[0] - cand_cost) <= kFuncTol * sc[0]) { st.done = 1; return false; }
-    const double rel = lm_div(sc[0] - cand_cost, sc[1]);
-    if (rel > kMinRelDec) {
-#pragma unroll
-        for (int a = 0; a < NP; ++a) { st.x[a] = xn[a]; st.g[a] = gl[a]; }
-#pragma unroll
-        for (int i = 0; i < NT; ++i) st.A[i] = Al[i];
-        st.cost = cand_cost;
-        st.gmax = grad_max_norm<NP>(xn, gl, lb, ub);
-        const double w = 2.0 * rel - 1.0;
-        st.radius = fmin(kMaxRadius, lm_div(sc[2], fmax(1.0 / 3.0, 1.0 - w * w * w)));
-        st.decrease = 2.0; st.reuse_diag = 0;
-    } else {
-        st.radius = sc[2] / sc[3]; st.decrease = sc[3] * 2.0; st.reuse_diag = 1;
-    }
-    return true;
-}
-
-// Second half of a failed line-search trial: the next step size st.tn is known.  -> ACT_FINISH_FIRST when the search gives up
-// (the candidate is then the first trial point, whose sums were kept), ACT_NONE when the next sweep evaluates the new trial point.
-template <int NP>
-__device__ __forceinline__ int lm_trial_next_decide(LMState<NP>& st) {
-    const double tn = st.tn;
-    if (tn * st.dmax < 1e-9) return ACT_FINISH_FIRST;
-    st.t = tn;
-    plus_proj<NP>(st.x, st.delta, tn, st.lb, st.ub, st.xe);
-    return ACT_NONE;
-}
-
-// Last stage: finish the iteration with the chosen candidate (the point just swept, or the first trial point) and start the next one.
-template <int NP>
-__device__ __forceinline__ void lm_apply(LMState<NP>& st, int action, double fe, const double* ge, const double* Ae) {
-    bool begin = action == ACT_BEGIN;
-    if (action == ACT_FINISH_CUR || action == ACT_FINISH_FIRST) {
-        DI2P_LMSTAMP(tf0);
-        const bool first = action == ACT_FINISH_FIRST;
-        if (first) plus_proj<NP>(st.x, st.delta, 1.0, st.lb, st.ub, st.xe);     // delta stays unscaled: back to the first trial point
-        begin = lm_finish_iteration<NP>(st, first ? st.f1 : fe, first ? st.g1 : ge, first ? st.A1 : Ae);
-        DI2P_LMCLK(0, tf0);
-    }
-    if (begin) lm_begin_iteration<NP>(st);
-}
-
-// Wave 0, all lanes: minimise the pending interpolant (MinimizePolynomial over u in [1e-3 t, 0.6 t] / t).
-template <int NP>
-__device__ __forceinline__ void lm_poly_wave(LMState<NP>& st) {
-    double p[6];
-#pragma unroll
-    for (int j = 0; j < 6; ++j) p[j] = st.poly[j];
-    const double t = st.t;
-    const double u = poly_min_on_wave(p, (1e-3 * t) / t, (0.6 * t) / t);
-    if ((threadIdx.x & 63) == 0) st.tn = u * t;
-}
-
-// First stage, called by thread 0 after every sweep with the combined sums of the point just evaluated (st.xe).  -> action code
-template <int NP>
-__device__ __forceinline__ int lm_decide(LMState<NP>& st, bool ok, double fe, const double* ge_in, const double* Ae_in) {
-    double ge[NP], Ae[Tri<NP>::N];       // the combined sums, fetched in one batch (copied field by field they were read -> wait -> write pairs)
-#pragma unroll
-    for (int a = 0; a < NP; ++a) ge[a] = ge_in[a];
-#pragma unroll
-    for (int i = 0; i < Tri<NP>::N; ++i) Ae[i] = Ae_in[i];
-    pin_regs<NP>(ge); pin_regs<Tri<NP>::N>(Ae);
-    ++st.nsweep;
-    if (st.phase == PH_INIT) {
-        st.cost = fe;
-        // evaluation failure at the start: the sums that exist leave out the record that failed (a label-0 record on a frustum plane is flagged
-        // and skipped), so a finite fe is NOT the cost of this pose -- report NaN, as the reference's final evaluation does; never the argmin
-        if (!ok) { st.cost = __builtin_nan(""); st.done = 1; return ACT_NONE; }
-#pragma unroll
-        for (int a = 0; a < NP; ++a) { st.g[a] = ge[a]; st.S[a] = 1.0 / (1.0 + sqrt(Ae[a * (a + 1) / 2 + a])); }
-#pragma unroll
-        for (int i = 0; i < Tri<NP>::N; ++i) st.A[i] = Ae[i];
-        st.gmax = grad_max_norm<NP>(st.x, st.g, st.lb, st.ub);
-        return ACT_BEGIN;
-    }
-    // PH_TRIAL: projected Armijo search along delta (Ceres ArmijoLineSearch, CUBIC interpolation: every trial needs its
-    // gradient).  Every sweep also carries the normal equations (10 more fma per Jacobian row, ~3 % of a sweep), so whichever
-    // trial satisfies Armijo is used at once; the sums of the first trial (t = 1) are kept: it is the candidate when the
-    // search fails.
-    if (st.ls_it == 0) {
-        st.f1 = ok ? fe : DBL_MAX; st.ok1 = ok;
-#pragma unroll
-        for (int a = 0; a < NP; ++a) st.g1[a] = ge[a];
-#pragma unroll
-        for (int i = 0; i < Tri<NP>::N; ++i) st.A1[i] = Ae[i];
-    } else {
-        ++st.n_ls_extra;
-    }
-    if (ok && fe <= st.cost + 1e-4 * st.gd * st.t) {
-        if (st.ls_it > 0) ++st.n_ls_late_accept;
-        return ACT_FINISH_CUR;       // every sweep carries its normal equations: an accepted trial needs no second sweep
-    }
-    if (++st.ls_it >= 20) return ACT_FINISH_FIRST;      // the search gives up
-    LsSample cur{st.t, fe, 0.0, ok, false}, prev{st.prev_t, st.prev_f, st.prev_g, st.prev_vok != 0, st.prev_gok != 0};
-    if (ok) {
-        double gdir = 0.0;
-#pragma unroll
-        for (int a = 0; a < NP; ++a) gdir += st.delta[a] * ge[a];
-        cur.gradient = gdir;
-        cur.grad_ok = isfinite(gdir);
-    }
-    st.prev_t = cur.x; st.prev_f = cur.value; st.prev_g = cur.gradient; st.prev_vok = cur.value_ok; st.prev_gok = cur.grad_ok;
-    double p[6];
-    DI2P_LMSTAMP(tfit0);
-    const bool fitted = interpolating_fit(st.cost, st.gd, cur, prev, p);
-    DI2P_LMCLK(6, tfit0);
-    if (fitted) {
-        // the minimiser of the interpolant over [1e-3, 0.6] x t is found by the whole wavefront (lm_poly_wave), then lm_trial_next_decide
-#pragma unroll
-        for (int j = 0; j < 6; ++j) st.poly[j] = p[j];
-        st.poly_req = 1;
-        return ACT_POLY;
-    }
-    st.tn = fmin(fmax(st.t * 0.5, 1e-3 * st.t), 0.6 * st.t);
-    return ACT_TRIAL_NEXT;
-}
-
 // Kernel arguments as ONE struct: the kernel reads every field through the kernarg segment pointer (scalar loads from constant
 // memory at the point of use), so the fields that are only needed before / after the sweep loop (outputs, start values, the
 // diagnostics buffers) do not sit in SGPRs through it -- as plain kernel parameters hipcc loaded all 30 of them at entry and kept
@@ -1687,442 +1064,6 @@ __global__ __launch_bounds__(WPH * 64, MINW) void solve_kernel(const SolveArgs<P
     }
 }
 
-__device__ __forceinline__ void angle_axis_to_R(const double* w, double* R) {
-    const double t2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-    if (t2 > DBL_EPSILON) {
-        const double t = sqrt(t2), wx = w[0] / t, wy = w[1] / t, wz = w[2] / t, c = cos(t), s = sin(t);
-        R[0] = c + wx * wx * (1 - c);       R[1] = wx * wy * (1 - c) - wz * s;  R[2] = wy * s + wx * wz * (1 - c);
-        R[3] = wz * s + wx * wy * (1 - c);  R[4] = c + wy * wy * (1 - c);       R[5] = -wx * s + wy * wz * (1 - c);
-        R[6] = -wy * s + wx * wz * (1 - c); R[7] = wx * s + wy * wz * (1 - c);  R[8] = c + wz * wz * (1 - c);
-    } else {
-        R[0] = 1; R[1] = -w[2]; R[2] = w[1]; R[3] = w[2]; R[4] = 1; R[5] = -w[0]; R[6] = -w[1]; R[7] = w[0]; R[8] = 1;
-    }
-}
-
-// one wavefront per frame: argmin over R (ties -> lowest r), assemble P
-__global__ __launch_bounds__(64) void select_best_kernel(const double* __restrict__ params, const double* __restrict__ cost,
-                                                         const int* __restrict__ has_inside, int np, int R, int* __restrict__ best,
-                                                         double* __restrict__ P, double* __restrict__ best_cost) {
-    const int f = blockIdx.x, lane = threadIdx.x;
-    double bc = __builtin_inf();
-    int bi = 0x7fffffff;
-    for (int r = lane; r < R; r += 64) {
-        const double c = cost[(long long)f * R + r];
-        if (c < bc || (c == bc && r < bi)) { bc = c; bi = r; }   // NaN never wins
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double oc = __shfl_xor(bc, o);
-        const int oi = __shfl_xor(bi, o);
-        if (oc < bc || (oc == bc && oi < bi)) { bc = oc; bi = oi; }
-    }
-    if (lane != 0) return;
-    double* Pf = P + (long long)f * 16;
-    for (int i = 0; i < 16; ++i) Pf[i] = (i % 5 == 0) ? 1.0 : 0.0;
-    if (has_inside && has_inside[f] == 0) {  // registration_lsq.py:329-332
-        best[f] = -1;
-        best_cost[f] = 1e4;
-        return;
-    }
-    if (bi == 0x7fffffff) bi = 0;
-    const double* x = params + ((long long)f * R + bi) * np;
-    double w[3] = {0, 0, 0};
-    int toff;
-    if (np == 4) { w[1] = x[0]; toff = 1; } else { w[0] = x[0]; w[1] = x[1]; w[2] = x[2]; toff = 3; }
-    double Rm[9];
-    angle_axis_to_R(w, Rm);
-    for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) Pf[r * 4 + c] = Rm[r * 3 + c]; Pf[r * 4 + 3] = x[toff + r]; }
-    best[f] = bi;
-    best_cost[f] = cost[(long long)f * R + bi];
-}
-
-// registration_lsq.py:196-220.  One 1024-thread workgroup per frame, fixed-order tree reductions.
-__global__ __launch_bounds__(1024) void initial_guess_kernel(const double* __restrict__ points, const int* __restrict__ labels,
-                                                             double* __restrict__ yaw0, int* __restrict__ labels_out,
-                                                             int* __restrict__ has_inside, int N) {
-    __shared__ double s_a[1024], s_b[1024], s_c[1024];
-    const int f = blockIdx.x, tid = threadIdx.x;
-    const double* px = points + (long long)f * 3 * N;
-    const double* pz = px + 2 * (long long)N;
-    const int* lab = labels + (long long)f * N;
-    double sx = 0, sz = 0, cnt = 0;
-    for (int n = tid; n < N; n += 1024)
-        if (lab[n] == 1) { sx += px[n]; sz += pz[n]; cnt += 1.0; }
-    s_a[tid] = sx; s_b[tid] = sz; s_c[tid] = cnt;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if (tid < o) { s_a[tid] += s_a[tid + o]; s_b[tid] += s_b[tid + o]; s_c[tid] += s_c[tid + o]; }
-        __syncthreads();
-    }
-    const double count = s_c[0];
-    const double mx = s_a[0] / count, mz = s_b[0] / count;
-    __syncthreads();
-    if (!(count > 0.0)) {
-        if (tid == 0) { yaw0[f] = 0.0; has_inside[f] = 0; }
-        for (int n = tid; n < N; n += 1024) labels_out[(long long)f * N + n] = lab[n];
-        return;
-    }
-    const double kPi = 3.14159265358979323846;
-    double a = fmod(atan2(mz, mx) - kPi / 2 + kPi, 2 * kPi);   // wrap_in_pi (:189-193)
-    if (a < 0) a += 2 * kPi;
-    a -= kPi;
-    const double c = cos(a), s = sin(a);
-    double zmin = __builtin_inf();
-    for (int n = tid; n < N; n += 1024)
-        if (lab[n] == 1) zmin = fmin(zmin, -s * px[n] + c * pz[n]);
-    s_a[tid] = zmin;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if (tid < o) s_a[tid] = fmin(s_a[tid], s_a[tid + o]);
-        __syncthreads();
-    }
-    const double thr = s_a[0] - 10.0;
-    for (int n = tid; n < N; n += 1024) {
-        const double zr = -s * px[n] + c * pz[n];
-        labels_out[(long long)f * N + n] = zr > thr ? lab[n] : -1;
-    }
-    if (tid == 0) { yaw0[f] = a; has_inside[f] = 1; }
-}
-
-// Problem::Evaluate (registration.cpp:150-155): loss-corrected residuals in point order, compacted.
-template <int NP>
-__global__ __launch_bounds__(256) void residuals_kernel(const double* __restrict__ points, const int* __restrict__ labels,
-                                                        const double* __restrict__ Kmat, const double* __restrict__ params, double H,
-                                                        double W, int N, double* __restrict__ residuals, int* __restrict__ counts,
-                                                        double* __restrict__ cost_out) {
-    __shared__ int s_scan[256];
-    __shared__ double s_cost[256];
-    __shared__ int s_base;
-    constexpr int TOFF = NP == 4 ? 1 : 3;
-    const int f = blockIdx.x, tid = threadIdx.x;
-    const double* px = points + (long long)f * 3 * N;
-    const int* lab = labels + (long long)f * N;
-    const double* Kf = Kmat + (long long)f * 9;
-    const Cam k{Kf[0], Kf[4], Kf[2], Kf[5], H - 1.0, W - 1.0};
-    const double* x = params + (long long)f * NP;
-    double xr[NP];
-    for (int i = 0; i < NP; ++i) xr[i] = x[i];
-    Rot<NP> rot;
-    make_rot<NP>(xr, rot);
-    double* out = residuals + (long long)f * 3 * N;
-    if (tid == 0) s_base = 0;
-    double cost = 0.0;
-    __syncthreads();
-    for (int n0 = 0; n0 < N; n0 += 256) {
-        const int n = n0 + tid;
-        int nr = 0;
-        double rv[3] = {0, 0, 0};
-        if (n < N && (lab[n] == 0 || lab[n] == 1)) {
-            const double X = px[n], Y = px[N + n], Z = px[2 * (long long)N + n];
-            const double qx = rot.R[0] * X + rot.R[1] * Y + rot.R[2] * Z, qy = rot.R[3] * X + rot.R[4] * Y + rot.R[5] * Z,
-                         qz = rot.R[6] * X + rot.R[7] * Y + rot.R[8] * Z;
-            const double p0 = qx + xr[TOFF], p1 = qy + xr[TOFF + 1], p2 = qz + xr[TOFF + 2];
-            const double pix_x = p0 * k.fx / p2 + k.cx, pix_y = p1 * k.fy / p2 + k.cy;
-            if (lab[n] == 1) {
-                nr = 3;
-                rv[0] = fmax(-pix_x, 0.0) + fmax(pix_x - k.W1, 0.0);
-                rv[1] = fmax(-pix_y, 0.0) + fmax(pix_y - k.H1, 0.0);
-                rv[2] = fmax(-p2, 0.0) * 100.0;
-            } else {
-                nr = 1;
-                const double dx = k.W1 * 0.5 - fabs(pix_x - k.W1 * 0.5), dy = k.H1 * 0.5 - fabs(pix_y - k.H1 * 0.5);
-                rv[0] = (dx + dy) * (fmax(p2, 0.0) / p2) * (fmax(dx, 0.0) / dx) * (fmax(dy, 0.0) / dy);
-            }
-            const double s = rv[0] * rv[0] + rv[1] * rv[1] + rv[2] * rv[2];
-            cost += 0.5 * log1p(s);
-            const double sq = sqrt(1.0 / (1.0 + s));
-            for (int i = 0; i < 3; ++i) rv[i] *= sq;
-        }
-        s_scan[tid] = nr;
-        __syncthreads();
-        for (int o = 1; o < 256; o <<= 1) {
-            const int v = tid >= o ? s_scan[tid - o] : 0;
-            __syncthreads();
-            s_scan[tid] += v;
-            __syncthreads();
-        }
-        const int excl = s_scan[tid] - nr + s_base;
-        for (int i = 0; i < nr; ++i) out[excl + i] = rv[i];
-        __syncthreads();
-        if (tid == 255) s_base += s_scan[255];
-        __syncthreads();
-    }
-    s_cost[tid] = cost;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) s_cost[tid] += s_cost[tid + o];
-        __syncthreads();
-    }
-    if (tid == 0) { counts[f] = s_base; cost_out[f] = s_cost[0]; }
-}
-
-// ----------------------------------------------------------------------------------------------
-// Pose confidence: the normal matrix A = sum_blocks rho'(s) J^T J, the gradient g = sum rho'(s) J^T r and the cost 1/2 sum log1p(s) at GIVEN
-// parameters, by the plain per-point evaluation of residuals_kernel (no clusters, no cache, no fast reciprocal) with the analytic Jacobian
-// rows of eval_active.  Grid (F, C): workgroup (f, c) owns the points [c * INFO_CHUNK, (c + 1) * INFO_CHUNK) of frame f, thread t the points
-// c * INFO_CHUNK + t + 256 j in ascending j; the wave butterflies and the in-order sum of the four wave partials give one partial per
-// workgroup, and info_finish_kernel adds the C partials of a frame in index order.  No atomics: a frame's sums are a function of its own
-// points, labels, K and parameters alone.
-constexpr int INFO_CHUNK = 1024;                 // points per workgroup: C = ceil(N / INFO_CHUNK) depends on N only
-constexpr int INFO_STRIDE = 32;                  // fp64 words per partial: NP (NP + 1) / 2 of A | NP of g | cost | label-1 count | label-0 count
-template <int NP> struct InfoWords { static constexpr int A = 0, G = Tri<NP>::N, COST = G + NP, ACT1 = COST + 1, ACT0 = COST + 2, N = COST + 3; };
-static_assert(InfoWords<6>::N <= INFO_STRIDE && InfoWords<4>::N <= INFO_STRIDE, "a partial has INFO_STRIDE words");
-
-template <int NP>
-__global__ __launch_bounds__(256) void info_partial_kernel(const float* __restrict__ points, const int* __restrict__ labels,
-                                                           const double* __restrict__ Kmat, const double* __restrict__ params, double H,
-                                                           double W, int N, int C, double* __restrict__ partial) {
-    using IW = InfoWords<NP>;
-    __shared__ double s_part[4][INFO_STRIDE];
-    constexpr int TOFF = NP == 4 ? 1 : 3;
-    const int f = blockIdx.x, c = blockIdx.y, tid = threadIdx.x;
-    const float* px = points + (long long)f * 3 * N;
-    const int* lab = labels + (long long)f * N;
-    const double* Kf = Kmat + (long long)f * 9;
-    const Cam k{Kf[0], Kf[4], Kf[2], Kf[5], H - 1.0, W - 1.0};
-    double xr[NP];
-    for (int i = 0; i < NP; ++i) xr[i] = params[(long long)f * NP + i];
-    Rot<NP> rot;
-    make_rot<NP>(xr, rot);
-    double acc[IW::N];
-#pragma unroll
-    for (int i = 0; i < IW::N; ++i) acc[i] = 0.0;
-    const int n_end = min(N, (c + 1) * INFO_CHUNK);
-    for (int n = c * INFO_CHUNK + tid; n < n_end; n += 256) {
-        const int l = lab[n];
-        if (l != 0 && l != 1) continue;
-        const double X = (double)px[n], Y = (double)px[N + n], Z = (double)px[2 * (long long)N + n];
-        const double qx = rot.R[0] * X + rot.R[1] * Y + rot.R[2] * Z, qy = rot.R[3] * X + rot.R[4] * Y + rot.R[5] * Z,
-                     qz = rot.R[6] * X + rot.R[7] * Y + rot.R[8] * Z;
-        const double p0 = qx + xr[TOFF], p1 = qy + xr[TOFF + 1], p2 = qz + xr[TOFF + 2];
-        const double pix_x = p0 * k.fx / p2 + k.cx, pix_y = p1 * k.fy / p2 + k.cy;
-        // residual rows as value and slopes (d/dpix_x, d/dpix_y, d/dp2 direct); fmax(v, 0) keeps v and its slope at v == 0 (Ceres' Jet max)
-        double rv[3] = {0, 0, 0}, sx[3] = {0, 0, 0}, sy[3] = {0, 0, 0}, sz[3] = {0, 0, 0};
-        if (l == 1) {
-            const double a0 = -pix_x, b0 = pix_x - k.W1, a1 = -pix_y, b1 = pix_y - k.H1, a2 = -p2;
-            rv[0] = fmax(a0, 0.0) + fmax(b0, 0.0);
-            sx[0] = (a0 < 0.0 ? 0.0 : -1.0) + (b0 < 0.0 ? 0.0 : 1.0);
-            rv[1] = fmax(a1, 0.0) + fmax(b1, 0.0);
-            sy[1] = (a1 < 0.0 ? 0.0 : -1.0) + (b1 < 0.0 ? 0.0 : 1.0);
-            rv[2] = fmax(a2, 0.0) * 100.0;
-            sz[2] = a2 < 0.0 ? 0.0 : -100.0;
-        } else {
-            const double ex = pix_x - k.W1 * 0.5, ey = pix_y - k.H1 * 0.5;
-            const double dx = k.W1 * 0.5 - fabs(ex), dy = k.H1 * 0.5 - fabs(ey);
-            // the three indicators are constant where they are defined: 1 inside the frustum, 0 outside, NaN on a plane (as the functor's)
-            const double ind = (fmax(p2, 0.0) / p2) * (fmax(dx, 0.0) / dx) * (fmax(dy, 0.0) / dy);
-            rv[0] = (dx + dy) * ind;
-            sx[0] = (ex < 0.0 ? 1.0 : -1.0) * ind;
-            sy[0] = (ey < 0.0 ? 1.0 : -1.0) * ind;
-        }
-        const double s = rv[0] * rv[0] + rv[1] * rv[1] + rv[2] * rv[2];       // rows 1 and 2 of a label-0 block are 0
-        acc[IW::COST] += 0.5 * log1p(s);
-        if (s != 0.0) { acc[IW::ACT1] += l == 1 ? 1.0 : 0.0; acc[IW::ACT0] += l == 1 ? 0.0 : 1.0; }
-        const double rho1 = 1.0 / (1.0 + s);
-        // dp_i / dparam: rotation columns from dR (NP == 6) or d/dtheta of Ry(theta) X (NP == 4), then the identity of t
-        double dp0[NP], dp1[NP], dp2[NP];
-        if (NP == 4) {
-            const bool first_order = !(xr[0] * xr[0] > DBL_EPSILON);
-            dp0[0] = first_order ? Z : qz; dp1[0] = 0.0; dp2[0] = first_order ? -X : -qx;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                dp0[i] = rot.dR[i][0] * X + rot.dR[i][1] * Y + rot.dR[i][2] * Z;
-                dp1[i] = rot.dR[i][3] * X + rot.dR[i][4] * Y + rot.dR[i][5] * Z;
-                dp2[i] = rot.dR[i][6] * X + rot.dR[i][7] * Y + rot.dR[i][8] * Z;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 3; ++i) { dp0[TOFF + i] = i == 0 ? 1.0 : 0.0; dp1[TOFF + i] = i == 1 ? 1.0 : 0.0; dp2[TOFF + i] = i == 2 ? 1.0 : 0.0; }
-        const double iz = 1.0 / p2;
-        const double ax = k.fx * iz, bx = -k.fx * p0 * iz * iz;   // dpix_x = ax*dp0 + bx*dp2
-        const double ay = k.fy * iz, by = -k.fy * p1 * iz * iz;   // dpix_y = ay*dp1 + by*dp2
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            if (sx[i] == 0.0 && sy[i] == 0.0 && sz[i] == 0.0) continue;       // a constant row (NaN slopes do not compare equal: they are added)
-            double J[NP];
-#pragma unroll
-            for (int a = 0; a < NP; ++a) J[a] = sx[i] * (ax * dp0[a] + bx * dp2[a]) + sy[i] * (ay * dp1[a] + by * dp2[a]) + sz[i] * dp2[a];
-            const double wr = rho1 * rv[i];
-#pragma unroll
-            for (int a = 0; a < NP; ++a) {
-                acc[IW::G + a] += wr * J[a];
-                const double wa = rho1 * J[a];
-#pragma unroll
-                for (int b = 0; b <= a; ++b) acc[IW::A + a * (a + 1) / 2 + b] += wa * J[b];
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < IW::N; ++i) acc[i] = wave_sum(acc[i]);
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int i = 0; i < IW::N; ++i) s_part[tid >> 6][i] = acc[i];
-    }
-    __syncthreads();
-    if (tid < IW::N) partial[((long long)f * C + c) * INFO_STRIDE + tid] = ((s_part[0][tid] + s_part[1][tid]) + s_part[2][tid]) + s_part[3][tid];
-}
-
-template <int NP>
-__global__ __launch_bounds__(64) void info_finish_kernel(const double* __restrict__ partial, int C, double* __restrict__ info,
-                                                         double* __restrict__ grad, double* __restrict__ cost, int* __restrict__ active) {
-    using IW = InfoWords<NP>;
-    __shared__ double s_sum[INFO_STRIDE];
-    const int f = blockIdx.x, tid = threadIdx.x;
-    if (tid < IW::N) {
-        double v = 0.0;
-        for (int c = 0; c < C; ++c) v += partial[((long long)f * C + c) * INFO_STRIDE + tid];
-        s_sum[tid] = v;
-    }
-    __syncthreads();
-    if (tid < NP * NP) info[(long long)f * NP * NP + tid] = s_sum[IW::A + tri<NP>(tid / NP, tid % NP)];
-    if (tid < NP) grad[(long long)f * NP + tid] = s_sum[IW::G + tid];
-    if (tid == 0) cost[f] = s_sum[IW::COST];
-    if (tid < 2) active[2 * f + tid] = (int)s_sum[tid == 0 ? IW::ACT1 : IW::ACT0];
-}
-
-// params[f, best[f]] -> out[f] (a frame without a selected restart, best < 0, takes restart 0: its covariance reports status 2 anyway)
-__global__ __launch_bounds__(64) void gather_best_kernel(const double* __restrict__ params, const int* __restrict__ best, int F, int R, int np,
-                                                         double* __restrict__ out) {
-    const int i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= F * np) return;
-    const int f = i / np;
-    int b = best[f];
-    if (b < 0 || b >= R) b = 0;
-    out[i] = params[((long long)f * R + b) * np + (i - f * np)];
-}
-
-// Bounded inverse of the information matrix, one thread per frame.  A translation parameter exactly on its bound is fixed: its row and
-// column are replaced by the identity's before the Cholesky factorisation (the factor of the free block is then the factor of the free
-// sub-matrix, operation for operation: the replaced entries contribute exact zeros) and its covariance entries are written as 0.
-template <int NP>
-__global__ __launch_bounds__(64) void pose_covariance_kernel(const double* __restrict__ info, const double* __restrict__ params,
-                                                             const int* __restrict__ has_inside, Bounds bnd, int F, double* __restrict__ cov,
-                                                             int* __restrict__ free_mask, int* __restrict__ status, double* __restrict__ sigma_t,
-                                                             double* __restrict__ sigma_r) {
-    constexpr int TOFF = NP == 4 ? 1 : 3;
-    const int f = blockIdx.x * 64 + threadIdx.x;
-    if (f >= F) return;
-    double A[NP][NP], x[NP];
-    bool finite = true;
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-        x[i] = params[(long long)f * NP + i];
-        finite = finite && isfinite(x[i]);
-#pragma unroll
-        for (int j = 0; j < NP; ++j) { A[i][j] = info[((long long)f * NP + i) * NP + j]; finite = finite && isfinite(A[i][j]); }
-    }
-    int mask = 0;
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-        const int ti = i >= TOFF ? i - TOFF : 0;
-        const bool fixed = i >= TOFF && (x[i] == bnd.lb[ti] || x[i] == bnd.ub[ti]);
-        if (!fixed) mask |= 1 << i;
-    }
-    free_mask[f] = mask;
-    int st = (!finite || (has_inside && has_inside[f] == 0)) ? 2 : (mask == 0 ? 1 : 0);
-    double amax = 0.0;
-#pragma unroll
-    for (int i = 0; i < NP; ++i) if ((mask >> i) & 1) amax = fmax(amax, A[i][i]);
-    const double tiny = NP * DBL_EPSILON * amax;
-    // L: Cholesky factor of the free block (identity on the fixed parameters)
-    double L[NP][NP];
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-        const bool fi = (mask >> i) & 1;
-#pragma unroll
-        for (int j = 0; j <= i; ++j) {
-            const bool fj = (mask >> j) & 1;
-            double s = (fi && fj) ? A[i][j] : (i == j ? 1.0 : 0.0);
-#pragma unroll
-            for (int q = 0; q < j; ++q) s -= L[i][q] * L[j][q];
-            if (i == j) {
-                if (fi && !(s > tiny) && st == 0) st = 1;
-                L[i][i] = sqrt(s);
-            } else {
-                L[i][j] = s / L[j][j];
-            }
-        }
-    }
-    // M = L^-1 (lower triangular, column by column), cov = M^T M
-    double M[NP][NP];
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-#pragma unroll
-        for (int i = j; i < NP; ++i) {
-            double s = i == j ? 1.0 : 0.0;
-#pragma unroll
-            for (int q = j; q < i; ++q) s -= L[i][q] * M[q][j];
-            M[i][j] = s / L[i][i];
-        }
-    }
-    const double nan = __builtin_nan("");
-    double tr_r = 0.0, tr_t = 0.0;
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-#pragma unroll
-        for (int j = 0; j <= i; ++j) {
-            double s = 0.0;
-#pragma unroll
-            for (int q = i; q < NP; ++q) s += M[q][i] * M[q][j];
-            if (!((mask >> i) & 1) || !((mask >> j) & 1)) s = 0.0;
-            if (st != 0) s = nan;
-            cov[((long long)f * NP + i) * NP + j] = s;
-            cov[((long long)f * NP + j) * NP + i] = s;
-            if (i == j) { if (i < TOFF) tr_r += s; else tr_t += s; }
-        }
-    }
-    status[f] = st;
-    sigma_t[f] = sqrt(tr_t);
-    sigma_r[f] = sqrt(tr_r) * (180.0 / 3.14159265358979323846);
-}
-
-__device__ __forceinline__ void params_to_pose(const double* x, int np, double* P) {      // row-major 4x4, as select_best_kernel assembles it
-    double w[3] = {0, 0, 0};
-    int toff;
-    if (np == 4) { w[1] = x[0]; toff = 1; } else { w[0] = x[0]; w[1] = x[1]; w[2] = x[2]; toff = 3; }
-    double Rm[9];
-    angle_axis_to_R(w, Rm);
-    for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) P[r * 4 + c] = Rm[r * 3 + c]; P[r * 4 + 3] = x[toff + r]; }
-    P[12] = P[13] = P[14] = 0.0; P[15] = 1.0;
-}
-
-// What the other restarts say: one wave per frame, lanes stride over R.  A restart AGREES when its cost is finite and get_P_diff of
-// P_r^-1 P_best is below both tolerances (pose_diff.h, the rule of di2p_pose_errors); the gap is the cheapest disagreeing restart's cost
-// minus the best's.
-__global__ __launch_bounds__(64) void restart_consensus_kernel(const double* __restrict__ params, const double* __restrict__ cost,
-                                                               const int* __restrict__ best, const int* __restrict__ has_inside, int np, int R,
-                                                               double t_tol, double r_tol_deg, int* __restrict__ finite_out,
-                                                               int* __restrict__ agree_out, double* __restrict__ gap) {
-    const int f = blockIdx.x, lane = threadIdx.x;
-    const int b = best[f];
-    if ((has_inside && has_inside[f] == 0) || b < 0 || b >= R) {        // wave-uniform
-        if (lane == 0) { finite_out[f] = 0; agree_out[f] = 0; gap[f] = __builtin_nan(""); }
-        return;
-    }
-    double G[16], A[16];
-    params_to_pose(params + ((long long)f * R + b) * np, np, G);
-    int n_finite = 0, n_agree = 0;
-    double other = __builtin_inf();
-    for (int r = lane; r < R; r += 64) {
-        const double c = cost[(long long)f * R + r];
-        if (!isfinite(c)) continue;
-        n_finite += 1;
-        params_to_pose(params + ((long long)f * R + r) * np, np, A);
-        double t, ang;
-        di2p_pose_diff(A, G, t, ang);
-        if (t < t_tol && ang < r_tol_deg) n_agree += 1;
-        else other = fmin(other, c);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        n_finite += __shfl_xor(n_finite, o);
-        n_agree += __shfl_xor(n_agree, o);
-        other = fmin(other, __shfl_xor(other, o));
-    }
-    if (lane == 0) { finite_out[f] = n_finite; agree_out[f] = n_agree; gap[f] = other - cost[(long long)f * R + b]; }
-}
-
 static long long* g_prof = nullptr;   // diagnostics hook, see di2p_solver_set_profile_buffer
 
 constexpr size_t kStateBytes = sizeof(LMState<6>) > sizeof(LMState<4>) ? sizeof(LMState<6>) : sizeof(LMState<4>);
@@ -2152,8 +1093,6 @@ template <typename PT>
 int launch_solve(const PT* points, const int* labels, const double* K, const double* init_y, const double* init_T,
                  const double* yaw0, double H, double W, const double* lb, const double* ub, int max_iter, int is_2d, int F,
                  int R, int N, double* params, double* cost, int* iters, int* sweeps, void* workspace, hipStream_t st) {
-    Bounds b;
-    for (int i = 0; i < 3; ++i) { b.lb[i] = lb[i]; b.ub[i] = ub[i]; }
     // workspace: counts i32[F][4] | records Rec[F][N] | cluster boxes [F][NCMAX] | sort keys u64[F][P] | pending i32[F][R] | parked LM states [F][R] |
     // classification cache [F][R][NCMAX + CACHE_PAD] | normalised plane coefficients f32[F][8] | multi-workgroup preparation: partial bounds
     // f32[F][G][8], bucket counts per slice i32[F][G][2048], bucket offsets i32[F][2049], fallback flag i32[F]
@@ -2201,7 +1140,7 @@ int launch_solve(const PT* points, const int* labels, const double* K, const dou
     ka.params_out = params; ka.cost_out = cost; ka.iters_out = iters; ka.sweeps_out = sweeps; ka.prof = g_prof; ka.state_buf = state;
     ka.cache = (CacheEnt*)(base + ws.off_cache);
     ka.camf = camf;
-    ka.H = H; ka.W = W; ka.bnd = b; ka.NCMAX = ws.NCMAX; ka.nocull = nocull; ka.max_iter = max_iter; ka.F = F; ka.R = R; ka.N = N;
+    ka.H = H; ka.W = W; ka.bnd = make_bounds(lb, ub); ka.NCMAX = ws.NCMAX; ka.nocull = nocull; ka.max_iter = max_iter; ka.F = F; ka.R = R; ka.N = N;
     // the diagnostics (phase clocks, cluster / evaluation counters) are a separate instantiation: the production kernel carries none of it.
     // It exists for the first tier only and runs at <= 3 waves per SIMD: at 128 registers its timers push it into scratch and distort the phases
 #define DI2P_LAUNCH_SOLVE(NPV, MW, WP, PROFILE, PEND, BUDGET, RESUME)                                                            \
@@ -2254,96 +1193,6 @@ extern "C" int di2p_solve_batched_f32(const float* points, const int32_t* labels
                                       const double* ub_host, int max_iter, int is_2d, int F, int R, int N, double* params,
                                       double* cost, int32_t* iters, int32_t* sweeps, void* workspace, void* stream) {
     return solve_batched_entry(__func__, points, labels, K, init_y, init_T, yaw0, H, W, lb_host, ub_host, max_iter, is_2d, F, R, N, params, cost, iters, sweeps, workspace, stream);
-}
-
-extern "C" int di2p_select_best(const double* params, const double* cost, const int32_t* has_inside, int is_2d, int F, int R,
-                                int32_t* best, double* P, double* best_cost, void* stream) {
-    DI2P_CHECK_ARG(params && cost && best && P && best_cost && F >= 0 && R >= 1, "bad args");
-    if (F == 0) return 0;
-    hipLaunchKernelGGL(select_best_kernel, dim3(F), dim3(64), 0, (hipStream_t)stream, params, cost, has_inside, is_2d ? 4 : 6, R, best, P, best_cost);
-    DI2P_RETURN_LAUNCH();
-}
-
-extern "C" int di2p_initial_guess(const double* points, const int32_t* labels, double* yaw0, int32_t* labels_out,
-                                  int32_t* has_inside, int F, int N, void* stream) {
-    DI2P_CHECK_ARG(points && labels && yaw0 && labels_out && has_inside && F >= 0 && N >= 0, "bad args");
-    if (F == 0) return 0;
-    hipLaunchKernelGGL(initial_guess_kernel, dim3(F), dim3(1024), 0, (hipStream_t)stream, points, labels, yaw0, labels_out, has_inside, N);
-    DI2P_RETURN_LAUNCH();
-}
-
-extern "C" int di2p_solver_residuals(const double* points, const int32_t* labels, const double* K, const double* params, double H,
-                                     double W, int is_2d, int F, int N, double* residuals, int32_t* counts, double* cost,
-                                     void* stream) {
-    DI2P_CHECK_ARG(points && labels && K && params && residuals && counts && cost && F >= 0 && N >= 0, "bad args");
-    if (F == 0) return 0;
-    if (is_2d)
-        hipLaunchKernelGGL(residuals_kernel<4>, dim3(F), dim3(256), 0, (hipStream_t)stream, points, labels, K, params, H, W, N, residuals, counts, cost);
-    else
-        hipLaunchKernelGGL(residuals_kernel<6>, dim3(F), dim3(256), 0, (hipStream_t)stream, points, labels, K, params, H, W, N, residuals, counts, cost);
-    DI2P_RETURN_LAUNCH();
-}
-
-static int info_chunks(int N) { return N > 0 ? (N + INFO_CHUNK - 1) / INFO_CHUNK : 1; }      // (an empty cloud still launches: a grid of 0 is an error)
-
-extern "C" long long di2p_pose_information_workspace_bytes(int F, int N) {
-    if (F < 0 || N < 0) return 0;
-    return (long long)F * info_chunks(N) * INFO_STRIDE * (long long)sizeof(double);
-}
-
-extern "C" int di2p_pose_information(const float* points, const int32_t* labels, const double* K, const double* params, double H, double W,
-                                     int is_2d, int F, int N, double* info, double* grad, double* cost, int32_t* active, void* workspace,
-                                     void* stream) {
-    DI2P_CHECK_ARG(F >= 0 && N >= 0, "bad size");
-    if (F == 0) return 0;
-    DI2P_CHECK_ARG(points && labels && K && params && info && grad && cost && active && workspace, "null pointer");
-    const int C = info_chunks(N);
-    DI2P_CHECK_ARG(C <= 65535, "N too large");
-    double* partial = (double*)workspace;
-    if (is_2d) {
-        hipLaunchKernelGGL(info_partial_kernel<4>, dim3(F, C), dim3(256), 0, (hipStream_t)stream, points, labels, K, params, H, W, N, C, partial);
-        hipLaunchKernelGGL(info_finish_kernel<4>, dim3(F), dim3(64), 0, (hipStream_t)stream, (const double*)partial, C, info, grad, cost, active);
-    } else {
-        hipLaunchKernelGGL(info_partial_kernel<6>, dim3(F, C), dim3(256), 0, (hipStream_t)stream, points, labels, K, params, H, W, N, C, partial);
-        hipLaunchKernelGGL(info_finish_kernel<6>, dim3(F), dim3(64), 0, (hipStream_t)stream, (const double*)partial, C, info, grad, cost, active);
-    }
-    DI2P_RETURN_LAUNCH();
-}
-
-extern "C" int di2p_gather_best_params(const double* params, const int32_t* best, int is_2d, int F, int R, double* out, void* stream) {
-    DI2P_CHECK_ARG(F >= 0 && R >= 1, "bad size (F >= 0, R >= 1)");
-    if (F == 0) return 0;
-    DI2P_CHECK_ARG(params && best && out, "null pointer");
-    const int np = is_2d ? 4 : 6;
-    hipLaunchKernelGGL(gather_best_kernel, dim3(di2p_cdiv((long long)F * np, 64)), dim3(64), 0, (hipStream_t)stream, params, best, F, R, np, out);
-    DI2P_RETURN_LAUNCH();
-}
-
-extern "C" int di2p_pose_covariance(const double* info, const double* params, const int32_t* has_inside, const double* lb_host,
-                                    const double* ub_host, int is_2d, int F, double* cov, int32_t* free_mask, int32_t* status, double* sigma_t,
-                                    double* sigma_r, void* stream) {
-    DI2P_CHECK_ARG(F >= 0, "bad size");
-    if (F == 0) return 0;
-    DI2P_CHECK_ARG(info && params && lb_host && ub_host && cov && free_mask && status && sigma_t && sigma_r, "null pointer");
-    Bounds b;
-    for (int i = 0; i < 3; ++i) { b.lb[i] = lb_host[i]; b.ub[i] = ub_host[i]; }
-    if (is_2d)
-        hipLaunchKernelGGL(pose_covariance_kernel<4>, dim3(di2p_cdiv(F, 64)), dim3(64), 0, (hipStream_t)stream, info, params, has_inside, b, F, cov,
-                           free_mask, status, sigma_t, sigma_r);
-    else
-        hipLaunchKernelGGL(pose_covariance_kernel<6>, dim3(di2p_cdiv(F, 64)), dim3(64), 0, (hipStream_t)stream, info, params, has_inside, b, F, cov,
-                           free_mask, status, sigma_t, sigma_r);
-    DI2P_RETURN_LAUNCH();
-}
-
-extern "C" int di2p_restart_consensus(const double* params, const double* cost, const int32_t* best, const int32_t* has_inside, int is_2d,
-                                      int F, int R, double t_tol, double r_tol_deg, int32_t* finite, int32_t* agree, double* gap, void* stream) {
-    DI2P_CHECK_ARG(F >= 0 && R >= 1, "bad size (F >= 0, R >= 1)");
-    if (F == 0) return 0;
-    DI2P_CHECK_ARG(params && cost && best && finite && agree && gap, "null pointer");
-    hipLaunchKernelGGL(restart_consensus_kernel, dim3(F), dim3(64), 0, (hipStream_t)stream, params, cost, best, has_inside, is_2d ? 4 : 6, R, t_tol,
-                       r_tol_deg, finite, agree, gap);
-    DI2P_RETURN_LAUNCH();
 }
 
 extern "C" long long di2p_solve_workspace_bytes(int F, int R, int N) {

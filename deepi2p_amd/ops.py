@@ -1038,7 +1038,7 @@ def pose_information_into(points, labels, K, params, H, W, is_2d, info, grad, co
 
 
 def pose_information(points, labels, K, params, H, W, is_2d, workspace=None):
-    """The Cauchy-weighted normal matrix, gradient and cost of the registration problem at GIVEN parameters (csrc/solver.hip).
+    """The Cauchy-weighted normal matrix, gradient and cost of the registration problem at GIVEN parameters (csrc/solver_aux.hip).
     points f32[F,3,N], labels i32[F,N] (labels outside {0, 1} are skipped), K f64[F,3,3], params f64[F,np]
     -> info f64[F,np,np] = sum rho'(s) J^T J, grad f64[F,np] = sum rho'(s) J^T r, cost f64[F] = 1/2 sum log1p(s), active i32[F,2] (label-1 /
     label-0 points with a non-zero residual block).  In the solver's parameterisation; deterministic (no atomics), independent of F."""

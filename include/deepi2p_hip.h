@@ -838,7 +838,7 @@ int di2p_world_render_profiles(const double* prims, const int32_t* count, int B,
                                double reflectance_sigma, unsigned long long seed, const unsigned long long* seed_dev, int frame0, double* scan_xyr,
                                int32_t* scan_offsets, int32_t* out_count, int32_t* status, void* workspace, void* stream);
 
-/* ---- (additive, ABI 9; detect by symbol) pose confidence (csrc/solver.hip): information matrix, covariance, restart consensus ----------------------
+/* ---- (additive, ABI 9; detect by symbol) pose confidence (csrc/solver_aux.hip): information matrix, covariance, restart consensus ----------------------
  * No allocation, no synchronisation, no atomics: every entry point can be captured into a hipGraph, and a frame's outputs are bit-identical
  * from run to run and do not depend on F or on the frame's position in the batch.
  * WHAT THE NUMBERS ARE.  info, grad and cov live in the SOLVER's parameterisation ([ry, tx, ty, tz] or [angle-axis, t] of the points the

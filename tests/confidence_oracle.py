@@ -1,4 +1,4 @@
-"""Numpy fp64 references of the pose-confidence entry points (csrc/solver.hip: di2p_pose_information, di2p_pose_covariance,
+"""Numpy fp64 references of the pose-confidence entry points (csrc/solver_aux.hip: di2p_pose_information, di2p_pose_covariance,
 di2p_restart_consensus).  Helper of tests/test_confidence_host.py and tests/test_gpu_confidence.py; no tests here.
 
 The residuals and Jacobians are the oracle's (oracle/frustum_lm.cpp, dual numbers: uncorrected rows in point order); this file only groups

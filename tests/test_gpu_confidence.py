@@ -1,4 +1,4 @@
-"""GPU: pose confidence (csrc/solver.hip: di2p_pose_information, di2p_pose_covariance, di2p_restart_consensus; ops.py, the pipeline's and
+"""GPU: pose confidence (csrc/solver_aux.hip: di2p_pose_information, di2p_pose_covariance, di2p_restart_consensus; ops.py, the pipeline's and
 the executors' confidence=True) against the numpy references of tests/confidence_oracle.py.
 
 Bars.  Information matrix: |A_ab - ref| <= 1e-9 sqrt(A_aa A_bb) and |g_a - ref| <= 1e-9 sum |terms| (Cauchy-Schwarz bounds every sum of
