@@ -1,6 +1,9 @@
 """Numpy restatement of the device random draws (deepi2p_amd/csrc/rng.hip): Philox4x32-10 (Salmon et al., "Parallel random
 numbers: as easy as 1, 2, 3", SC'11; constants of the Random123 reference implementation), 53-bit uniforms in (0, 1],
-Box-Muller normals, and the key-sort random choice.
+Box-Muller normals, the key-sort random choice, and the dropout keep-mask.
+
+Streams (the fourth counter word): 0 and 1 the restart list (`draw_restarts`), 2 the random choice (`random_choice`), 3 the dropout
+keep-mask (`dropout_mask`: counter (block lo, block hi, stream_id, 3), four mask bytes per Philox block).
 
 TEST INFRASTRUCTURE ONLY (see oracle/__init__.py).  The REFERENCE draws from unseeded host Mersenne Twisters
 (evaluation/registration_lsq.py:163-164 `random.gauss / random.uniform`; data/kitti_pc_img_pose_loader.py:158-171,416-423
@@ -58,3 +61,14 @@ def random_choice(seed, stream_id, B, n_src, n_out):
         keys = (r[0] << np.uint64(32)) | n
         out[b] = (np.sort(keys)[:n_out] & np.uint64(MASK)).astype(np.int32)
     return out
+
+
+def dropout_mask(seed, stream_id, p, n):
+    """-> u8[n] exactly as di2p_dropout_mask: element i is word i % 4 of the Philox block with counter (i // 4 lo, i // 4 hi, stream_id, 3);
+    it is kept (1) iff the word, as a double, is at least float32(p) * 2^32 -- so p = 0 keeps a word that is 0."""
+    nq = (n + 3) // 4
+    q = np.arange(nq, dtype=np.uint64)
+    r = philox4x32_10(q & np.uint64(MASK), q >> np.uint64(32), np.full(nq, int(stream_id) & MASK, np.uint64), np.full(nq, 3, np.uint64),
+                      seed & MASK, (seed >> 32) & MASK)
+    v = np.stack(r, axis=1).reshape(-1)[:n].astype(np.float64)
+    return (v >= np.float64(np.float32(p)) * 4294967296.0).astype(np.uint8)

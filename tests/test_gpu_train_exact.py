@@ -9,71 +9,9 @@ import pytest
 import torch
 
 from tests import train_exact_cases as tc
+from tests.gpu_exact_harness import _Out, _Workspace, _device, _same, _twice, _untouched
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 64                        # floats of NaN before and after every output and after every workspace
-NAN_BITS = 0x7FC00000             # what torch.full(..., nan) writes
-
-
-def _untouched(t):
-    return bool((t.view(torch.int32) == NAN_BITS).all())
-
-
-class _Out:
-    """n floats of output between two guard bands, everything NaN"""
-
-    def __init__(self, n, dev):
-        self.n = int(n)
-        self.buf = torch.full((GUARD + self.n + GUARD,), tc.NAN, device=dev)
-        self.ptr = self.buf.data_ptr() + 4 * GUARD
-
-    def values(self, shape):
-        return self.buf[GUARD:GUARD + self.n].view(*shape)
-
-    def guards_untouched(self):
-        return _untouched(self.buf[:GUARD]) and _untouched(self.buf[GUARD + self.n:])
-
-
-class _Workspace(_Out):
-    """nbytes of workspace (a whole number of floats) with a guard band behind it"""
-
-    def __init__(self, nbytes, dev):
-        assert nbytes % 4 == 0 and nbytes > 0
-        super().__init__(nbytes // 4, dev)
-        self.bytes = int(nbytes)
-
-
-def _device(placed, dev):
-    """(the buffer on the device, the pointer to the operand's element (0,0,0)); fresh allocations are 256-byte aligned, which is what the
-    host test assumes when it asks the routing query which kernel a case runs on"""
-    buf = placed.buf.to(dev)
-    assert buf.data_ptr() % 256 == 0
-    return buf, buf.data_ptr() + 4 * placed.offset
-
-
-def _same(got, ref, what, explain=None):
-    got, ref = got.cpu(), ref.float()
-    idx = tc.first_mismatch(got, ref)
-    if idx is not None:
-        more = explain(idx, float(got[idx])) if explain else ""
-        raise AssertionError("%s: first differing index %s of %s: got %r, expected %r%s; %d of %d elements differ" % (
-            what, idx, tuple(ref.shape), float(got[idx]), float(ref[idx]), more, int((~(got == ref)).sum()), ref.numel()))
-    assert torch.equal(got, ref)
-
-
-def _twice(launch, out_floats, ws_bytes, dev):
-    """run `launch(out, ws)` twice on fresh NaN-filled buffers; the bits must agree, the guards must be NaN: returns the first output"""
-    runs = []
-    for _ in range(2):
-        out, ws = _Out(out_floats, dev), (_Workspace(ws_bytes, dev) if ws_bytes else None)
-        launch(out, ws)
-        torch.cuda.synchronize()
-        assert out.guards_untouched(), "the guard bands of the output were written"
-        assert ws is None or _untouched(ws.buf[GUARD + ws.n:]) and _untouched(ws.buf[:GUARD]), "the kernel wrote outside its workspace"
-        runs.append(out)
-    assert torch.equal(runs[0].buf.view(torch.int32), runs[1].buf.view(torch.int32)), "two runs of the same call differ"
-    return runs[0]
 
 
 # ------------------------------------------------------------------------------------------------ di2p_bmm_rc

@@ -2,7 +2,7 @@
 
 CPU: the restatement against the Random123 known-answer vectors of Philox4x32-10 (kat_vectors of the reference
 implementation: all-zero, all-ones and the pi-digits case), and distribution sanity.
-GPU: device == restatement bit for bit for the uniforms / choices, 1e-12 for the Box-Muller normals (device libm)."""
+GPU: device == restatement bit for bit for the uniforms / choices / dropout masks, 1e-12 for the Box-Muller normals (device libm)."""
 import math
 
 import numpy as np
@@ -81,3 +81,51 @@ def test_device_downsample_and_node_sampling(dev):
     assert nodes.shape == (2, 3, 128)
     d = (nodes[0].t().unsqueeze(1) - p2[0].t().unsqueeze(0)).abs().sum(-1).min(dim=1).values
     assert float(d.max()) == 0.0
+
+
+# The dropout keep-mask.  A Philox word that is exactly 0 (kept at p = 0: the rule is word >= p * 2^32) comes once in 2^32 draws; this seed
+# has one among its first 99457 elements on stream 5 (found by searching seeds from 2^40 upwards), so the boundary of the rule is tested.
+DROPOUT_SEED, DROPOUT_STREAMS, DROPOUT_ZERO_AT = 2**40 + 75044, (5, 0), 16528
+DROPOUT_N = (1, 2, 3, 4, 5, 1023, 1025, 99457)
+DROPOUT_P = (0.0, 0.1, 0.5, float(np.nextafter(np.float32(1.0), np.float32(0.0))))
+
+
+def test_dropout_mask_restatement_keep_rate_and_purity():
+    n = 99457
+    q = np.array([DROPOUT_ZERO_AT // 4], dtype=np.uint64)
+    words = rng_np.philox4x32_10(q, q * np.uint64(0), q * np.uint64(0) + np.uint64(5), q * np.uint64(0) + np.uint64(3),
+                                 DROPOUT_SEED & rng_np.MASK, DROPOUT_SEED >> 32)
+    assert int(words[DROPOUT_ZERO_AT % 4][0]) == 0                       # the word behind element DROPOUT_ZERO_AT is 0 ...
+    assert rng_np.dropout_mask(DROPOUT_SEED, 5, 0.0, n).all()             # ... and p = 0 keeps it, like every other element
+    assert rng_np.dropout_mask(DROPOUT_SEED, 5, float(np.float32(2.0 ** -32)), n)[DROPOUT_ZERO_AT] == 0 and \
+        rng_np.dropout_mask(DROPOUT_SEED, 5, float(np.float32(2.0 ** -32)), n).sum() == n - 1
+    for p in DROPOUT_P:
+        m = rng_np.dropout_mask(DROPOUT_SEED, 5, p, n)
+        assert m.dtype == np.uint8 and m.shape == (n,) and set(np.unique(m)) <= {0, 1}
+        keep = 1.0 - float(np.float32(p))
+        assert abs(m.mean() - keep) <= 4.0 * math.sqrt(max(keep * (1.0 - keep), 1e-7) / n)            # four standard deviations of the mean
+        assert np.array_equal(m, rng_np.dropout_mask(DROPOUT_SEED, 5, p, n))                            # a pure function of its arguments
+        for shorter in (1, 2, 3, 4, 5, 1023):                                                           # element i does not depend on n
+            assert np.array_equal(m[:shorter], rng_np.dropout_mask(DROPOUT_SEED, 5, p, shorter))
+    half = rng_np.dropout_mask(DROPOUT_SEED, 5, 0.5, n)
+    assert not np.array_equal(half, rng_np.dropout_mask(DROPOUT_SEED, 0, 0.5, n))                       # the stream id matters,
+    assert not np.array_equal(half, rng_np.dropout_mask(DROPOUT_SEED + 1, 5, 0.5, n))                   # so does the low word of the seed
+    assert not np.array_equal(half, rng_np.dropout_mask(DROPOUT_SEED + 2**32, 5, 0.5, n))               # and the high word
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", DROPOUT_N)
+def test_device_dropout_mask_matches_restatement(dev, n):
+    """di2p_dropout_mask on raw pointers, the mask between NaN guard bands (n is mostly no multiple of 4: the last Philox block is cut)"""
+    import torch
+    from deepi2p_amd import _lib
+    from tests.gpu_exact_harness import Guarded, twice
+    for stream_id in DROPOUT_STREAMS:
+        for p in DROPOUT_P:
+            def run():
+                out = Guarded(n, dev)
+                _lib.call("di2p_dropout_mask", DROPOUT_SEED, stream_id, p, n, out.ptr, _lib.stream())
+                return [out]
+            got = twice(run)[0].cpu(torch.uint8).numpy()
+            want = rng_np.dropout_mask(DROPOUT_SEED, stream_id, p, n)
+            assert np.array_equal(got, want), "stream %d p %r: first differing element %d" % (stream_id, p, int(np.nonzero(got != want)[0][0]))
