@@ -3,8 +3,9 @@
 //
 //   rc-GEMM          out[row][col] = sum_r A(r,row) * B(r,col) with BOTH operands contiguous along the reduction index r
 //                    (the shape of every "gradient with respect to a weight": reduce over points / pixels).  Lanes load along r
-//                    (coalesced dwords), the tile is transposed on its way into LDS ([r][row] panels, row pitch 65: the 32 lanes
+//                    (coalesced dwords), the tile is transposed on its way into LDS ([r][row] panels, row pitch tile + 1: the 32 lanes
 //                    of a store group hit 32 different banks) and feeds v_mfma_f32_32x32x2_f32 exactly like the forward engine.
+//                    One tile body (rc_gemm_tile) at 64 x 64, and at 128 x 128 for the big plainly strided pairs.
 //                    The reduction is cut into chunks (one workgroup each, partial tiles in scratch) that a second kernel adds in
 //                    chunk order: deterministic, no float atomics.  Instances:
 //                      * d W of a 1x1 layer            A = dY[b][m][n],  B = X[b][k][n]                (nn.Conv1d / MyConv2d)
@@ -15,8 +16,9 @@
 //                      * attention: d feat               A = dOut[b][c][m], B = score[b][hw][m]
 //   km-GEMM          out[row][col] = sum_k A[k][row] * B[k][col] per batch (attention: d score)
 //   conv dgrad       d X as an implicit GEMM over (co, ky, kx) with the stride folded into the loader
-//   BatchNorm        batch statistics in fp64 partial sums (two kernels), normalise + affine (+ residual) (+ ReLU) fused;
-//                    backward = one reduction pass (sum g, sum g*xhat) + one elementwise pass
+//   BatchNorm        two launches per direction: a reduction into fp64 partial pairs (sum x, sum x^2 / sum g, sum g*xhat), then one kernel
+//                    that adds the pairs per channel and streams normalise + affine (+ residual) (+ ReLU) / dx (knob bn_unfused: that
+//                    second kernel as a finalize and an elementwise launch, the same device functions, the same bits)
 //   arg-max routers  segment max (index_max), max over neighbours / nodes, 3x3/2 max-pool: gradient goes to the saved / recomputed
 //                    arg-max (first maximum in scan order, the rule of torch.max / max_pool2d)
 #include "common.h"
@@ -26,14 +28,18 @@
 namespace {
 
 // =============================================================================================== rc-GEMM
-constexpr int RC_BK = 32, RC_BM = 64, RC_LD = 65, RC_PASSES = 8;
-constexpr int RC_LDS_FLOATS = 2 * 2 * RC_BK * RC_LD;
+constexpr int RC_BK = 32, RC_BM = 64, RC2_BM = 128, RC_PASSES = 8;
+// a tile's [r][row] panels: row pitch BM + 1, A and B, double-buffered (128: 66048 bytes, a dynamic-LDS opt-in)
+constexpr int rc_lds_floats(int bm) { return 2 * 2 * RC_BK * (bm + 1); }
+// k-pairs whose operands a wave reads from LDS before it issues their matrix instructions: all 16 of a K-step at 64 (32 operand registers
+// for one accumulator tile), four at a time at 128 (16 operand registers beside 2 x 2 accumulator tiles)
+constexpr int rc_kbatch(int bm) { return bm == RC_BM ? RC_BK / 2 : 4; }
 
 // Loader protocol: set_index(p, i) once per pass p (row / column i of the output tile, may be out of range), set_r(r, ok)
 // once per K-step (this lane's reduction index; !ok = past the end), load(p) -> value (0 where out of range).
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// Scalar stager of one operand: lane = (reduction index r_in, 8 rows per pass); any loader.
+// Scalar stager of one operand of a 64-wide tile: lane = (reduction index r_in, 8 rows per pass); any loader.
 template <class L>
 struct RcStageScalar {
     float v[RC_PASSES];
@@ -52,22 +58,24 @@ struct RcStageScalar {
     }
     __device__ __forceinline__ void store(float* S) const {
 #pragma unroll
-        for (int p = 0; p < RC_PASSES; ++p) S[r_in * RC_LD + q0 + 8 * p] = v[p];
+        for (int p = 0; p < RC_PASSES; ++p) S[r_in * (RC_BM + 1) + q0 + 8 * p] = v[p];
     }
 };
 
 // 16-byte stager for an operand that is plainly strided (value(r, i) = base[i*ld + r]) with 16-byte addressable rows and a
-// reduction range that is a multiple of 4: lane = (4 consecutive r, 32 rows per pass): 2 loads instead of 8 per K-step.
+// reduction range that is a multiple of 4: lane = (4 consecutive r, 32 rows per pass): BM / 32 loads instead of 8 per K-step.
+template <int BM>
 struct RcStageVec {
-    f32x4 v[2];
-    const float* ptr[2];
-    bool okp[2];
+    static constexpr int P = BM / 32;
+    f32x4 v[P];
+    const float* ptr[P];
+    bool okp[P];
     int r4, row0;
     template <class L>
     __device__ __forceinline__ void init(int tid, L& l, int blk) {
         r4 = tid & 7; row0 = tid >> 3;
 #pragma unroll
-        for (int p = 0; p < 2; ++p) {
+        for (int p = 0; p < P; ++p) {
             const int i = blk + row0 + 32 * p;
             okp[p] = i < l.n;
             ptr[p] = l.p + (long long)min(i, l.n - 1) * l.ld + r4 * 4;
@@ -78,33 +86,40 @@ struct RcStageVec {
         const bool ok = r0 + r4 * 4 < r_end;
         const int rc = ok ? r0 : r_end - 32;           // (a clamped, still in-range 16-byte read; zeroed below)
 #pragma unroll
-        for (int p = 0; p < 2; ++p) {
+        for (int p = 0; p < P; ++p) {
             const f32x4 t = *reinterpret_cast<const f32x4*>(ptr[p] + (rc < 0 ? 0 : rc));
             v[p] = (ok && okp[p]) ? t : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
         }
     }
     __device__ __forceinline__ void store(float* S) const {
 #pragma unroll
-        for (int p = 0; p < 2; ++p)
+        for (int p = 0; p < P; ++p)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) S[(r4 * 4 + i) * RC_LD + row0 + 32 * p] = v[p][i];
+            for (int i = 0; i < 4; ++i) S[(r4 * 4 + i) * (BM + 1) + row0 + 32 * p] = v[p][i];
     }
 };
 
-template <bool AV, bool BV, class LA, class LB>
+// One BM x BM output tile over the reduction range [r_begin, r_end): four waves, 2 x 2, each WT x WT matrix tiles (WT = BM / 64).
+template <int BM, bool AV, bool BV, class LA, class LB>
 __device__ __forceinline__ void rc_gemm_tile(float* lds, LA& la, LB& lb, int r_begin, int r_end, int row_blk, int col_blk,
                                              float* __restrict__ out, int rows, int cols) {
+    static_assert(BM == RC_BM || (BM == RC2_BM && AV && BV), "the scalar stagers fill 64-wide panels");
+    constexpr int LD = BM + 1, WT = BM / 64, KB = rc_kbatch(BM);
     float* As = lds;                          // [2][BK][LD]
-    float* Bs = lds + 2 * RC_BK * RC_LD;
+    float* Bs = lds + 2 * RC_BK * LD;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, half = lane >> 5;
-    typename std::conditional<AV, RcStageVec, RcStageScalar<LA>>::type sa;
-    typename std::conditional<BV, RcStageVec, RcStageScalar<LB>>::type sb;
+    typename std::conditional<AV, RcStageVec<BM>, RcStageScalar<LA>>::type sa;
+    typename std::conditional<BV, RcStageVec<BM>, RcStageScalar<LB>>::type sb;
     sa.init(tid, la, row_blk);
     sb.init(tid, lb, col_blk);
-    f32x16 acc;
+    f32x16 acc[WT][WT];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+    for (int i = 0; i < WT; ++i)
+#pragma unroll
+        for (int j = 0; j < WT; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
     const int T = (r_end - r_begin + RC_BK - 1) / RC_BK;
     if (T > 0) {
         sa.load(la, r_begin, r_end); sb.load(lb, r_begin, r_end);
@@ -114,24 +129,40 @@ __device__ __forceinline__ void rc_gemm_tile(float* lds, LA& la, LB& lb, int r_b
     for (int t = 0; t < T; ++t) {
         const int buf = t & 1;
         if (t + 1 < T) { sa.load(la, r_begin + (t + 1) * RC_BK, r_end); sb.load(lb, r_begin + (t + 1) * RC_BK, r_end); }
-        const float* Ab = As + buf * RC_BK * RC_LD + wm * 32 + l31;
-        const float* Bb = Bs + buf * RC_BK * RC_LD + wn * 32 + l31;
-        float a[RC_BK / 2], b[RC_BK / 2];
+        const float* Ab = As + buf * RC_BK * LD + wm * 32 * WT + l31;
+        const float* Bb = Bs + buf * RC_BK * LD + wn * 32 * WT + l31;
 #pragma unroll
-        for (int kk = 0; kk < RC_BK; kk += 2) { a[kk / 2] = Ab[(kk + half) * RC_LD]; b[kk / 2] = Bb[(kk + half) * RC_LD]; }
+        for (int k0 = 0; k0 < RC_BK; k0 += 2 * KB) {
+            float a[KB][WT], b[KB][WT];
 #pragma unroll
-        for (int kk = 0; kk < RC_BK / 2; ++kk) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kk], b[kk], acc, 0, 0, 0);
-        if (t + 1 < T) { sa.store(As + (buf ^ 1) * RC_BK * RC_LD); sb.store(Bs + (buf ^ 1) * RC_BK * RC_LD); }
+            for (int kk = 0; kk < KB; ++kk)
+#pragma unroll
+                for (int i = 0; i < WT; ++i) {
+                    a[kk][i] = Ab[(k0 + 2 * kk + half) * LD + i * 32];
+                    b[kk][i] = Bb[(k0 + 2 * kk + half) * LD + i * 32];
+                }
+#pragma unroll
+            for (int kk = 0; kk < KB; ++kk)
+#pragma unroll
+                for (int i = 0; i < WT; ++i)
+#pragma unroll
+                    for (int j = 0; j < WT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kk][i], b[kk][j], acc[i][j], 0, 0, 0);
+        }
+        if (t + 1 < T) { sa.store(As + (buf ^ 1) * RC_BK * LD); sb.store(Bs + (buf ^ 1) * RC_BK * LD); }
         __syncthreads();
     }
-    const int col = col_blk + wn * 32 + l31;
-    if (col < cols) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = row_blk + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-            if (row < rows) out[(long long)row * cols + col] = acc[r];
+    for (int i = 0; i < WT; ++i)
+#pragma unroll
+        for (int j = 0; j < WT; ++j) {
+            const int col = col_blk + wn * 32 * WT + j * 32 + l31;
+            if (col >= cols) continue;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = row_blk + wm * 32 * WT + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                if (row < rows) out[(long long)row * cols + col] = acc[i][j][r];
+            }
         }
-    }
 }
 
 // value(r, i) = p[i * ld + r], i < n
@@ -200,116 +231,17 @@ struct RcSelect {
     }
 };
 
-template <bool AV, bool BV, class LA, class LB>
+// BM = 128 (a wave: 64 x 64 = 2 x 2 matrix tiles) serves the plainly strided operand pair with 16-byte rows -- the weight gradients of the big
+// point layers.  Those launches are bound by operand traffic (every 64 x 64 tile re-reads its 64 + 64 rows over the whole reduction range:
+// dW of the per-point head's first layer, 256 x 736 over 8 x 20480 columns, moved 4 GB for 62 Gflop: 0.86 ms); a 128 x 128 tile reads half of
+// that per output element.  Same reduction order per output element for the same chunks.
+template <int BM, bool AV, bool BV, class LA, class LB>
 __global__ __launch_bounds__(256) void rc_gemm_kernel(LA la, LB lb, int R, int rch, int chunks, float* __restrict__ partial, int rows, int cols) {
     extern __shared__ float lds[];
     const int z = blockIdx.z / chunks, ch = blockIdx.z % chunks;
     la.batch(z); lb.batch(z);
     const int r_begin = ch * rch, r_end = min(R, r_begin + rch);
-    rc_gemm_tile<AV, BV>(lds, la, lb, r_begin, r_end, blockIdx.y * RC_BM, blockIdx.x * RC_BM, partial + (long long)blockIdx.z * rows * cols, rows, cols);
-}
-
-// 128 x 128 tiles (a wave: 64 x 64 = 2 x 2 matrix tiles) for the plainly strided operand pair with 16-byte rows -- the weight gradients of the
-// big point layers.  Those launches are bound by operand traffic (every 64 x 64 tile re-reads its 64 + 64 rows over the whole reduction range:
-// dW of the per-point head's first layer, 256 x 736 over 8 x 20480 columns, moved 4 GB for 62 Gflop: 0.86 ms); a 128 x 128 tile reads half of
-// that per output element.  Same reduction order per output element for the same chunks.
-constexpr int RC2_BM = 128, RC2_LD = 129;
-constexpr int RC2_LDS_FLOATS = 2 * 2 * RC_BK * RC2_LD;
-struct RcStageVec4 {
-    f32x4 v[4];
-    const float* ptr[4];
-    bool okp[4];
-    int r4, row0;
-    template <class L>
-    __device__ __forceinline__ void init(int tid, L& l, int blk) {
-        r4 = tid & 7; row0 = tid >> 3;
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const int i = blk + row0 + 32 * p;
-            okp[p] = i < l.n;
-            ptr[p] = l.p + (long long)min(i, l.n - 1) * l.ld + r4 * 4;
-        }
-    }
-    __device__ __forceinline__ void load(int r0, int r_end) {
-        const bool ok = r0 + r4 * 4 < r_end;
-        const int rc = ok ? r0 : r_end - 32;           // (a clamped, still in-range 16-byte read; zeroed below)
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const f32x4 t = *reinterpret_cast<const f32x4*>(ptr[p] + (rc < 0 ? 0 : rc));
-            v[p] = (ok && okp[p]) ? t : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        }
-    }
-    __device__ __forceinline__ void store(float* S) const {
-#pragma unroll
-        for (int p = 0; p < 4; ++p)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) S[(r4 * 4 + i) * RC2_LD + row0 + 32 * p] = v[p][i];
-    }
-};
-__global__ __launch_bounds__(256) void rc_gemm128_kernel(RcStrided la, RcStrided lb, int R, int rch, int chunks, float* __restrict__ partial, int rows, int cols) {
-    extern __shared__ float lds[];
-    const int z = blockIdx.z / chunks, ch = blockIdx.z % chunks;
-    la.batch(z); lb.batch(z);
-    const int r_begin = ch * rch, r_end = min(R, r_begin + rch);
-    float* out = partial + (long long)blockIdx.z * rows * cols;
-    const int row_blk = blockIdx.y * RC2_BM, col_blk = blockIdx.x * RC2_BM;
-    float* As = lds;                          // [2][BK][LD]
-    float* Bs = lds + 2 * RC_BK * RC2_LD;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, half = lane >> 5;
-    RcStageVec4 sa, sb;
-    sa.init(tid, la, row_blk);
-    sb.init(tid, lb, col_blk);
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-    const int T = (r_end - r_begin + RC_BK - 1) / RC_BK;
-    if (T > 0) {
-        sa.load(r_begin, r_end); sb.load(r_begin, r_end);
-        sa.store(As); sb.store(Bs);
-    }
-    __syncthreads();
-    for (int t = 0; t < T; ++t) {
-        const int buf = t & 1;
-        if (t + 1 < T) { sa.load(r_begin + (t + 1) * RC_BK, r_end); sb.load(r_begin + (t + 1) * RC_BK, r_end); }
-        const float* Ab = As + buf * RC_BK * RC2_LD + wm * 64 + l31;
-        const float* Bb = Bs + buf * RC_BK * RC2_LD + wn * 64 + l31;
-#pragma unroll
-        for (int k0 = 0; k0 < RC_BK; k0 += 8) {          // four k-pairs at a time: 16 operand registers
-            float a[4][2], b[4][2];
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    a[kk][i] = Ab[(k0 + 2 * kk + half) * RC2_LD + i * 32];
-                    b[kk][i] = Bb[(k0 + 2 * kk + half) * RC2_LD + i * 32];
-                }
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kk][i], b[kk][j], acc[i][j], 0, 0, 0);
-        }
-        if (t + 1 < T) { sa.store(As + (buf ^ 1) * RC_BK * RC2_LD); sb.store(Bs + (buf ^ 1) * RC_BK * RC2_LD); }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int col = col_blk + wn * 64 + j * 32 + l31;
-            if (col >= cols) continue;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = row_blk + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                if (row < rows) out[(long long)row * cols + col] = acc[i][j][r];
-            }
-        }
+    rc_gemm_tile<BM, AV, BV>(lds, la, lb, r_begin, r_end, blockIdx.y * BM, blockIdx.x * BM, partial + (long long)blockIdx.z * rows * cols, rows, cols);
 }
 
 // out[g][e] = alpha * sum_{p < per_group} partial[g * per_group + p][e], in a fixed order
@@ -335,7 +267,7 @@ __global__ __launch_bounds__(256) void rc_reduce_kernel(const float* __restrict_
 }
 
 struct RcPlan { int rch, chunks; long long bytes; };
-// the big strided pairs take 128 x 128 tiles (rc_gemm128_kernel)
+// the big strided pairs take 128 x 128 tiles (rc_gemm_kernel<128, true, true>)
 inline bool rc_big(int rows, int cols) { return rows >= 128 && cols >= 128 && !di2p_opt(DI2P_OPT_RC_TILE64); }
 RcPlan rc_plan(int Z, int rows, int cols, int R, int bm = RC_BM) {
     RcPlan pl;
@@ -375,25 +307,27 @@ int rc_launch(const char* who, LA la, LB lb, int Z, int rows, int cols, int R, f
     constexpr bool a_strided = std::is_same<LA, RcStrided>::value, b_strided = std::is_same<LB, RcStrided>::value;
     constexpr int kind = a_strided && b_strided ? RC_KIND_STRIDED : a_strided && std::is_same<LB, RcIm2col>::value ? RC_KIND_WGRAD : RC_KIND_GATHER;
     const RcRoute rt = rc_route(kind, Z, rows, cols, R, a_vec, b_vec);
-    const bool big = rt.tile == RC2_BM;
     const RcPlan pl = rt.pl;
-    a_vec = rt.a_vec; b_vec = rt.b_vec;
     if (!ws || ws_bytes < pl.bytes) { di2p_set_error("%s: workspace too small (%lld bytes needed)", who, pl.bytes); return -1; }
     if ((long long)Z * pl.chunks > 65535) { di2p_set_error("%s: too many reduction chunks", who); return -1; }
-    const dim3 grid(di2p_cdiv(cols, big ? RC2_BM : RC_BM), di2p_cdiv(rows, big ? RC2_BM : RC_BM), Z * pl.chunks);
-    const size_t lds = RC_LDS_FLOATS * sizeof(float);
-    if constexpr (std::is_same<LA, RcStrided>::value && std::is_same<LB, RcStrided>::value) {
-        if (big) {
-            if (di2p_allow_dynamic_lds((const void*)rc_gemm128_kernel, RC2_LDS_FLOATS * sizeof(float), who)) return -1;
-            hipLaunchKernelGGL(rc_gemm128_kernel, grid, dim3(256), RC2_LDS_FLOATS * sizeof(float), st, la, lb, R, pl.rch, pl.chunks, (float*)ws, rows, cols);
-        } else if (a_vec && b_vec) hipLaunchKernelGGL((rc_gemm_kernel<true, true, LA, LB>), grid, dim3(256), lds, st, la, lb, R, pl.rch, pl.chunks, (float*)ws, rows, cols);
-        else hipLaunchKernelGGL((rc_gemm_kernel<false, false, LA, LB>), grid, dim3(256), lds, st, la, lb, R, pl.rch, pl.chunks, (float*)ws, rows, cols);
-    } else if constexpr (std::is_same<LA, RcStrided>::value) {
-        if (a_vec) hipLaunchKernelGGL((rc_gemm_kernel<true, false, LA, LB>), grid, dim3(256), lds, st, la, lb, R, pl.rch, pl.chunks, (float*)ws, rows, cols);
-        else hipLaunchKernelGGL((rc_gemm_kernel<false, false, LA, LB>), grid, dim3(256), lds, st, la, lb, R, pl.rch, pl.chunks, (float*)ws, rows, cols);
-    } else {
-        hipLaunchKernelGGL((rc_gemm_kernel<false, false, LA, LB>), grid, dim3(256), lds, st, la, lb, R, pl.rch, pl.chunks, (float*)ws, rows, cols);
-    }
+    const dim3 grid(di2p_cdiv(cols, rt.tile), di2p_cdiv(rows, rt.tile), Z * pl.chunks);
+    auto launch = [&](auto bm, auto av, auto bv) {          // the instance <BM, AV, BV> of this loader pair
+        constexpr int BM = decltype(bm)::value;
+        const auto kernel = rc_gemm_kernel<BM, decltype(av)::value, decltype(bv)::value, LA, LB>;
+        constexpr size_t lds = rc_lds_floats(BM) * sizeof(float);
+        if (lds > 64 * 1024 && di2p_allow_dynamic_lds((const void*)kernel, lds, who)) return -1;
+        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, la, lb, R, pl.rch, pl.chunks, (float*)ws, rows, cols);
+        return 0;
+    };
+    constexpr std::integral_constant<int, RC_BM> bm64{};
+    constexpr std::integral_constant<int, RC2_BM> bm128{};
+    constexpr std::true_type vec{};
+    constexpr std::false_type scalar{};
+    int refused = 0;
+    if constexpr (kind == RC_KIND_STRIDED) refused = rt.tile == RC2_BM ? launch(bm128, vec, vec) : rt.a_vec ? launch(bm64, vec, vec) : launch(bm64, scalar, scalar);
+    else if constexpr (kind == RC_KIND_WGRAD) refused = rt.a_vec ? launch(bm64, vec, scalar) : launch(bm64, scalar, scalar);
+    else refused = launch(bm64, scalar, scalar);
+    if (refused) return -1;
     const long long elems = (long long)rows * cols;
     const int per_group = reduce_z ? Z * pl.chunks : pl.chunks;
     const long long total = reduce_z ? elems : elems * Z;
@@ -535,6 +469,50 @@ __global__ __launch_bounds__(KmCfg::THREADS) void conv_dgrad_s2_kernel(const flo
 }
 
 // =============================================================================================== per-channel reductions (BatchNorm, bias)
+// The BatchNorm arithmetic, each formula once: the unfused kernels (knob bn_unfused) and the fused ones inline the same expressions, so
+// they give the same bits by construction.
+// element i of the backward: g = dy * [y > 0 if relu], xhat = (x - mean) * invstd
+__device__ __forceinline__ void bn_g_xhat(const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ y, long long i, int relu,
+                                          float mean, float invstd, float& g, float& xh) {
+    g = dy[i];
+    if (relu && !(y[i] > 0.0f)) g = 0.0f;
+    xh = (x[i] - mean) * invstd;
+}
+// dx = gamma * invstd * (g - mean(g) - xhat * mean(g*xhat))
+__device__ __forceinline__ float bn_dx(float gamma, float invstd, float g, float xh, float mean_g, float mean_gxh) {
+    return gamma * invstd * (g - mean_g - xh * mean_gxh);
+}
+// element i of the forward: normalise + affine (+ residual) (+ ReLU)
+__device__ __forceinline__ float bn_y(const float* __restrict__ x, const float* __restrict__ res, long long i, int relu, float mean, float invstd, float gamma,
+                                      float beta) {
+    float v = (x[i] - mean) * invstd * gamma + beta;
+    if (res) v += res[i];
+    if (relu) v = fmaxf(v, 0.0f);
+    return v;
+}
+// channel c's S fp64 partial pairs added on one thread in the order q = 0 .. S - 1
+__device__ __forceinline__ void channel_sum_partials(const double* __restrict__ partial, int c, int S, double& a0, double& a1) {
+    a0 = 0.0; a1 = 0.0;
+    for (int q = 0; q < S; ++q) { a0 += partial[((long long)c * S + q) * 2]; a1 += partial[((long long)c * S + q) * 2 + 1]; }
+}
+// (sum x, sum x^2) -> fp32 mean and invstd of the batch; write: also stores them and updates the running statistics (unbiased variance,
+// torch.nn.BatchNorm semantics)
+__device__ __forceinline__ void bn_statistics(double a0, double a1, double count, float eps, float momentum, int c, bool write, float* __restrict__ save_mean,
+                                              float* __restrict__ save_invstd, float* __restrict__ run_mean, float* __restrict__ run_var, float& fm, float& fi) {
+    const double mu = a0 / count;
+    double var = a1 / count - mu * mu;
+    if (var < 0.0) var = 0.0;
+    fm = (float)mu; fi = (float)(1.0 / sqrt(var + (double)eps));
+    if (!write) return;
+    save_mean[c] = fm;
+    save_invstd[c] = fi;
+    if (run_mean) {
+        const double unb = count > 1.0 ? var * count / (count - 1.0) : var;
+        run_mean[c] = (float)((1.0 - momentum) * run_mean[c] + momentum * mu);
+        run_var[c] = (float)((1.0 - momentum) * run_var[c] + momentum * unb);
+    }
+}
+
 // x[B][C][N]; grid (C, B * SN): block (c, s) reduces n in [chunk*per, ...) of row (b, c); fp64 partial pairs
 template <int MODE>   // 0: (sum x, sum x^2)   1: (sum g, sum g*xhat) with g = dy * [y > 0 if relu]
 __global__ __launch_bounds__(256) void channel_reduce_kernel(const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ y,
@@ -552,9 +530,8 @@ __global__ __launch_bounds__(256) void channel_reduce_kernel(const float* __rest
             const double v = x[row + n];
             a0 += v; a1 += v * v;
         } else {
-            float g = dy[row + n];
-            if (relu && !(y[row + n] > 0.0f)) g = 0.0f;
-            const float xh = (x[row + n] - mu) * is;
+            float g, xh;
+            bn_g_xhat(x, dy, y, row + n, relu, mu, is, g, xh);
             a0 += g; a1 += (double)g * xh;
         }
     }
@@ -578,19 +555,11 @@ __global__ __launch_bounds__(64) void channel_finalize_kernel(const double* __re
                                                               float* __restrict__ run_var, float* __restrict__ sums) {
     const int c = blockIdx.x * 64 + threadIdx.x;
     if (c >= C) return;
-    double a0 = 0.0, a1 = 0.0;
-    for (int s = 0; s < S; ++s) { a0 += partial[((long long)c * S + s) * 2]; a1 += partial[((long long)c * S + s) * 2 + 1]; }
+    double a0, a1;
+    channel_sum_partials(partial, c, S, a0, a1);
     if (MODE == 0) {
-        const double mu = a0 / count;
-        double var = a1 / count - mu * mu;
-        if (var < 0.0) var = 0.0;
-        out0[c] = (float)mu;
-        out1[c] = (float)(1.0 / sqrt(var + (double)eps));
-        if (run_mean) {
-            const double unb = count > 1.0 ? var * count / (count - 1.0) : var;
-            run_mean[c] = (float)((1.0 - momentum) * run_mean[c] + momentum * mu);
-            run_var[c] = (float)((1.0 - momentum) * run_var[c] + momentum * unb);
-        }
+        float fm, fi;
+        bn_statistics(a0, a1, count, eps, momentum, c, true, out0, out1, run_mean, run_var, fm, fi);
     } else if (MODE == 1) {
         out0[c] = (float)a1;          // dgamma
         out1[c] = (float)a0;          // dbeta
@@ -607,10 +576,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
     const int c = (int)((i / N) % C);
-    float v = (x[i] - mean[c]) * invstd[c] * gamma[c] + beta[c];
-    if (res) v += res[i];
-    if (relu) v = fmaxf(v, 0.0f);
-    y[i] = v;
+    y[i] = bn_y(x, res, i, relu, mean[c], invstd[c], gamma[c], beta[c]);
 }
 
 // dx = gamma * invstd * (g - mean(g) - xhat * mean(g*xhat)),  dres = g
@@ -621,10 +587,9 @@ __global__ __launch_bounds__(256) void bn_backward_apply_kernel(const float* __r
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
     const int c = (int)((i / N) % C);
-    float g = dy[i];
-    if (relu && !(y[i] > 0.0f)) g = 0.0f;
-    const float xh = (x[i] - mean[c]) * invstd[c];
-    dx[i] = gamma[c] * invstd[c] * (g - sums[2 * c] - xh * sums[2 * c + 1]);
+    float g, xh;
+    bn_g_xhat(x, dy, y, i, relu, mean[c], invstd[c], g, xh);
+    dx[i] = bn_dx(gamma[c], invstd[c], g, xh, sums[2 * c], sums[2 * c + 1]);
     if (dres) dres[i] = g;
 }
 
@@ -640,33 +605,17 @@ __global__ __launch_bounds__(256) void bn_finalize_apply_kernel(const float* __r
     __shared__ float s_stat[2];
     const int c = blockIdx.x, s = blockIdx.y, b = s / SN, ch = s - b * SN;
     if (threadIdx.x == 0) {
-        double a0 = 0.0, a1 = 0.0;
-        for (int q = 0; q < S; ++q) { a0 += partial[((long long)c * S + q) * 2]; a1 += partial[((long long)c * S + q) * 2 + 1]; }
-        const double mu = a0 / count;
-        double var = a1 / count - mu * mu;
-        if (var < 0.0) var = 0.0;
-        const float fm = (float)mu, fi = (float)(1.0 / sqrt(var + (double)eps));
+        double a0, a1;
+        channel_sum_partials(partial, c, S, a0, a1);
+        float fm, fi;
+        bn_statistics(a0, a1, count, eps, momentum, c, s == 0, save_mean, save_invstd, run_mean, run_var, fm, fi);
         s_stat[0] = fm; s_stat[1] = fi;
-        if (s == 0) {
-            save_mean[c] = fm;
-            save_invstd[c] = fi;
-            if (run_mean) {
-                const double unb = count > 1.0 ? var * count / (count - 1.0) : var;
-                run_mean[c] = (float)((1.0 - momentum) * run_mean[c] + momentum * mu);
-                run_var[c] = (float)((1.0 - momentum) * run_var[c] + momentum * unb);
-            }
-        }
     }
     __syncthreads();
     const float mean = s_stat[0], invstd = s_stat[1], g = gamma[c], be = beta[c];
     const long long row = ((long long)b * C + c) * N;
     const int n0 = ch * per, n1 = min(N, n0 + per);
-    for (int n = n0 + threadIdx.x; n < n1; n += 256) {
-        float v = (x[row + n] - mean) * invstd * g + be;
-        if (res) v += res[row + n];
-        if (relu) v = fmaxf(v, 0.0f);
-        y[row + n] = v;
-    }
+    for (int n = n0 + threadIdx.x; n < n1; n += 256) y[row + n] = bn_y(x, res, row + n, relu, mean, invstd, g, be);
 }
 
 __global__ __launch_bounds__(256) void bn_finalize_backward_kernel(const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ y,
@@ -677,8 +626,8 @@ __global__ __launch_bounds__(256) void bn_finalize_backward_kernel(const float* 
     __shared__ float s_sum[2];
     const int c = blockIdx.x, s = blockIdx.y, b = s / SN, ch = s - b * SN;
     if (threadIdx.x == 0) {
-        double a0 = 0.0, a1 = 0.0;
-        for (int q = 0; q < S; ++q) { a0 += partial[((long long)c * S + q) * 2]; a1 += partial[((long long)c * S + q) * 2 + 1]; }
+        double a0, a1;
+        channel_sum_partials(partial, c, S, a0, a1);
         s_sum[0] = (float)(a0 / count);
         s_sum[1] = (float)(a1 / count);
         if (s == 0) { dgamma[c] = (float)a1; dbeta[c] = (float)a0; }
@@ -688,10 +637,9 @@ __global__ __launch_bounds__(256) void bn_finalize_backward_kernel(const float* 
     const long long row = ((long long)b * C + c) * N;
     const int n0 = ch * per, n1 = min(N, n0 + per);
     for (int n = n0 + threadIdx.x; n < n1; n += 256) {
-        float g = dy[row + n];
-        if (relu && !(y[row + n] > 0.0f)) g = 0.0f;
-        const float xh = (x[row + n] - mean) * invstd;
-        dx[row + n] = gm * invstd * (g - m0 - xh * m1);
+        float g, xh;
+        bn_g_xhat(x, dy, y, row + n, relu, mean, invstd, g, xh);
+        dx[row + n] = bn_dx(gm, invstd, g, xh, m0, m1);
         if (dres) dres[row + n] = g;
     }
 }
@@ -712,6 +660,31 @@ RedPlan red_plan(int B, int C, int N) {
 // scan order (max_pool2d keeps `val > maxval`).  GATHER form: one thread per INPUT pixel visits the <= 4 windows that cover it
 // (oy in {ceil((iy-1)/2) .. floor((iy+1)/2)}, likewise ox), recomputes each window's first arg-max and adds the gradients of the
 // windows it wins in a fixed (oy, ox) order -- deterministic, no float atomics, no memset of dx.
+// first maximum of window (oy, ox) as the linear index iy * W + ix; src holds the plane's rows from row y_org on (global memory: 0)
+__device__ __forceinline__ int maxpool_first_argmax(const float* __restrict__ src, int y_org, int pitch, int oy, int ox, int H, int W) {
+    float best = 0.0f;
+    int arg = -1;
+    for (int ky = 0; ky < 3; ++ky) {
+        const int yy = oy * 2 - 1 + ky;
+        if (yy < 0 || yy >= H) continue;
+        for (int kx = 0; kx < 3; ++kx) {
+            const int xx = ox * 2 - 1 + kx;
+            if (xx < 0 || xx >= W) continue;
+            const float v = src[(yy - y_org) * pitch + xx];
+            if (arg < 0 || v > best) { best = v; arg = yy * W + xx; }
+        }
+    }
+    return arg;
+}
+// gradient of input pixel (iy, ix): the gradients of the windows it won, added in (oy, ox) order; argmax_of(oy, ox) -> that window's first maximum
+template <class F>
+__device__ __forceinline__ float maxpool_winner_sum(const float* __restrict__ dyp, int iy, int ix, int W, int OH, int OW, F argmax_of) {
+    float g = 0.0f;
+    for (int oy = max(iy / 2, 0); oy <= min((iy + 1) / 2, OH - 1); ++oy)          // windows with oy*2-1 <= iy <= oy*2+1
+        for (int ox = max(ix / 2, 0); ox <= min((ix + 1) / 2, OW - 1); ++ox)
+            if (argmax_of(oy, ox) == iy * W + ix) g += dyp[oy * OW + ox];
+    return g;
+}
 __global__ __launch_bounds__(256) void maxpool_backward_kernel(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ dx, int H, int W,
                                                                int OH, int OW, long long total) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -720,25 +693,7 @@ __global__ __launch_bounds__(256) void maxpool_backward_kernel(const float* __re
     const long long plane = i / ((long long)W * H);
     const float* xp = x + plane * H * W;
     const float* dyp = dy + plane * OH * OW;
-    float g = 0.0f;
-    for (int oy = max(iy / 2, 0); oy <= min((iy + 1) / 2, OH - 1); ++oy) {          // windows with oy*2-1 <= iy <= oy*2+1
-        for (int ox = max(ix / 2, 0); ox <= min((ix + 1) / 2, OW - 1); ++ox) {
-            float best = 0.0f;
-            int arg = -1;
-            for (int ky = 0; ky < 3; ++ky) {
-                const int yy = oy * 2 - 1 + ky;
-                if (yy < 0 || yy >= H) continue;
-                for (int kx = 0; kx < 3; ++kx) {
-                    const int xx = ox * 2 - 1 + kx;
-                    if (xx < 0 || xx >= W) continue;
-                    const float v = xp[yy * W + xx];
-                    if (arg < 0 || v > best) { best = v; arg = yy * W + xx; }
-                }
-            }
-            if (arg == iy * W + ix) g += dyp[oy * OW + ox];
-        }
-    }
-    dx[i] = g;
+    dx[i] = maxpool_winner_sum(dyp, iy, ix, W, OH, OW, [&](int oy, int ox) { return maxpool_first_argmax(xp, 0, W, oy, ox, H, W); });
 }
 
 // The same gradient with the windows' arg-maxima computed ONCE: a workgroup owns MPB_R output rows of one plane -- it stages the 2 R + 3 input
@@ -763,31 +718,13 @@ __global__ __launch_bounds__(256) void maxpool_backward_lds_kernel(const float* 
     __syncthreads();
     for (int i = threadIdx.x; i < (MPB_R + 1) * OW; i += 256) {
         const int wr = i / OW, oy = oy0 + wr, ox = i - wr * OW;
-        float best = 0.0f;
-        int a = -1;
-        if (oy < OH) {
-            for (int ky = 0; ky < 3; ++ky) {
-                const int yy = oy * 2 - 1 + ky;
-                if (yy < 0 || yy >= H) continue;
-                for (int kx = 0; kx < 3; ++kx) {
-                    const int xx = ox * 2 - 1 + kx;
-                    if (xx < 0 || xx >= W) continue;
-                    const float v = xs[(yy - y_lo) * W + xx];
-                    if (a < 0 || v > best) { best = v; a = yy * W + xx; }
-                }
-            }
-        }
-        arg[i] = a;
+        arg[i] = oy < OH ? maxpool_first_argmax(xs, y_lo, W, oy, ox, H, W) : -1;
     }
     __syncthreads();
     for (int i = threadIdx.x; i < 2 * MPB_R * W; i += 256) {
         const int r = i / W, iy = 2 * oy0 + r, ix = i - r * W;
         if (iy >= H) break;
-        float g = 0.0f;
-        for (int oy = max(iy / 2, 0); oy <= min((iy + 1) / 2, OH - 1); ++oy)
-            for (int ox = max(ix / 2, 0); ox <= min((ix + 1) / 2, OW - 1); ++ox)
-                if (arg[(oy - oy0) * OW + ox] == iy * W + ix) g += dyp[oy * OW + ox];
-        dx[plane * H * W + iy * W + ix] = g;
+        dx[plane * H * W + iy * W + ix] = maxpool_winner_sum(dyp, iy, ix, W, OH, OW, [&](int oy, int ox) { return arg[(oy - oy0) * OW + ox]; });
     }
 }
 
@@ -829,16 +766,26 @@ __global__ __launch_bounds__(256) void apply_mask_kernel(const float* __restrict
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i < n) y[i] = mask[i] ? x[i] * scale : 0.0f;
 }
+// four lanes: byte k of m selects a[k] * scale or 0
+__device__ __forceinline__ float4 mask_select4(float4 a, unsigned m, float scale) {
+    return make_float4((m & 0xffu) ? a.x * scale : 0.0f, (m & 0xff00u) ? a.y * scale : 0.0f, (m & 0xff0000u) ? a.z * scale : 0.0f,
+                       (m & 0xff000000u) ? a.w * scale : 0.0f);
+}
 // eight elements per thread (two 16-byte loads, one 8-byte mask load, two 16-byte stores); n % 8 == 0, 16-byte aligned x / y, 8-byte aligned mask
 __global__ __launch_bounds__(256) void apply_mask8_kernel(const float4* __restrict__ x, const uint2* __restrict__ mask, float scale, float4* __restrict__ y, long long n8) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n8) return;
     const float4 a = x[2 * i], b = x[2 * i + 1];
     const uint2 m = mask[i];
-    y[2 * i] = make_float4((m.x & 0xffu) ? a.x * scale : 0.0f, (m.x & 0xff00u) ? a.y * scale : 0.0f, (m.x & 0xff0000u) ? a.z * scale : 0.0f,
-                           (m.x & 0xff000000u) ? a.w * scale : 0.0f);
-    y[2 * i + 1] = make_float4((m.y & 0xffu) ? b.x * scale : 0.0f, (m.y & 0xff00u) ? b.y * scale : 0.0f, (m.y & 0xff0000u) ? b.z * scale : 0.0f,
-                               (m.y & 0xff000000u) ? b.w * scale : 0.0f);
+    y[2 * i] = mask_select4(a, m.x, scale);
+    y[2 * i + 1] = mask_select4(b, m.y, scale);
+}
+
+// output size of a convolution; false where the filter does not fit or the output is empty (the division truncates toward zero: a filter
+// that does not fit gives 1 at stride > 1, hence the explicit check)
+inline bool conv_out_dims(int H, int W, int KH, int KW, int stride, int pad, int& OH, int& OW) {
+    OH = (H + 2 * pad - KH) / stride + 1; OW = (W + 2 * pad - KW) / stride + 1;
+    return H + 2 * pad >= KH && W + 2 * pad >= KW && OH >= 1 && OW >= 1;
 }
 
 }  // namespace
@@ -911,7 +858,7 @@ extern "C" int di2p_channel_sum(const float* x, float* out, int B, int C, int N,
 
 extern "C" long long di2p_bmm_rc_workspace_bytes(int Z, int rows, int cols, int R) {
     if (Z < 1 || rows < 1 || cols < 1 || R < 1) return 0;
-    const long long b64 = rc_plan(Z, rows, cols, R).bytes, b128 = rc_plan(Z, rows, cols, R, RC2_BM).bytes;      // (whichever kernel the call takes)
+    const long long b64 = rc_plan(Z, rows, cols, R).bytes, b128 = rc_plan(Z, rows, cols, R, RC2_BM).bytes;      // (whichever tile the call takes)
     return b64 > b128 ? b64 : b128;
 }
 
@@ -961,16 +908,16 @@ extern "C" int di2p_gather_backward(const float* dy, const int32_t* idx, const f
 
 extern "C" long long di2p_conv2d_wgrad_workspace_bytes(int B, int Cin, int H, int W, int Cout, int KH, int KW, int stride, int pad) {
     if (B < 1 || Cin < 1 || Cout < 1 || KH < 1 || KW < 1 || stride < 1) return 0;
-    const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
-    if (H + 2 * pad < KH || W + 2 * pad < KW || OH < 1 || OW < 1) return 0;
+    int OH, OW;
+    if (!conv_out_dims(H, W, KH, KW, stride, pad, OH, OW)) return 0;
     return rc_plan(B, Cout, Cin * KH * KW, OH * OW).bytes;
 }
 
 extern "C" int di2p_conv2d_wgrad(const float* x, const float* dy, float* dW, int B, int Cin, int H, int W, int Cout, int KH, int KW, int stride, int pad,
                                  void* workspace, long long workspace_bytes, void* stream) {
     DI2P_CHECK_ARG(x && dy && dW && B >= 1 && Cin >= 1 && Cout >= 1 && KH >= 1 && KW >= 1 && stride >= 1 && pad >= 0, "bad args");
-    const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
-    DI2P_CHECK_ARG(H + 2 * pad >= KH && W + 2 * pad >= KW && OH >= 1 && OW >= 1, "empty output");          // (the division truncates toward zero: a filter that does not fit gives 1 at stride > 1)
+    int OH, OW;
+    DI2P_CHECK_ARG(conv_out_dims(H, W, KH, KW, stride, pad, OH, OW), "empty output");
     RcStrided la{}; la.base = dy; la.ld = (long long)OH * OW; la.batch_stride = (long long)Cout * OH * OW; la.n = Cout;
     RcIm2col lb{}; lb.base = x; lb.Cin = Cin; lb.H = H; lb.W = W; lb.OW = OW; lb.KH = KH; lb.KW = KW; lb.stride = stride; lb.pad = pad; lb.ncols = Cin * KH * KW;
     return rc_launch(__func__, la, lb, B, Cout, Cin * KH * KW, OH * OW, 1.0f, true, dW, workspace, workspace_bytes, (hipStream_t)stream,
@@ -980,8 +927,8 @@ extern "C" int di2p_conv2d_wgrad(const float* x, const float* dy, float* dW, int
 extern "C" int di2p_conv2d_dgrad(const float* dy, const float* Wgt, float* dx, int B, int Cin, int H, int W, int Cout, int KH, int KW, int stride, int pad,
                                  void* stream) {
     DI2P_CHECK_ARG(dy && Wgt && dx && B >= 1 && B <= 65535 && Cin >= 1 && Cout >= 1 && KH >= 1 && KW >= 1 && stride >= 1 && pad >= 0, "bad args");
-    const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
-    DI2P_CHECK_ARG(H + 2 * pad >= KH && W + 2 * pad >= KW && OH >= 1 && OW >= 1, "empty output");          // (the division truncates toward zero: a filter that does not fit gives 1 at stride > 1)
+    int OH, OW;
+    DI2P_CHECK_ARG(conv_out_dims(H, W, KH, KW, stride, pad, OH, OW), "empty output");
     if (stride == 2 && B <= 16383 && !di2p_opt(DI2P_OPT_CONV_DGRAD_DENSE)) {          // one parity class of input pixels per workgroup: 1/4 of the matrix work
         const int ncol = ((H + 1) / 2) * ((W + 1) / 2);
         hipLaunchKernelGGL(conv_dgrad_s2_kernel, dim3(di2p_cdiv(ncol, KmCfg::BN), di2p_cdiv(Cin, KmCfg::BM), B * 4), dim3(KmCfg::THREADS),

@@ -28,8 +28,8 @@ def rc_route_of(c, case):
 
 def instance_of(rt):
     if rt["tile"] == 128:
-        return "rc_gemm128_kernel"
-    return "rc_gemm_kernel<%s,%s>" % ("true" if rt["a_stager"] else "false", "true" if rt["b_stager"] else "false")
+        return "rc_gemm_kernel<128,true,true>"
+    return "rc_gemm_kernel<64,%s,%s>" % ("true" if rt["a_stager"] else "false", "true" if rt["b_stager"] else "false")
 
 
 def _bounded(absum, what):
@@ -119,7 +119,7 @@ def test_rc_table_reaches_every_instance_and_plan_edge():
             both = [ops.rc_route("strided", c.Z, c.rows, c.cols, c.R, v, v) for v in (False, True)]
         assert lib.di2p_bmm_rc_workspace_bytes(c.Z, c.rows, c.cols, c.R) == max(c.Z * r["chunks"] * c.rows * c.cols * 4 for r in both), c
     print("di2p_bmm_rc cases per kernel instance:", dict(seen))
-    assert set(seen) == {"rc_gemm_kernel<false,false>", "rc_gemm_kernel<true,true>", "rc_gemm128_kernel"}
+    assert set(seen) == {"rc_gemm_kernel<64,false,false>", "rc_gemm_kernel<64,true,true>", "rc_gemm_kernel<128,true,true>"}
     for fam in ("S", "IDA", "IDB"):
         assert per_family[fam] == set(seen), fam
     assert per_group >= {1, 7, 8, 9, 17} and last >= {1, 4, 34}
@@ -215,7 +215,7 @@ def test_wgrad_table_reaches_every_instance_and_edge():
         assert lib.di2p_conv2d_wgrad_workspace_bytes(1, 3, 9, 2, 5, 3, 3, stride, 0) == 0
     assert lib.di2p_conv2d_wgrad_workspace_bytes(1, 3, 3, 3, 5, 3, 3, 2, 0) == 5 * 27 * 4
     print("di2p_conv2d_wgrad cases per kernel instance:", dict(seen))
-    assert set(seen) == {"rc_gemm_kernel<false,false>", "rc_gemm_kernel<true,false>"}
+    assert set(seen) == {"rc_gemm_kernel<64,false,false>", "rc_gemm_kernel<64,true,false>"}
     assert spatial >= {1, 31, 32, 35, 36, 576} and chunks == {1, 2}
     for side in (lambda c: c.Cout, lambda c: c.Cin * c.KH * c.KW):
         assert any(side(c) < 64 for c in cs) and any(side(c) > 64 for c in cs) and any(side(c) in (63, 64, 65) for c in cs)
@@ -291,7 +291,7 @@ def test_gather_table_reaches_every_edge():
         seen[instance_of(rt)] += 1
         assert lib.di2p_gather_backward_workspace_bytes(c.B, c.C, c.J, c.M) == c.B * rt["chunks"] * c.C * c.M * 4, c
     print("di2p_gather_backward cases per kernel instance:", dict(seen))
-    assert set(seen) == {"rc_gemm_kernel<false,false>"}
+    assert set(seen) == {"rc_gemm_kernel<64,false,false>"}
 
 
 @pytest.mark.parametrize("c", tc.GATHER_CASES, ids=tc.gather_id)

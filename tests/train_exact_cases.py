@@ -148,7 +148,7 @@ def _rc_table():
                                   (4352, 1, 1, 1.0), (772, 3, 1, 0.25), (2050, 3, 1, 1.0), (2308, 3, 1, -3.0), (1800, 1, 1, 1.0)):
         add("S", Z, 5, 65, R, reduce_z, alpha)
     # layouts, on each operand alone and on both: at a 64-tile shape and at a 128-tile shape (where a layout that keeps 16-byte rows stays on
-    # rc_gemm128_kernel and any other falls to the scalar stagers)
+    # rc_gemm_kernel<128,true,true> and any other falls to the scalar stagers)
     for lay in ("ld4", "ld1", "off1", "bs4", "bs1", "ld4bs4"):
         for la, lb in ((lay, "c"), ("c", lay), (lay, lay)):
             add("S", 3, 65, 63, 516, 0, 1.0, la, lb)
