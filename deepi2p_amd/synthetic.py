@@ -486,3 +486,41 @@ def make_camera_image(rng, H0=370, W0=1226):
     g = rng.integers(0, 256, (ph, pw)).astype(np.uint8)          # a textured but exactly grey patch: S = 0 pixels next to each other
     img[H0 // 2:H0 // 2 + ph, W0 // 3:W0 // 3 + pw] = g[: img[H0 // 2:H0 // 2 + ph].shape[0], : img[:, W0 // 3:W0 // 3 + pw].shape[1], None]
     return img
+
+
+def make_map(rng, n, length=300.0, half_width=8.0, bend=12.0, boxes=6, poses=16, camera_height=1.6):
+    """A street-like LiDAR map in camera convention (x right, y DOWN, z forward; up_axis=1 for map_index.MapIndex.build), host only and
+    deterministic for a given rng: ground, two walls and a few boxes along a gently curved path of `length` metres (its centre line is
+    x = bend sin(pi z / length), z in [0, length]).  The rows are in SCAN ORDER, profile after profile along the path, 64 points per profile
+    across it, as a push-broom traversal lays a map down.
+    -> dict(points f32[n,4] rows (x, y, z, intensity), poses f64[poses,4,4] map <- camera at even steps along the path: the camera
+    `camera_height` above the ground, looking along the path's tangent, s f64[poses] their arc parameter z)"""
+    per = 64
+    profiles = -(-n // per)
+    centre = lambda z: bend * np.sin(np.pi * z / length)
+    slope = lambda z: bend * np.pi / length * np.cos(np.pi * z / length)          # dx / dz of the centre line
+    z0 = np.repeat(np.linspace(0.0, length, profiles), per)[:n]
+    a = np.tile(np.linspace(-1.35, 1.35, per), profiles)[:n]                      # the beam's angle across the path
+    road = np.abs(a) < 1.2
+    lateral = np.where(road, camera_height * np.tan(a), np.sign(a) * half_width)
+    y = np.where(road, camera_height, camera_height - (np.abs(a) - 1.2) * 30.0)  # y down: the walls rise towards negative y
+    inten = np.where(road, 0.3, 0.6)
+    # boxes: stretches of the path where one side's returns stop 3 m short of the wall, on the face of a 2 m high box
+    starts = rng.uniform(0.05 * length, 0.9 * length, boxes)
+    sides = rng.integers(0, 2, boxes) * 2 - 1
+    for s0, side in zip(starts, sides):
+        hit = (z0 >= s0) & (z0 < s0 + 4.0) & (np.sign(a) == side) & (np.abs(lateral) > half_width - 3.0)
+        lateral = np.where(hit, side * (half_width - 3.0), lateral)
+        y = np.where(hit, camera_height - 2.0 * rng.uniform(0.0, 1.0, n), y)
+        inten = np.where(hit, 0.85, inten)
+    x = centre(z0) + lateral + rng.normal(0.0, 0.02, n)
+    z = z0 + rng.normal(0.0, 0.01, n)
+    y = y + rng.normal(0.0, 0.02, n)
+    inten = np.clip(inten + rng.normal(0.0, 0.05, n), 0.0, 1.0)
+    points = np.stack([x, y, z, inten], axis=1).astype(np.float32)
+    s = np.linspace(0.1 * length, 0.9 * length, poses)
+    T = np.tile(np.eye(4), (poses, 1, 1))
+    for k, zk in enumerate(s):
+        T[k, :3, :3] = ry_matrix(math.atan2(slope(zk), 1.0))                             # camera z along the tangent (dx/dz, 0, 1)
+        T[k, :3, 3] = (centre(zk), 0.0, zk)
+    return dict(points=points, poses=T, s=s)

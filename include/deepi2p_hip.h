@@ -878,6 +878,38 @@ int di2p_pose_covariance(const double* info, const double* params, const int32_t
 int di2p_restart_consensus(const double* params, const double* cost, const int32_t* best, const int32_t* has_inside, int is_2d, int F, int R,
                            double t_tol, double r_tol_deg, int32_t* finite, int32_t* agree, double* gap, void* stream);
 
+/* ---- (additive, ABI 9; detect by symbol) map localisation (csrc/map_index.hip): cell index, prior crops, camera pose in the map -------------------
+ * The map is points f32[M,4] rows (x, y, z, intensity) in a map frame; the caller keeps its coordinates small enough for float32 (relative to
+ *   a map origin of its own).  up_axis in {0, 1, 2} names the vertical axis, the ground axes (a, b) are the other two in ascending order
+ *   (camera-convention maps, y down: up_axis 1, ground plane x-z; z-up maps: up_axis 2).  The grid: origin (origin0, origin1) on (a, b), cell
+ *   metres (> 0), nx x ny cells, nx ny <= 2^24; M <= 2^27.  All index arithmetic is fp64, every operation rounded once, no fused multiply-add.
+ * di2p_map_index_build, eager, once per map; refuses (returns -1, nothing enqueued, the capture stays usable) while `stream` is capturing.
+ *   Cell of a row: ix = floor(((double)p[a] - origin0) / cell), iy likewise on b, id = iy nx + ix.  -> cell_start i32[nx ny + 1]; order i32[M]
+ *   the map row of every stored row; sorted f32[M,4] the rows cell after cell in ascending id, inside a cell in ascending map row (a stable
+ *   sort); status i32[1]: 0, or 1 when a coordinate is not finite or a row falls outside the grid (the arrays are then unspecified).
+ *   workspace: di2p_map_index_workspace_bytes(M, nx ny) bytes (0 for bad sizes), 256-byte aligned.
+ * di2p_map_crop, five launches, no allocation, no synchronisation, no memset node, no atomics: T_map_prior f64[B,4,4] (map <- prior frame),
+ *   radius f64[B] (both device memory, read inside the launches).  Frame b: centre c = (T[a][3], T[b][3]); window
+ *   ix0 = max(0, floor(((c0 - r) - origin0) / cell)), ix1 = min(nx - 1, floor(((c0 + r) - origin0) / cell)), iy0 and iy1 likewise; window
+ *   cells are visited iy-major (iy ascending outside, ix ascending inside), the rows of a cell in stored order.  A row is kept iff
+ *   dx dx + dy dy < r r (strict) with dx = (double)p[a] - c0, dy = (double)p[b] - c1, and written in the prior frame: with
+ *   d_k = (double)p[k] - T[k][3], q_i = (float)((T[0][i] d0 + T[1][i] d1) + T[2][i] d2); the intensity bit for bit.
+ *   -> rows f32[cap,4], offsets i32[B+1], index i32[cap] (may be NULL) the map row of every kept row.  Rows past offsets[B] are not written.
+ *   status i32[B] (may be NULL): 0 ok; 1 more than max_frame_points (<= 2^20) kept rows, rows that would pass cap, or a window of more than
+ *     max_cells cells; 4 no kept row (also a disc that misses the grid); 5 a non-finite entry of the prior, or a radius that is not finite and
+ *     positive.  A frame with a status has no rows (offsets[b+1] = offsets[b]) and leaves every other frame's rows as they are without it.
+ *   workspace: di2p_map_crop_workspace_bytes(B, max_cells) bytes (0 for bad sizes; B max_cells <= 2^28), 256-byte aligned.
+ * di2p_map_pose: T_map_cam[b] = T_map_prior[b] . P_scan[b]^-1 for n row-major f64 4x4 matrices, the inverse as the rigid [R^T | -R^T t]
+ *   (P_scan's last row is not read), the product as di2p_compose_poses writes it; T_map_cam may be one of the inputs. */
+long long di2p_map_index_workspace_bytes(int M, int ncell);
+long long di2p_map_crop_workspace_bytes(int B, int max_cells);
+int di2p_map_index_build(const float* points, int M, int up_axis, double origin0, double origin1, double cell, int nx, int ny,
+                         int32_t* cell_start, int32_t* order, float* sorted, int32_t* status, void* workspace, void* stream);
+int di2p_map_crop(const float* sorted, const int32_t* cell_start, const int32_t* order, int M, int up_axis, double origin0, double origin1,
+                  double cell, int nx, int ny, const double* T_map_prior, const double* radius, int B, int cap, int max_frame_points,
+                  int max_cells, float* rows, int32_t* offsets, int32_t* index, int32_t* status, void* workspace, void* stream);
+int di2p_map_pose(const double* T_map_prior, const double* P_scan, int n, double* T_map_cam, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
