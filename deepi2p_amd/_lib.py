@@ -184,6 +184,8 @@ _SIGS = {
     "di2p_map_index_build": [c_void_p, c_int, c_int, c_double, c_double, c_double, c_int, c_int] + [c_void_p] * 6,
     "di2p_map_crop": [c_void_p] * 3 + [c_int, c_int, c_double, c_double, c_double, c_int, c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 6,
     "di2p_map_pose": [c_void_p, c_void_p, c_int, c_void_p, c_void_p],
+    "di2p_map_normals": [c_void_p, c_int, c_int, c_int, c_double, c_int] + [c_void_p] * 6,
+    "di2p_map_crop_normals": [c_void_p] * 4 + [c_int, c_int, c_void_p, c_void_p],
 }
 _WS_SIGS = {        # <name>_workspace_bytes helpers returning long long
     "di2p_channel_reduce_workspace_bytes": [c_int] * 3,
@@ -208,6 +210,7 @@ _WS_SIGS = {        # <name>_workspace_bytes helpers returning long long
     "di2p_pose_information_workspace_bytes": [c_int, c_int],
     "di2p_map_index_workspace_bytes": [c_int, c_int],
     "di2p_map_crop_workspace_bytes": [c_int, c_int],
+    "di2p_map_normals_workspace_bytes": [c_int],
 }
 EXPORTS = sorted(list(_SIGS) + ["di2p_last_error", "di2p_version", "di2p_solve_workspace_bytes", "di2p_solver_set_profile_buffer", "di2p_pnp_workspace_bytes",
                  "di2p_conv2d_workspace_bytes", "di2p_set_option", "di2p_get_option", "di2p_random_choice_workspace_bytes", "di2p_classifier_loss_workspace_bytes", "di2p_normals_cells_candidates"] + list(_WS_SIGS))

@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libdeepi2p_hip.so")
-SOURCES = ["common.cpp", "index_max.hip", "ball_query.hip", "point_ops.hip", "gemm.hip", "conv.hip", "solver.hip", "solver_aux.hip", "prep.hip", "pnp.hip", "rng.hip", "loss.hip", "train.hip", "winograd.hip", "stem.hip", "conv_x3.hip", "head_x3.hip", "stem_x3.hip", "head_labels_x3.hip", "scan_prep.hip", "sample_prep.hip", "eval.hip", "vis.hip", "submap.hip", "sweeps.hip", "world.hip", "map_index.hip"]
+SOURCES = ["common.cpp", "index_max.hip", "ball_query.hip", "point_ops.hip", "gemm.hip", "conv.hip", "solver.hip", "solver_aux.hip", "prep.hip", "pnp.hip", "rng.hip", "loss.hip", "train.hip", "winograd.hip", "stem.hip", "conv_x3.hip", "head_x3.hip", "stem_x3.hip", "head_labels_x3.hip", "scan_prep.hip", "sample_prep.hip", "eval.hip", "vis.hip", "submap.hip", "sweeps.hip", "world.hip", "map_index.hip", "map_normals.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc"] + os.environ.get("DI2P_EXTRA_HIPCC_FLAGS", "").split()
 # hipcc's SLP vectoriser turns adjacent scalar fp32 adds / multiplies (epilogues, the Winograd transforms, the solver's fp32
@@ -43,7 +43,9 @@ PER_FILE_FLAGS = {"solver.hip": SOLVER_FLAGS,
                   # world.hip: the trace, the shading and the scan rows are compared with numpy bit for bit
                   "world.hip": ["-ffp-contract=off"],
                   # map_index.hip: the cell of a row, the window, the keep rule and the row transform are compared with numpy bit for bit
-                  "map_index.hip": ["-ffp-contract=off"]}
+                  "map_index.hip": ["-ffp-contract=off"],
+                  # map_normals.hip: shares its selection and PCA tail (normals_nn.h) with scan_prep.hip and must give the same bits
+                  "map_normals.hip": ["-ffp-contract=off"]}
 
 
 def _stale(out, deps):

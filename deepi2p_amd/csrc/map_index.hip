@@ -4,6 +4,8 @@
 //   di2p_map_index_build   once per map, eager: cell of every row -> stable radix sort (rocPRIM) -> cell_start, order, sorted
 //   di2p_map_crop          per batch, graph-safe: frame -> window cells -> rows, the count / prefix / write split of submap.hip and sweeps.hip on
 //                          ragged2.h (wave_prefix, offsets_kernel, the status codes, the workspace helpers)
+//   di2p_map_crop_normals  per batch, graph-safe, behind the crop: the map's normals (map_normals.hip, or the user's own) of the kept rows,
+//                          rotated into the prior frame; a second launch, so di2p_map_crop and its outputs are what they were
 //   di2p_map_pose          T_map_cam = T_map_prior . P_scan^-1
 //
 // The map is f32[M,4] rows (x, y, z, intensity) in a map frame whose coordinates are small enough for float32 (relative to a map origin the
@@ -262,6 +264,22 @@ __global__ __launch_bounds__(64 * WAVES) void write_kernel(const float* __restri
     }
 }
 
+// The normals of the kept rows in the prior frame: R^T n, write_kernel's row formula without the translation.  One thread per kept row; the
+// frame of a row by binary search in the offsets the crop left, so the launch reads everything that varies from device memory.
+__global__ __launch_bounds__(256) void crop_normals_kernel(const float* __restrict__ normals, const int* __restrict__ index,
+                                                           const int* __restrict__ offsets, const double* __restrict__ T, int B, int cap,
+                                                           float* __restrict__ out) {
+    const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (k >= min(offsets[B], cap)) return;
+    const int b = frame_of(offsets, B, k);
+    const double* P = T + 16 * (long long)b;
+    const long long row = max(index[k], 0);
+    const double n0 = (double)normals[3 * row + 0], n1 = (double)normals[3 * row + 1], n2 = (double)normals[3 * row + 2];
+    out[3 * k + 0] = (float)((P[0] * n0 + P[4] * n1) + P[8] * n2);
+    out[3 * k + 1] = (float)((P[1] * n0 + P[5] * n1) + P[9] * n2);
+    out[3 * k + 2] = (float)((P[2] * n0 + P[6] * n1) + P[10] * n2);
+}
+
 // ---------------------------------------------------------------------------------------------------------------- pose
 // out = A . inv(Pm) with the rigid inverse [R^T | -R^T t] of Pm (its last row is not read); the product as di2p_compose_poses writes it
 __global__ __launch_bounds__(64) void map_pose_kernel(const double* A, const double* Pm, double* out, int n) {          // no __restrict__: out may be A or Pm
@@ -368,6 +386,17 @@ extern "C" int di2p_map_crop(const float* sorted, const int32_t* cell_start, con
     if (up_axis == 0) launch_crop<0>(sorted, cell_start, order, M, g, T_map_prior, radius, B, cap, max_frame_points, max_cells, rows, offsets, index, status, workspace, st);
     else if (up_axis == 1) launch_crop<1>(sorted, cell_start, order, M, g, T_map_prior, radius, B, cap, max_frame_points, max_cells, rows, offsets, index, status, workspace, st);
     else launch_crop<2>(sorted, cell_start, order, M, g, T_map_prior, radius, B, cap, max_frame_points, max_cells, rows, offsets, index, status, workspace, st);
+    DI2P_RETURN_LAUNCH();
+}
+
+extern "C" int di2p_map_crop_normals(const float* normals, const int32_t* index, const int32_t* offsets, const double* T_map_prior, int B, int cap,
+                                     float* out, void* stream) {
+    DI2P_CHECK_ARG(B >= 0 && cap >= 0, "bad sizes (B, cap >= 0)");
+    DI2P_CHECK_ARG(B == 0 || cap == 0 || (normals && index && offsets && T_map_prior && out), "null pointer");
+    DI2P_CHECK_ARG(((uintptr_t)T_map_prior & 7) == 0, "T_map_prior must be 8-byte aligned");
+    if (B == 0 || cap == 0) return 0;
+    hipLaunchKernelGGL(crop_normals_kernel, dim3(di2p_cdiv(cap, 256)), dim3(256), 0, (hipStream_t)stream, normals, index, offsets, T_map_prior, B, cap,
+                       out);
     DI2P_RETURN_LAUNCH();
 }
 

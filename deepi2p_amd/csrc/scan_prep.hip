@@ -13,6 +13,7 @@
 // Sorting: rocPRIM's stable device radix sort, temporary storage from the workspace.  Stability makes the summation order (ascending
 // input index inside a voxel) and therefore the bits reproducible.
 #include "common.h"
+#include "normals_nn.h"
 #include "philox.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -20,24 +21,12 @@
 
 namespace {
 
-constexpr int AXIS_BITS = 21;
-constexpr int AXIS_MAX = (1 << AXIS_BITS) - 1;
 constexpr int MAX_FRAME_POINTS = 1 << 20;
 constexpr unsigned long long PAD_KEY = (1ull << 63) - 1;
-constexpr int NN_MAX = 64;
 constexpr int NN_CAP = 1024;          // LDS candidate buffer of one query (entries); compacted to the best max_nn when full
 constexpr int CELL_WAVES = 4;          // normals_cells_kernel: waves of a workgroup, each on a query of its own
 constexpr int CELL_CAND = 960;         // ... candidate capacity of a cell in LDS (entries: fp64 position + frame-local index, 28 B)
-constexpr int CELL_NN_CAP = 256;       // ... LDS candidate list of one wave (entries); compacted like the per-query kernel's
 constexpr int ST_OK = 0, ST_TOO_MANY = 1, ST_SPAN = 2, ST_OFFSETS = 3;
-
-__device__ __forceinline__ unsigned long long compose_key(long long ix, long long iy, long long iz) {
-    return ((unsigned long long)ix << (2 * AXIS_BITS)) | ((unsigned long long)iy << AXIS_BITS) | (unsigned long long)iz;
-}
-
-__device__ __forceinline__ long long clamp_axis(double f) {
-    return f < 0.0 ? 0 : (f > (double)AXIS_MAX ? AXIS_MAX : (long long)f);
-}
 
 // largest b in [0, B) with off[b] <= i (off non-decreasing)
 __device__ __forceinline__ int frame_of(const int* __restrict__ off, int B, long long i) {
@@ -47,11 +36,6 @@ __device__ __forceinline__ int frame_of(const int* __restrict__ off, int B, long
         if ((long long)off[mid] <= i) lo = mid; else hi = mid - 1;
     }
     return lo;
-}
-
-__device__ __forceinline__ double d2_of(double ax, double ay, double az, double bx, double by, double bz) {
-    const double dx = ax - bx, dy = ay - by, dz = az - bz;
-    return __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
 }
 
 // ---------------------------------------------------------------- workspace layout
@@ -275,122 +259,15 @@ __global__ __launch_bounds__(256) void cell_positions_kernel(const double* __res
     for (int c = 0; c < 3; ++c) cpos[3 * (long long)j + c] = cen[3 * v + c];
 }
 
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x = __dadd_rn(x, __shfl_xor(x, o, 64));
-    return x;
-}
-
-// (d2 bits, index) lexicographic order; d2 >= 0 so the bit pattern orders like the value
-__device__ __forceinline__ bool nn_less(unsigned long long da, int ia, unsigned long long db, int ib) {
-    return da < db || (da == db && ia < ib);
-}
-
-// Barrier between the LDS accesses of the lanes that share a candidate list: the workgroup's when it is one wave (normals_kernel), else
-// a wave-level one (normals_cells_kernel: the waves of a workgroup work on different queries and never meet inside one).  A wave's LDS
-// instructions execute in order; the fences keep the compiler from moving or merging accesses across the point.
-template <bool kWave> __device__ __forceinline__ void nn_sync() {
-    if (kWave) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    } else {
-        __syncthreads();
+// normal_from_list's positions (normals_nn.h): list entry i is centroid fs + i of the frame, already fp64
+struct CentroidPos {
+    const double* __restrict__ cen;
+    int fs;
+    __device__ __forceinline__ void operator()(int i, double& x, double& y, double& z) const {
+        const long long g = (long long)fs + i;
+        x = cen[3 * g + 0]; y = cen[3 * g + 1]; z = cen[3 * g + 2];
     }
-}
-
-// bitonic sort of n2 (power of two >= cnt) entries of the LDS list, padding [cnt, n2) with +inf first; one wave
-template <bool kWave> __device__ void nn_sort(unsigned long long* sd, int* si, int cnt, int lane) {
-    int n2 = 64;
-    while (n2 < cnt) n2 <<= 1;
-    for (int i = cnt + lane; i < n2; i += 64) { sd[i] = ~0ull; si[i] = 0x7fffffff; }
-    nn_sync<kWave>();
-    for (int k = 2; k <= n2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = lane; t < n2 / 2; t += 64) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                const int l = i + j;
-                const bool up = (i & k) == 0;
-                const unsigned long long a = sd[i], c = sd[l];
-                const int ia = si[i], ic = si[l];
-                if (nn_less(c, ic, a, ia) == up) { sd[i] = c; sd[l] = a; si[i] = ic; si[l] = ia; }
-            }
-            nn_sync<kWave>();
-        }
-    }
-}
-
-// eigenvector of the smallest eigenvalue of a symmetric 3x3 matrix (cyclic Jacobi, fp64, registers only)
-__device__ void smallest_eigvec(double a00, double a01, double a02, double a11, double a12, double a22, double& nx, double& ny, double& nz) {
-    double A[3][3] = {{a00, a01, a02}, {a01, a11, a12}, {a02, a12, a22}};
-    double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-    for (int sweep = 0; sweep < 24; ++sweep) {
-        if (A[0][1] == 0.0 && A[0][2] == 0.0 && A[1][2] == 0.0) break;
-#pragma unroll
-        for (int pq = 0; pq < 3; ++pq) {
-            const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2;
-            if (A[p][q] != 0.0) {
-                const double theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
-                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-                for (int r = 0; r < 3; ++r) {          // A <- A J
-                    const double arp = A[r][p], arq = A[r][q];
-                    A[r][p] = c * arp - s * arq;
-                    A[r][q] = s * arp + c * arq;
-                }
-#pragma unroll
-                for (int r = 0; r < 3; ++r) {          // A <- J^T A
-                    const double apr = A[p][r], aqr = A[q][r];
-                    A[p][r] = c * apr - s * aqr;
-                    A[q][r] = s * apr + c * aqr;
-                }
-                A[p][q] = 0.0; A[q][p] = 0.0;
-#pragma unroll
-                for (int r = 0; r < 3; ++r) {          // V <- V J
-                    const double vrp = V[r][p], vrq = V[r][q];
-                    V[r][p] = c * vrp - s * vrq;
-                    V[r][q] = s * vrp + c * vrq;
-                }
-            }
-        }
-    }
-    int m = 0;
-    if (A[1][1] < A[m][m]) m = 1;
-    if (A[2][2] < (m == 0 ? A[0][0] : A[1][1])) m = 2;
-    nx = m == 0 ? V[0][0] : m == 1 ? V[0][1] : V[0][2];
-    ny = m == 0 ? V[1][0] : m == 1 ? V[1][1] : V[1][2];
-    nz = m == 0 ? V[2][0] : m == 1 ? V[2][1] : V[2][2];
-}
-
-// From the sorted candidate list of query v to its stored normal (one wave; rank t in lane t): the neighbour outputs, the mean and the
-// six covariance sums by the wave_sum butterfly, the eigenvector, the orientation rule.  Shared by both normals kernels.
-__device__ __forceinline__ void normal_from_list(const double* __restrict__ cen, const int* si, int cnt, int max_nn, int fs, int v, int lane,
-                                                 float* __restrict__ normals, int* __restrict__ nn_count, int* __restrict__ nn_idx) {
-    const int k = cnt < max_nn ? cnt : max_nn;
-    if (nn_idx)
-        for (int t = lane; t < max_nn; t += 64) nn_idx[(long long)v * max_nn + t] = t < k ? si[t] : -1;
-    if (nn_count && lane == 0) nn_count[v] = k;
-    double px = 0.0, py = 0.0, pz = 0.0;
-    if (lane < k) {
-        const long long g = (long long)fs + si[lane];
-        px = cen[3 * g + 0]; py = cen[3 * g + 1]; pz = cen[3 * g + 2];
-    }
-    const double dk = (double)k;
-    const double mx = wave_sum(px) / dk, my = wave_sum(py) / dk, mz = wave_sum(pz) / dk;
-    const double ex = lane < k ? px - mx : 0.0, ey = lane < k ? py - my : 0.0, ez = lane < k ? pz - mz : 0.0;
-    const double cxx = wave_sum(ex * ex), cxy = wave_sum(ex * ey), cxz = wave_sum(ex * ez);
-    const double cyy = wave_sum(ey * ey), cyz = wave_sum(ey * ez), czz = wave_sum(ez * ez);
-    double nx = 0.0, ny = 0.0, nz = 0.0;
-    if (k >= 3 && (cxx != 0.0 || cxy != 0.0 || cxz != 0.0 || cyy != 0.0 || cyz != 0.0 || czz != 0.0))
-        smallest_eigvec(cxx, cxy, cxz, cyy, cyz, czz, nx, ny, nz);
-    // orient_normals_to_align_with_direction([0,0,1]): a zero normal becomes the direction, n . dir < 0 flips
-    if (nx == 0.0 && ny == 0.0 && nz == 0.0) { nz = 1.0; }
-    else if (nz < 0.0) { nx = -nx; ny = -ny; nz = -nz; }
-    if (lane == 0) {
-        normals[3 * (long long)v + 0] = (float)nx; normals[3 * (long long)v + 1] = (float)ny; normals[3 * (long long)v + 2] = (float)nz;
-    }
-}
+};
 
 // One wave (workgroup of 64) per query centroid, persistent over the batch.  The 27 neighbour cells (9 key ranges of 3 z-adjacent cells)
 // are located by binary search in the frame's cell-sorted keys (18 lanes in parallel), their members streamed 64 at a time; candidates with d2 < r2 that beat the
@@ -458,7 +335,7 @@ __global__ __launch_bounds__(64) void normals_kernel(const double* __restrict__ 
             }
         }
         nn_sort<false>(sd, si, cnt, lane);
-        normal_from_list(cen, si, cnt, max_nn, fs, v, lane, normals, nn_count, nn_idx);
+        normal_from_list(CentroidPos{cen, fs}, si, cnt, max_nn, v, lane, 2, 1, normals, nn_count, nn_idx);          // Open3D's direction [0,0,1]
         __syncthreads();
     }
 }
@@ -481,24 +358,6 @@ __global__ __launch_bounds__(256) void cell_starts_kernel(const int* __restrict_
     const int nvox = min(max(*nvox_p, 0), cap);
     if (j < nvox && head[j]) cstart[scan[j]] = j;
     if (j == nvox) { cstart[scan[j]] = nvox; *ncell = scan[j]; }
-}
-
-// One candidate of one wave's query: the per-query kernel's acceptance rule and list handling on the wave's own LDS list.
-__device__ __forceinline__ void nn_offer(bool in, double d2, int li, double r2, int max_nn, unsigned long long* sd, int* si, int& cnt,
-                                         unsigned long long& thr_d, int& thr_i, int lane) {
-    const unsigned long long db = (unsigned long long)__double_as_longlong(d2);
-    const bool acc = in && d2 < r2 && nn_less(db, li, thr_d, thr_i);
-    const unsigned long long m = __ballot(acc);
-    if (acc) {
-        const int pos = cnt + __popcll(m & ((1ull << lane) - 1));
-        sd[pos] = db; si[pos] = li;
-    }
-    cnt += __popcll(m);
-    if (cnt > CELL_NN_CAP - 64) {       // (> max_nn: always cut back)
-        nn_sort<true>(sd, si, cnt, lane);
-        if (cnt >= max_nn) { thr_d = sd[max_nn - 1]; thr_i = si[max_nn - 1]; cnt = max_nn; }
-        nn_sync<true>();
-    }
 }
 
 // One workgroup (CELL_WAVES waves) per occupied grid cell, persistent over the batch.  Once per cell: the 9 key ranges of the 27 neighbour
@@ -589,7 +448,7 @@ __global__ __launch_bounds__(CELL_WAVES * 64) void normals_cells_kernel(const do
                 }
             }
             nn_sort<true>(sd, si, cnt, lane);
-            normal_from_list(cen, si, cnt, max_nn, fs, v, lane, normals, nn_count, nn_idx);
+            normal_from_list(CentroidPos{cen, fs}, si, cnt, max_nn, v, lane, 2, 1, normals, nn_count, nn_idx);          // Open3D's direction [0,0,1]
             nn_sync<true>();
         }
         __syncthreads();          // the next cell's staging overwrites what the other waves may still read

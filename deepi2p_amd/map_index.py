@@ -2,9 +2,11 @@
 over it, and the crop of one disc per camera frame around a rough pose prior (GPS and a compass, or the last frame's pose).
 
   MapIndex.build   once per map, eager      cell of every row -> stable sort -> cell_start, order, sorted             di2p_map_index_build
+  estimate_normals once per map, eager      3-D cell keys -> stable sort -> radius-bounded kNN -> PCA normal of every row  di2p_map_normals
   MapIndex.crop    per batch, allocating    frame -> window cells -> rows inside the disc, in the prior frame         di2p_map_crop
-  CropPlan         per batch, graph-safe    the same, preallocated: the priors and radii are read from device memory
-  MapRawPlan       CropPlan + sample_prep.SamplePlan(dataset="oxford" | "nuscenes"): priors and camera frames to the loader's sample
+  CropPlan         per batch, graph-safe    the same, preallocated: the priors and radii are read from device memory;
+                                            want_normals: the map's normals of the kept rows, R^T n, behind the crop     di2p_map_crop_normals
+  MapRawPlan       CropPlan + sample_prep.SamplePlan(dataset="oxford" | "nuscenes" | "kitti"): priors and camera frames to the loader's sample
   map_pose         T_map_cam = T_map_prior . P_scan^-1                                                                di2p_map_pose
 
 The map is f32[M,4] rows (x, y, z, intensity) in a map frame.  Coordinates are float32: the caller keeps them small, relative to a map origin
@@ -14,6 +16,12 @@ other two in ascending order: camera-convention maps (y down, the Oxford record)
 dx^2 + dy^2 < radius^2 on the ground plane around the prior's translation (strict, as the Oxford loader's range filter) and gets them in the
 PRIOR frame, R^T (p - t).  The arithmetic is fp64 with every operation rounded once, so the tests restate it in numpy bit for bit.
 
+The KITTI model reads surface normals (`sn`), so a map it is to be localised in carries one normal per row: MapIndex.build(..., normals=...)
+takes the user's own f32[M,3] (Open3D's, computed offline) or computes them with estimate_normals -- scan_prep.estimate_normals' rule (the
+at most max_nn nearest rows inside `radius`, PCA, oriented along orient . e_up_axis) on the whole map as one cloud.  Normals are computed
+once per map, as the index is; a step gathers 12 more bytes per kept row.  A raw, unthinned map can hold its 30 nearest rows within 0.6 m in
+a very small patch: thin the map first (a voxel pass), as the KITTI records are.
+
 status per frame: 0 ok, 1 more than max_frame_points kept rows (or more than the capacity, or a window of more than max_cells cells), 2 (voxel
 pass of the sample stage) bounding box above its limit, 4 no kept row (also a disc off the map), 5 a non-finite prior or a radius that is not
 finite and positive.  A frame with a status has no rows and leaves the others as they are without it.
@@ -21,13 +29,15 @@ finite and positive.  A frame with a status has no rows and leaves the others as
 import numpy as np
 import torch
 
-from . import _ragged, sample_prep, scan_prep
+from . import _lib, _ragged, sample_prep, scan_prep
 from ._lib import DeepI2PHipError, call, ptr, require_cuda, stream
 from ._ragged import _dev
 
 MAX_FRAME_POINTS = scan_prep.MAX_FRAME_POINTS
 MAX_ROWS, MAX_CELLS = 1 << 27, 1 << 24
 RIGID_TOL = 1e-6          # largest |R^T R - I| entry a prior checked on the host may have
+NORMALS_RADIUS, NORMALS_MAX_NN, NORMALS_NN_LIMIT = 0.6, 30, 64          # the offline KITTI script's radius and max_nn; the kernel's limit
+_NORMALS_STATUS = {1: "the map has a non-finite coordinate", 2: "an edge of the map's bounds is above radius * (2^21 - 4)"}
 _STATUS = dict(scan_prep._STATUS)
 _STATUS.update({1: "more than max_frame_points kept rows, more than the capacity, or a window of more than max_cells cells",
                 4: "no map row inside the disc", 5: "non-finite prior, or a radius that is not finite and positive"})
@@ -56,6 +66,71 @@ def _check_grid(nx, ny):
     if nx < 1 or ny < 1 or nx * ny > MAX_CELLS:
         raise ValueError("map_index: the grid must have nx, ny >= 1 and nx * ny <= 2^24 cells, got %d x %d (a larger cell?)" % (nx, ny))
     return nx, ny
+
+
+def _check_points(points):
+    """host array or tensor -> float32 tensor [M,4] with 1 <= M <= 2^27 (ValueError otherwise)"""
+    if not torch.is_tensor(points):
+        arr = np.asarray(points)
+        if arr.dtype != np.float32:
+            raise ValueError("map_index: points must be float32 [M, 4] (x, y, z, intensity), got %s" % arr.dtype)
+        points = torch.from_numpy(np.ascontiguousarray(arr))
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4:
+        raise ValueError("map_index: points must be float32 [M, 4] (x, y, z, intensity), got %s %s" % (points.dtype, list(points.shape)))
+    M = int(points.shape[0])
+    if M < 1 or M > MAX_ROWS:
+        raise ValueError("map_index: a map has 1 to 2^27 rows, got %d" % M)
+    return points
+
+
+def _check_normals_args(radius, max_nn, up_axis, orient):
+    ground_axes(up_axis)
+    radius = float(radius)
+    if not (radius > 0.0 and np.isfinite(radius)):
+        raise ValueError("map_index: the normals' radius must be a finite number > 0 (metres)")
+    if int(max_nn) != max_nn or not 1 <= int(max_nn) <= NORMALS_NN_LIMIT:
+        raise ValueError("map_index: the normals' max_nn must be an integer in [1, %d], got %r" % (NORMALS_NN_LIMIT, max_nn))
+    if orient not in (1, -1):
+        raise ValueError("map_index: orient must be +1 or -1 (the sign of the up axis the normals point along), got %r" % (orient,))
+    return radius, int(max_nn), int(up_axis), int(orient)
+
+
+def _check_normals(normals, M):
+    """the user's own normals -> float32 tensor [M,3], as given (ValueError for another dtype or shape)"""
+    t = normals if torch.is_tensor(normals) else None
+    if t is None:
+        arr = np.asarray(normals)
+        if arr.dtype != np.float32:
+            raise ValueError("map_index: normals must be float32 [%d, 3] (one per map row), got %s" % (M, arr.dtype))
+        t = torch.from_numpy(np.ascontiguousarray(arr))
+    if t.dtype != torch.float32 or tuple(t.shape) != (M, 3):
+        raise ValueError("map_index: normals must be float32 [%d, 3] (one per map row), got %s %s" % (M, t.dtype, list(t.shape)))
+    return t
+
+
+def estimate_normals(points, radius=NORMALS_RADIUS, max_nn=NORMALS_MAX_NN, up_axis=2, orient=1, want_neighbors=False, device=None):
+    """points f32[M,4] (host array or tensor, any device) -> normals f32[M,3] on `device`, row i the normal of row i (+ nn_count i32[M] and
+    nn_idx i32[M,max_nn], -1 past the count, with want_neighbors).  scan_prep.estimate_normals' rule on the map as one cloud: the at most max_nn
+    rows inside `radius` in ascending (d2, row), the row itself included; the eigenvector of the smallest eigenvalue of their covariance,
+    flipped so that orient * n[up_axis] >= 0; orient * e_up_axis below 3 neighbours.  orient=-1 for camera-convention maps (up is -y).
+    ValueError for bad arguments before anything touches the device; DeepI2PHipError for a non-finite coordinate or bounds above
+    radius * (2^21 - 4) (one synchronisation)."""
+    points = _check_points(points)
+    radius, max_nn, up_axis, orient = _check_normals_args(radius, max_nn, up_axis, orient)
+    M = int(points.shape[0])
+    dev = device or (points.device if points.is_cuda else _dev())
+    pts = points.to(dev).contiguous()
+    normals = torch.zeros((M, 3), dtype=torch.float32, device=dev)
+    cnt = torch.zeros((M,), dtype=torch.int32, device=dev) if want_neighbors else None
+    idx = torch.zeros((M, max_nn), dtype=torch.int32, device=dev) if want_neighbors else None
+    status = torch.zeros((1,), dtype=torch.int32, device=dev)
+    ws = torch.empty((max(256, int(_lib.load().di2p_map_normals_workspace_bytes(M))),), dtype=torch.uint8, device=dev)
+    require_cuda(pts)
+    call("di2p_map_normals", ptr(pts), M, up_axis, orient, radius, max_nn, ptr(normals), ptr(cnt), ptr(idx), ptr(status), ptr(ws), stream())
+    st = int(status.item())
+    if st != 0:
+        raise DeepI2PHipError("map_index: estimate_normals: %s" % _NORMALS_STATUS.get(st, "status %d" % st))
+    return (normals, cnt, idx) if want_neighbors else normals
 
 
 def check_priors(T_map_prior, B=None, name="T_map_prior", prefix="map_index"):
@@ -107,10 +182,11 @@ def max_window_cells(index, max_radius):
 
 class MapIndex:
     """The resident map: sorted f32[M,4] (the rows cell after cell, inside a cell in map-row order), cell_start i32[nx ny + 1], order i32[M]
-    (the map row of every stored row), and the grid (origin, cell, nx, ny, up_axis).  Built by MapIndex.build; never modified afterwards."""
+    (the map row of every stored row), and the grid (origin, cell, nx, ny, up_axis); normals f32[M,3] | None in MAP-ROW order (row i belongs
+    to row i of the points given to build: what the crop's `index` output addresses).  Built by MapIndex.build; never modified afterwards."""
 
-    def __init__(self, sorted_rows, cell_start, order, origin, cell, nx, ny, up_axis):
-        self.sorted, self.cell_start, self.order = sorted_rows, cell_start, order
+    def __init__(self, sorted_rows, cell_start, order, origin, cell, nx, ny, up_axis, normals=None):
+        self.sorted, self.cell_start, self.order, self.normals = sorted_rows, cell_start, order, normals
         self.origin, self.cell, self.nx, self.ny, self.up_axis = (float(origin[0]), float(origin[1])), float(cell), int(nx), int(ny), int(up_axis)
         self.M, self.device = int(order.shape[0]), sorted_rows.device
 
@@ -118,23 +194,27 @@ class MapIndex:
         return (self.M, self.up_axis, self.origin[0], self.origin[1], self.cell, self.nx, self.ny)
 
     @staticmethod
-    def build(points, cell=8.0, up_axis=1, origin=None, device=None, shape=None):
+    def build(points, cell=8.0, up_axis=1, origin=None, device=None, shape=None, normals=None):
         """points f32[M,4] (host array or tensor, any device) -> MapIndex on `device`.  origin=None: origin = floor(min / cell) cell on the
         two ground axes and (nx, ny) from the map's own extent; with an origin, shape=(nx, ny) or again the extent.  Raises ValueError for bad
         arguments before anything touches the device, DeepI2PHipError for a non-finite coordinate or a row outside the grid (one
-        synchronisation)."""
+        synchronisation).  normals: None (index.normals is None: the Oxford and nuScenes models); a float32 [M,3] array or tensor, the
+        user's own normals, stored as given; or True / a dict of radius, max_nn, orient: estimate_normals on the points (orient defaults
+        to -1 for up_axis=1, camera-convention maps, else +1).  The KITTI model needs them."""
         a, b = ground_axes(up_axis)
         cell = _check_cell(cell)
-        if not torch.is_tensor(points):
-            arr = np.asarray(points)
-            if arr.dtype != np.float32:
-                raise ValueError("map_index: points must be float32 [M, 4] (x, y, z, intensity), got %s" % arr.dtype)
-            points = torch.from_numpy(np.ascontiguousarray(arr))
-        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4:
-            raise ValueError("map_index: points must be float32 [M, 4] (x, y, z, intensity), got %s %s" % (points.dtype, list(points.shape)))
+        points = _check_points(points)
         M = int(points.shape[0])
-        if M < 1 or M > MAX_ROWS:
-            raise ValueError("map_index: a map has 1 to 2^27 rows, got %d" % M)
+        own, estimate = None, None
+        if normals is True or isinstance(normals, dict):
+            estimate = {} if normals is True else dict(normals)
+            unknown = set(estimate) - {"radius", "max_nn", "orient"}
+            if unknown:
+                raise ValueError("map_index: normals=dict(...) takes radius, max_nn and orient, got %s" % sorted(unknown))
+            estimate = _check_normals_args(estimate.get("radius", NORMALS_RADIUS), estimate.get("max_nn", NORMALS_MAX_NN), up_axis,
+                                           estimate.get("orient", -1 if up_axis == 1 else 1))
+        elif normals is not None and normals is not False:
+            own = _check_normals(normals, M)
         if origin is not None:
             origin = np.asarray(origin, dtype=np.float64)
             if origin.shape != (2,) or not np.isfinite(origin).all():
@@ -166,13 +246,18 @@ class MapIndex:
         if int(status.item()) != 0:
             raise DeepI2PHipError("map_index: the map has a non-finite coordinate or a row outside the %d x %d grid at origin (%g, %g)"
                                   % (nx, ny, origin[0], origin[1]))
-        return MapIndex(sorted_rows, cell_start, order, origin, cell, nx, ny, up_axis)
+        if estimate is not None:
+            own = estimate_normals(pts, estimate[0], estimate[1], estimate[2], estimate[3], device=dev)
+        elif own is not None:
+            own = own.to(dev).contiguous()
+        return MapIndex(sorted_rows, cell_start, order, origin, cell, nx, ny, up_axis, own)
 
-    def crop(self, T_map_prior, radius, max_frame_points, cap=None, want_index=False, max_cells=None):
+    def crop(self, T_map_prior, radius, max_frame_points, cap=None, want_index=False, max_cells=None, want_normals=False):
         """Eager: T_map_prior [B,4,4], radius a number or [B] (host values, checked here; or f64 device tensors, checked on the device) ->
         (rows f32[cap,4] in each frame's prior frame, offsets i32[B+1], status i32[B][, index i32[cap]: the map row of every kept row]).
         cap: rows of the whole batch (default B * max_frame_points); max_cells: window cells per frame the workspace is sized for (default:
-        the whole grid).  No synchronisation."""
+        the whole grid).  want_normals appends normals f32[cap,3], the map's normals of the kept rows in the prior frame (R^T n; the index
+        must carry normals).  No synchronisation."""
         mfp = _ragged._check_max_frame_points("map_index", max_frame_points)
         T, r = _checked_priors(T_map_prior, radius, None)
         B = int(T.shape[0])
@@ -180,19 +265,23 @@ class MapIndex:
         max_cells = self.nx * self.ny if max_cells is None else int(max_cells)
         if cap < 0 or max_cells < 1:
             raise ValueError("map_index: cap must be >= 0 and max_cells >= 1")
-        plan = CropPlan(self, B, cap, mfp, None, want_index=want_index, max_cells=max_cells)
+        plan = CropPlan(self, B, cap, mfp, None, want_index=want_index, max_cells=max_cells, want_normals=want_normals)
         out = plan.run(T.to(self.device), r.to(self.device))
-        return out[:3] + ((plan.index,) if want_index else ())
+        return out[:3] + ((plan.index,) if want_index else ()) + ((plan.normals,) if want_normals else ())
 
 
 class CropPlan:
     """Fixed-capacity, preallocated form of MapIndex.crop: run() launches di2p_map_crop on the current stream with no allocation and no host
     synchronisation, so it can be captured in a hipGraph; a replay reads the priors and radii the tensors hold THEN.  cap: rows of the whole
-    batch; max_frame_points: of one frame; max_radius: the largest radius a frame will ask for (a wider window: status 1)."""
+    batch; max_frame_points: of one frame; max_radius: the largest radius a frame will ask for (a wider window: status 1).  want_normals: the
+    index must carry normals; run() then launches di2p_map_crop_normals behind the crop and fills plan.normals f32[cap,3], row k the normal of
+    kept row k in its frame's prior frame (rows past offsets[B] keep what they held); run() returns the same three tensors."""
 
-    def __init__(self, index, B, cap, max_frame_points, max_radius, want_index=False, max_cells=None):
+    def __init__(self, index, B, cap, max_frame_points, max_radius, want_index=False, max_cells=None, want_normals=False):
         if not isinstance(index, MapIndex):
             raise ValueError("map_index: index must be a MapIndex (MapIndex.build)")
+        if want_normals and index.normals is None:
+            raise ValueError("map_index: want_normals needs an index that carries normals (MapIndex.build(..., normals=...))")
         self.max_src = _ragged._check_max_frame_points("map_index", max_frame_points)
         if int(B) < 0 or int(cap) < 0:
             raise ValueError("map_index: B and cap must be >= 0")
@@ -206,7 +295,8 @@ class CropPlan:
         self.rows = torch.zeros((max(self.cap, 1), 4), dtype=torch.float32, device=dev)
         self.offsets = torch.zeros((self.B + 1,), dtype=torch.int32, device=dev)
         self.status = torch.zeros((b,), dtype=torch.int32, device=dev)
-        self.index = torch.zeros((max(self.cap, 1),), dtype=torch.int32, device=dev) if want_index else None
+        self.index = torch.zeros((max(self.cap, 1),), dtype=torch.int32, device=dev) if want_index or want_normals else None
+        self.normals = torch.zeros((max(self.cap, 1), 3), dtype=torch.float32, device=dev) if want_normals else None
 
     def run(self, T_map_prior, radius):
         """T_map_prior f64[B,4,4], radius f64[B] (device) -> (rows f32[cap,4], offsets i32[B+1], status i32[B]), views of the plan's buffers"""
@@ -216,6 +306,9 @@ class CropPlan:
         require_cuda(T_map_prior, radius)
         call("di2p_map_crop", ptr(ix.sorted), ptr(ix.cell_start), ptr(ix.order), *ix._grid_args(), ptr(T_map_prior), ptr(radius), B, self.cap,
              self.max_src, self.max_cells, ptr(self.rows), ptr(self.offsets), ptr(self.index), ptr(self.status), ptr(self.ws), stream())
+        if self.normals is not None:
+            call("di2p_map_crop_normals", ptr(ix.normals), ptr(self.index), ptr(self.offsets), ptr(T_map_prior), B, self.cap, ptr(self.normals),
+                 stream())
         return self.rows, self.offsets, self.status[:B]
 
 
@@ -231,10 +324,13 @@ def map_pose(T_map_prior, P_scan, out=None):
     return out
 
 
-def _check_dataset(dataset):
-    if dataset not in ("oxford", "nuscenes"):
-        raise ValueError("map_index: dataset must be 'oxford' or 'nuscenes' (the KITTI model wants normals; per-crop normals are out of scope), got %r"
-                         % (dataset,))
+def _check_dataset(dataset, index=None):
+    """`index`: the map the data set's model is to be localised in; the KITTI model reads normals, so its map must carry them"""
+    if dataset not in ("oxford", "nuscenes", "kitti"):
+        raise ValueError("map_index: dataset must be 'oxford', 'nuscenes' or 'kitti', got %r" % (dataset,))
+    if dataset == "kitti" and getattr(index, "normals", None) is None:
+        raise ValueError("map_index: dataset 'kitti': the KITTI model reads normals, so a KITTI map needs MapIndex.build(..., normals=...) "
+                         "(True, a dict of radius / max_nn / orient, or the user's own f32[M,3])")
 
 
 class MapRawPlan:
@@ -243,10 +339,10 @@ class MapRawPlan:
     points.  The result equals CropPlan.run followed by sample_prep.SamplePlan.run bit for bit."""
 
     def __init__(self, index, opt, B, cap, max_frame_points, max_radius, raw_hw, mode="val", dataset="oxford", jitter=sample_prep.JITTER, color=None):
-        _check_dataset(dataset)
+        _check_dataset(dataset, index)
         _ragged._check_max_frame_points("map_index", max_frame_points)
         sample_prep.option_block(opt, sample_prep.RAW_HW[dataset] if raw_hw is None else raw_hw, mode, dataset=dataset)      # argument errors first
-        self.crop = CropPlan(index, B, cap, max_frame_points, max_radius)
+        self.crop = CropPlan(index, B, cap, max_frame_points, max_radius, want_normals=dataset == "kitti")
         self.sample = sample_prep.SamplePlan(opt, B, int(cap), int(max_frame_points), raw_hw, mode, index.device, jitter=jitter, color=color,
                                              dataset=dataset)
         self.B = int(B)
@@ -268,7 +364,7 @@ class MapRawPlan:
         of the crop's and the sample's.  seed=None leaves the seed slot as it is (graph replays)."""
         sample_prep._check_images(images_u8, self.B, self.sample.image.raw_hw)
         rows, offsets, _ = self.crop.run(T_map_prior, radius)
-        out = self.sample.run(rows, None, offsets, images_u8, K_raw, P_cam_pc, seed=seed)
+        out = self.sample.run(rows, self.crop.normals, offsets, images_u8, K_raw, P_cam_pc, seed=seed)          # KITTI: P_cam_pc for Pc, no Pji
         torch.maximum(self.crop.status, self.sample.status, out=self.status)
         return tuple(out) + (self.status[:self.B], self.T_scan)
 
@@ -276,7 +372,7 @@ class MapRawPlan:
 def prepare_map_raw(index, T_map_prior, radius, images, K_raw, P_cam_pc, opt, max_frame_points, mode="val", seed=0, dataset="oxford", cap=None):
     """Convenience: builds a plan for this batch, runs it and checks the status (synchronises).  T_map_prior [B,4,4], radius a number or [B],
     images u8[B,H0,W0,3], K_raw [B,3,3], P_cam_pc [B,4,4] (host values) -> MapRawPlan.run's tuple."""
-    _check_dataset(dataset)
+    _check_dataset(dataset, index)
     T = check_priors(T_map_prior)
     B = int(T.shape[0])
     r = check_radius(radius, B)

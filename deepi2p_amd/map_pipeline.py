@@ -65,8 +65,9 @@ class MapFrameExecutor(PreparedFrameExecutor):
     out = executor.result(ticket)                 # the base executor's outputs + status i32[B], T_scan, P_scan, T_map_prior, T_map_cam f64[B,4,4]
 
     index: the map_index.MapIndex the frames are localised in.  opt: the option bag of sample_prep(dataset) (img_H / img_W / input_pt_num /
-    node numbers must be the classifier's); dataset "oxford" (camera-convention maps, up_axis=1, pipeline frame="cam") or "nuscenes" (z-up
-    maps, up_axis=2, frame="enu").  Fixed per executor: B, the raw image shape, cap (kept rows of the whole batch), max_frame_points (a frame
+    node numbers must be the classifier's); dataset "oxford" (camera-convention maps, up_axis=1, pipeline frame="cam"), "nuscenes" (z-up
+    maps, up_axis=2, frame="enu") or "kitti" (the index must carry normals, MapIndex.build(..., normals=...): the crop rotates them into
+    the prior frame and the KITTI sample stage hands the classifier its `sn`).  Fixed per executor: B, the raw image shape, cap (kept rows of the whole batch), max_frame_points (a frame
     that keeps more rows is rejected ON THE DEVICE: status != 0, its pose is whatever the solver makes of zeros, the other frames are
     unaffected) and max_radius (the crop's window workspace).  P_scan = P . T_scan maps PRIOR-frame coordinates into the camera frame, so
     T_map_cam = T_map_prior . P_scan^-1 is the camera's pose in the map.
@@ -82,7 +83,7 @@ class MapFrameExecutor(PreparedFrameExecutor):
                  samples=None, labels_override=None, mode="val", dataset="oxford", h2d_mode="copy_stream", post_fn=None, evaluate=False,
                  visualize=None, confidence=False):
         self._check_h2d_mode(h2d_mode)
-        map_index._check_dataset(dataset)
+        map_index._check_dataset(dataset, index)
         _ragged._check_max_frame_points("map_index", max_frame_points)
         if not isinstance(index, map_index.MapIndex):
             raise ValueError("MapFrameExecutor: index must be a map_index.MapIndex (MapIndex.build)")
@@ -133,7 +134,9 @@ class MapFrameExecutor(PreparedFrameExecutor):
         return plan.run(d["T_map_prior"].view(self.B, 4, 4), d["radius"], d["image"], d["K_raw"], d["P_cam_pc"], seed=None)
 
     def _normals(self, plan):
-        return plan.sample.sn          # a crop has no normals: the plan's zero buffer
+        if self.dataset == "kitti":
+            return plan.sample.points.sn          # the crop's normals through the KITTI sample stage, as RawFrameExecutor's
+        return plan.sample.sn          # the Oxford and nuScenes models read no normals: the plan's zero buffer
 
     def _map_pose(self, slot):
         call("di2p_map_pose", ptr(slot.T_map_prior), ptr(slot.P_scan), self.B, ptr(slot.T_map_cam), stream())

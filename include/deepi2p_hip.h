@@ -910,6 +910,29 @@ int di2p_map_crop(const float* sorted, const int32_t* cell_start, const int32_t*
                   int max_cells, float* rows, int32_t* offsets, int32_t* index, int32_t* status, void* workspace, void* stream);
 int di2p_map_pose(const double* T_map_prior, const double* P_scan, int n, double* T_map_cam, void* stream);
 
+/* ---- (additive, ABI 9; detect by symbol) normals of a map and crops that carry them (csrc/map_normals.hip, csrc/map_index.hip): the KITTI model ----
+ * di2p_map_normals, eager, once per map; refuses (returns -1, nothing enqueued, the capture stays usable) while `stream` is capturing.
+ *   di2p_estimate_normals' definition with the map as one frame and the row itself as the point: points f32[M,4], 1 <= M <= 2^27, radius
+ *   finite and > 0, 1 <= max_nn <= 64, up_axis in {0, 1, 2}, orient +1 or -1 (-1 for camera-convention maps, where up is -y).
+ *   Neighbours of row q: the at most max_nn rows j with d2 < radius^2, q included, d2 = ((dx dx + dy dy) + dz dz) in fp64 on (double) of the
+ *   float32 coordinates, taken in ascending (d2, j), j the row number in `points`; exact whatever the density; duplicated rows are distinct
+ *   neighbours.  Normal: the eigenvector of the smallest eigenvalue of the neighbours' covariance (butterfly sums, cyclic Jacobi, fp64);
+ *   orient . e_up_axis for fewer than 3 neighbours or a zero covariance; otherwise flipped so that orient . n[up_axis] >= 0.  With
+ *   up_axis 2, orient +1 the outputs are di2p_estimate_normals' bit for bit on the same points (one implementation: csrc/normals_nn.h).
+ *   The grid: cell edge radius (1 + 2^-20) over the map's own bounds, 21 bits per axis in a 63-bit key, a stable radix sort of (key, row).
+ *   -> normals f32[M,3], nn_count i32[M] (may be NULL), nn_idx i32[M,max_nn] (may be NULL; -1 past the count), all in the order of the rows
+ *   given; status i32[1]: 0; 1 a non-finite coordinate; 2 a bounds edge above radius (2^21 - 4).  With a status nothing else is written.
+ *   workspace: di2p_map_normals_workspace_bytes(M) bytes (0 for a bad size; about 64 M), 256-byte aligned; points 16-byte aligned.
+ * di2p_map_crop_normals, one launch behind di2p_map_crop, no allocation, no synchronisation, no memset node, no atomics; offsets (the crop's)
+ *   and T_map_prior are read from device memory inside the launch.  For every kept row k < offsets[B] of frame b, with
+ *   n = (double)normals[index[k]] (normals f32[M,3] in map-row order, index the crop's):
+ *   out[k][i] = (float)((T[0][i] n0 + T[1][i] n1) + T[2][i] n2), R^T n, every operation rounded once.  Rows past offsets[B] are not written. */
+long long di2p_map_normals_workspace_bytes(int M);
+int di2p_map_normals(const float* points, int M, int up_axis, int orient, double radius, int max_nn, float* normals, int32_t* nn_count,
+                     int32_t* nn_idx, int32_t* status, void* workspace, void* stream);
+int di2p_map_crop_normals(const float* normals, const int32_t* index, const int32_t* offsets, const double* T_map_prior, int B, int cap, float* out,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,8 +4,12 @@ eager and as a graph replay) at M = 2^22 and 2^24 map rows, B = 32 priors, r = 5
 run on the device: B passes of scan_prep.range_shuffle (the Oxford loader's range filter) over the WHOLE map, the map cut into frames of
 2^20 rows because that is the filter's limit per frame.  Then frames/s of map_pipeline.MapFrameExecutor next to
 submap_pipeline.OxfordFrameExecutor at the same B and N, timed alternately in one process.
+--normals adds, at both sizes, map_index.estimate_normals (radius 0.6, max_nn 30) next to scan_prep.estimate_normals(method="cells") on the
+same rows cut into frames of 2^20 (it loses the neighbours across the cuts: context, not a target), and the crop that carries normals
+(CropPlan(want_normals=True)) next to the plain crop.  --dataset kitti adds MapFrameExecutor(dataset="kitti") with the KITTI model (20480
+points, 160 x 512 images from 370 x 1226 frames) on the same map with normals.
     python tools/bench_map.py [--B 32] [--radius 50] [--cell 8] [--sizes 22 24] [--reps 20] [--warmup 3] [--streams 2] [--steps 20]
-                              [--rounds 3] [--no-executor] [--coarse]
+                              [--rounds 3] [--no-executor] [--coarse] [--normals] [--dataset kitti]
 The street (synthetic.make_map) is as long as it takes for a 50 m disc to hold about 2^18 of the map's rows: 1.6 km at 2^22, 6.4 km at 2^24.
 Bytes: the rows of the window cells a crop visits x 16, counted on the host from cell_start; the count and the write pass each read them."""
 import argparse
@@ -108,7 +112,44 @@ def bench_size(log2m, a, dev):
     print("  crop, graph replay          %9.3f ms (min %.3f, max %.3f) = %.2f TB/s of window-cell rows read once (%.1f %% of 8 TB/s; both passes read them)"
           % (replay + (res["window_bytes_per_s"] / 1e12, 100 * res["share_of_hbm_peak"])))
     print("  %d whole-map filter passes  %9.3f ms (min %.3f, max %.3f) = %.1f x the crop" % ((B,) + whole + (res["whole_map_over_crop"],)))
+    if a.normals or a.dataset == "kitti":
+        del out, ws
+        torch.cuda.empty_cache()
+        index = bench_normals(a, dev, pts, index, T, r, frames, off, res)
     return res, index, wm
+
+
+def bench_normals(a, dev, pts, index, T, r, frames, off, res):
+    """-> the index with normals; fills res with the times of estimate_normals, of the per-frame cells kernel and of the two crops"""
+    M, B = int(pts.shape[0]), a.B
+    reps = max(a.reps // 4, 3)
+    est = _ms(lambda: map_index.estimate_normals(pts, up_axis=1, orient=-1), reps, 1)
+    normals = map_index.estimate_normals(pts, up_axis=1, orient=-1)
+    index = map_index.MapIndex(index.sorted, index.cell_start, index.order, index.origin, index.cell, index.nx, index.ny, index.up_axis, normals)
+    res.update(normals_ms=est, normals_rows_per_s=M / (est[0] * 1e-3))
+    print("  estimate_normals            %9.3f ms (min %.3f, max %.3f) = %.1f M rows/s" % (est + (res["normals_rows_per_s"] / 1e6,)))
+    if a.normals:
+        # what there was before: the per-frame kernel on frames of 2^20 rows, every row a voxel of its own (2 mm voxels)
+        st = scan_prep.voxel_down_sample(pts, off, 0.002, max_frame_points=FILTER_FRAME)
+        cells = _ms(lambda: scan_prep.estimate_normals(st, method="cells"), reps, 1)
+        voxels = int(st.offsets[-1])
+        res.update(frame_cells_ms=cells, frame_cells_voxels=voxels, frame_cells_status=sorted(set(st.status.cpu().numpy().tolist())))
+        print("  per-frame cells kernel      %9.3f ms (min %.3f, max %.3f) on %d frames of 2^20 rows (%d voxels, status %s): neighbours lost at the cuts"
+              % (cells + (frames, voxels, res["frame_cells_status"])))
+        del st
+        torch.cuda.empty_cache()
+        mfp = map_index.MAX_FRAME_POINTS
+        for name, want in (("crop", False), ("crop_normals", True)):          # the plain crop again, in the same minute as the one with normals
+            plan = map_index.CropPlan(index, B, B * (1 << 19), mfp, a.radius, want_normals=want)
+            plan.run(T, r)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                plan.run(T, r)
+            res[name + "_again_replay_ms" if not want else name + "_replay_ms"] = t = _ms(g.replay, a.reps, a.warmup)
+            print("  %-27s %9.3f ms (min %.3f, max %.3f), graph replay, %d rows kept" % (("crop with normals" if want else "crop without normals",) + t
+                                                                                       + (int(plan.offsets[-1]),)))
+            del g, plan
+    return index
 
 
 def bench_executors(a, dev, index, wm):
@@ -121,12 +162,9 @@ def bench_executors(a, dev, index, wm):
     opt.device = dev
     mm = (MMClassiferCoarse if a.coarse else MMClassifer)(opt)
     mm.detector.load_state_dict(synthetic.synthetic_state_dict(opt))
-    if a.coarse:
-        from deepi2p_amd.registration import RegistrationPipeline
-        pipe = RegistrationPipeline(H, W, seed=0)
-    else:
-        from deepi2p_amd.registration_pnp import PnPPipeline
-        pipe = PnPPipeline(H, W, iterations=500, seed=0)
+    from deepi2p_amd.registration import RegistrationPipeline
+    from deepi2p_amd.registration_pnp import PnPPipeline
+    pipe = RegistrationPipeline(H, W, seed=0) if a.coarse else PnPPipeline(H, W, iterations=500, seed=0)
     draws = pipe.draw(B, dev)
     kw = dict(restarts=draws) if a.coarse else dict(samples=draws)
     rng = np.random.default_rng(1)
@@ -149,21 +187,41 @@ def bench_executors(a, dev, index, wm):
     oex = OxfordFrameExecutor(mm, pipe, opt, ohb, tp.S_cap, tp.P_cap, tp.P_cap, min(S * beams, submap.MAX_FRAME_POINTS), n_streams=a.streams,
                               skip_threshold=submap.VOXEL / 16.0, **kw)
     rates = {"map, resident": [], "map, with H2D": [], "oxford, resident": [], "oxford, with H2D": []}
+    kex = None
+    if a.dataset == "kitti":          # the KITTI model on the same map, which carries normals (bench_normals)
+        kH0, kW0 = sample_prep.RAW_HW["kitti"]
+        kopt = synthetic.OptLike(N, 160, 512, not a.coarse)
+        kopt.device = dev
+        kmm = (MMClassiferCoarse if a.coarse else MMClassifer)(kopt)
+        kmm.detector.load_state_dict(synthetic.synthetic_state_dict(kopt))
+        kpipe = RegistrationPipeline(160, 512, seed=0) if a.coarse else PnPPipeline(160, 512, iterations=500, seed=0)
+        kdraws = kpipe.draw(B, dev)
+        kimage = torch.from_numpy(np.stack([synthetic.make_camera_image(np.random.default_rng(b), kH0, kW0) for b in range(B)]))
+        khb = dict(hb, image=kimage)
+        kex = MapFrameExecutor(kmm, kpipe, kopt, index, khb, B * (1 << 19), map_index.MAX_FRAME_POINTS, a.radius, n_streams=a.streams,
+                               dataset="kitti", **(dict(restarts=kdraws) if a.coarse else dict(samples=kdraws)))
+        rates.update({"map kitti, resident": [], "map kitti, with H2D": []})
     for rnd in range(a.rounds + 1):                  # round 0 warms everything up and is dropped
         vals = {"map, resident": B * a.steps / mex.throughput(a.steps, a.warmup, False)[0],
                 "oxford, resident": B * a.steps / oex.throughput(a.steps, a.warmup, False)[0],
                 "map, with H2D": B * a.steps / mex.throughput(a.steps, a.warmup, True)[0],
                 "oxford, with H2D": B * a.steps / oex.throughput(a.steps, a.warmup, True)[0]}
+        if kex is not None:
+            vals.update({"map kitti, resident": B * a.steps / kex.throughput(a.steps, a.warmup, False)[0],
+                         "map kitti, with H2D": B * a.steps / kex.throughput(a.steps, a.warmup, True)[0]})
         if rnd:
             for k, v in vals.items():
                 rates[k].append(v)
     assert mex.use_graph and oex.use_graph, (mex.graph_error, oex.graph_error)
+    assert kex is None or kex.use_graph, kex.graph_error
     res = {k: float(np.median(v)) for k, v in rates.items()}
     for k, v in rates.items():
         print("  %-20s %8.1f frames/s = %7.3f ms per step of %d (median of %d rounds; min %.1f, max %.1f)"
               % (k, res[k], 1e3 * B / res[k], B, a.rounds, min(v), max(v)))
     print("  status map %s, oxford %s" % (sorted(set(mex.slots[0].prepared[9].cpu().numpy().tolist())),
                                           sorted(set(oex.slots[0].prepared[9].cpu().numpy().tolist()))))
+    if kex is not None:
+        print("  status map kitti %s" % sorted(set(kex.slots[0].prepared[9].cpu().numpy().tolist())))
     return dict(frames_per_s=res, spread={k: (min(v), max(v)) for k, v in rates.items()})
 
 
@@ -180,6 +238,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--no-executor", action="store_true")
     ap.add_argument("--coarse", action="store_true")
+    ap.add_argument("--normals", action="store_true", help="time estimate_normals and the crop with normals at every size")
+    ap.add_argument("--dataset", choices=["oxford", "kitti"], default="oxford", help="kitti: add the MapFrameExecutor(dataset='kitti') row")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_map.py measures on the GPU; there is none here")
